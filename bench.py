@@ -10,7 +10,13 @@ clip + fused AdamW over every parameter: nothing that contributes to the loss, a
 timed region (the last layer's prefix o_proj + MLP, whose output nothing reads, are dead values and not computed — see
 TRAIN_TFLOP_NEEDED_PER_SAMPLE).
 
-Extra objects on the same line:
+A plain run sets up, warms up, times the steps and prints the line (`ms_per_step` = one timed step).  `--dump-outputs DIR`
+writes what the last timed step computed to DIR/*.npy (float32, see `dump_outputs`); the inputs and weights are seeded, so two
+builds run with the same arguments can be compared array by array.
+
+Extra objects on the same line, measured only with `--full` (each takes runs of its own after the timed region):
+  ranks        — who took part: world size, device identities, per-rank step time (N > 1: also `comm`, the other partition).
+  trimmed_prompt — the same step with the prompt cut to the longest valid prompt of the batch (model.trim_prompt_padding).
   roofline     — the dominant kernel (gemm_bf16_kernel): achieved = algorithmic FLOPs (2 M N K of every launch; SURVEY.md
                  §8d: 14.04 TFLOP per sample per train step) / summed GEMM launch durations, measured with HIP events on
                  the launch stream over two further identical steps run right after the timed region (inside it the event
@@ -250,7 +256,8 @@ def cpu_baseline(batch: int = 32):
 
     from oracle import pi0_oracle as O
 
-    cores = min(os.cpu_count() or 1, 64)
+    # the cores this process may use (affinity / OMP_NUM_THREADS), not the machine's count: more threads than cores only slow it down
+    cores = min(len(os.sched_getaffinity(0)), int(os.environ.get("OMP_NUM_THREADS") or 64), 64)
     torch.set_num_threads(cores)
     t0 = time.time()
     # full vocabulary if the host has room: 4.14 B stored f32 parameters + gradients + two AdamW moments of the 3.35 B
@@ -455,6 +462,38 @@ def roofline_object(timer, timer_dual, timer_steps: int, B: int, ms_per_step: fl
     }
 
 
+DUMP_SAMPLE = 4096  # elements per parameter in the --dump-outputs samples (all of a parameter that has fewer)
+
+
+@torch.no_grad()
+def dump_outputs(out_dir: str, trainer, loss) -> None:
+    """What the last timed step computed, as float32 DIR/<name>.npy: `loss` (what train_step returns), `grad_norm` (the global
+    pre-clip gradient norm), and of this rank's shard of the updated state the same fixed, seeded sample of every parameter
+    (parameters in name order; positions drawn from a CPU generator seeded 0): `master` (the f32 weights after the update),
+    `exp_avg` (AdamW's first moment) and `grad` (the step's gradient).  `grad` leaves out the parameters whose gradient producer
+    accumulates into its slice (`_kai0_grad_accumulates`: the embedding table), because ShardedDataParallel.step zeroes those
+    slices after the update; `master` and `exp_avg` cover them.  About 30 MB at one GPU."""
+    import numpy as np
+
+    eng = trainer.engine
+    entries = sorted((n, b, o, p) for b in eng.buckets for n, p, o in zip(b.names, b.params, b.offsets))
+    g = torch.Generator().manual_seed(0)
+    picks = []
+    for _, b, o, p in entries:
+        n = p.numel()
+        idx = torch.arange(n) if n <= DUMP_SAMPLE else torch.randint(n, (DUMP_SAMPLE,), generator=g)
+        pos = idx + (o - b.lo)  # position in this rank's shard of the bucket
+        pos = pos[(pos >= 0) & (pos < b.shard)]
+        picks.append((b, pos.to(b.master.device), getattr(p, "_kai0_grad_accumulates", False)))
+    arrays = {"loss": loss.reshape(1), "grad_norm": trainer.last_grad_norm.reshape(-1),
+              "master": torch.cat([b.master[pos] for b, pos, _ in picks]),
+              "exp_avg": torch.cat([b.exp_avg[pos] for b, pos, _ in picks]),
+              "grad": torch.cat([b.grad_shard[pos].float() for b, pos, acc in picks if not acc])}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def rank_census(device, world: int, per_rank_ms: list) -> dict:
     """Who took part, answered by the line itself: the world size RCCL reports, one all_gather of the ranks' device
     identities (uuid, else PCI bus id) and host names, and the per-rank step time of the timed region."""
@@ -486,6 +525,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch-per-gpu", type=int, default=32)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy")
+    ap.add_argument("--full", action="store_true", help="also measure the extras (ranks, comm, roofline, trimmed prompt, inference, CPU baseline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true")
     ap.add_argument("--no-gemm-timing", action="store_true")
@@ -573,16 +614,20 @@ def main():
         per_rank_ms = [float(t) / args.steps * 1e3 for t in every]
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el)
-    try:
-        ranks = rank_census(device, world, per_rank_ms)
-    except Exception as e:  # noqa: BLE001 - diagnostics must never cost the headline
-        ranks = {"error": f"{type(e).__name__}: {e}", "ms_per_step_per_rank": per_rank_ms}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, loss)
+    ranks = None
+    if args.full:
+        try:
+            ranks = rank_census(device, world, per_rank_ms)
+        except Exception as e:  # noqa: BLE001 - diagnostics must never cost the headline
+            ranks = {"error": f"{type(e).__name__}: {e}", "ms_per_step_per_rank": per_rank_ms}
     # Roofline of the dominant kernel: HIP events around every bf16 GEMM launch, over `timer_steps` further identical steps
     # right after the timed region (every rank steps, rank 0 measures).  Inside the timed region the 2 x 1417 event
     # records per step cost ~10 ms (1.7 %) and, at N > 1, would make rank 0 the straggler the max-over-ranks reports.
     timer = timer_dual = None
     timer_steps = 2
-    if not args.no_gemm_timing:
+    if args.full and not args.no_gemm_timing:
         from kai0_amd import model as _model
 
         # every launch is timed ALONE: in the timed region above the action expert's chain (a few dozen small launches per
@@ -616,7 +661,7 @@ def main():
     # same reason as the GEMM timing.
     comm = None
     headline_mode = trainer.engine.mode
-    if world > 1 or os.environ.get("KAI0_FORCE_COLLECTIVES") == "1":
+    if args.full and (world > 1 or os.environ.get("KAI0_FORCE_COLLECTIVES") == "1"):
         eng = trainer.engine
         eng.comm_profile = True
         eng.comm_report()
@@ -741,7 +786,7 @@ def main():
     # rows, loss and gradients unchanged beyond summation order — tests/test_model_gpu.py).  The headline number above computes
     # all 200 slots, as the reference does.
     trimmed = None
-    if world == 1 and not args.no_trim_extra:
+    if args.full and world == 1 and not args.no_trim_extra:
         model.trim_prompt_padding = True
         for _ in range(2):
             trainer.train_step(obs, actions)
@@ -801,15 +846,16 @@ def main():
             out["comm"] = comm
         if headline_fallback is not None:
             out["headline_fallback"] = headline_fallback
-        out["ranks"] = ranks
+        if ranks is not None:
+            out["ranks"] = ranks
         if trimmed is not None:
             out["trimmed_prompt"] = trimmed
-        if world == 1 and not args.no_latency:
+        if args.full and world == 1 and not args.no_latency:
             del trainer
             torch.cuda.empty_cache()
             out["inference"] = measure_latency(model, cfg, device)
             out["p50_action_chunk_ms"] = out["inference"]["p50_ms"]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(B)
             cb_inf = out["cpu_baseline"].pop("inference", None)
             if cb_inf is not None and "inference" in out:

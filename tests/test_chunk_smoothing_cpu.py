@@ -1,7 +1,7 @@
 """kai0_amd.chunk_smoothing against the deployment scripts' classes EXECUTED from the reference source (lifted with `ast`; the
-scripts themselves import ROS and cannot be imported).  Needs /root/reference, which only exists in the build container:
-there the random-schedule comparison runs live; everywhere the committed vectors (tests/golden/chunk_smoothing.npz, written
-by this file when run as a script) are replayed."""
+scripts themselves import ROS and cannot be imported).  The reference classes' outputs on random schedules are committed
+(tests/golden/chunk_smoothing.npz, written by this file when run as a script next to a checkout of the reference) and
+replayed here."""
 import ast
 import os
 import sys
@@ -76,15 +76,13 @@ def test_against_committed_reference_vectors(seed):
     assert np.array_equal(s, g[f"stream.{seed}"], equal_nan=True) and np.array_equal(e, g[f"ensemble.{seed}"], equal_nan=True)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference sources only exist in the build container")
 @pytest.mark.parametrize("seed", range(100, 110))
 def test_live_against_the_reference_classes(seed):
-    ops = _schedule(seed)
-    ref_s = _lift(f"{REF}/agilex_inference_openpi_temporal_smoothing.py", "StreamActionBuffer")()
-    ref_e = _lift(f"{REF}/agilex_inference_openpi_temporal_ensembling.py", "TemporalEnsemblingBuffer")(exp_weight_m=0.05)
+    """Ten further schedules: the reference classes' outputs were recorded from their source (see __main__)."""
+    g = np.load(GOLD)
     s, e = _ours(seed)
-    assert np.array_equal(s, _run_stream(ref_s, ops), equal_nan=True)
-    assert np.array_equal(e, _run_ensemble(ref_e, ops), equal_nan=True)
+    assert np.array_equal(s, g[f"stream.{seed}"], equal_nan=True)
+    assert np.array_equal(e, g[f"ensemble.{seed}"], equal_nan=True)
 
 
 def test_documented_behaviour():
@@ -105,7 +103,7 @@ def test_documented_behaviour():
 
 if __name__ == "__main__":  # build container: write the committed vectors from the reference classes
     out = {}
-    for seed in range(6):
+    for seed in [*range(6), *range(100, 110)]:
         ops = _schedule(seed)
         out[f"stream.{seed}"] = _run_stream(_lift(f"{REF}/agilex_inference_openpi_temporal_smoothing.py", "StreamActionBuffer")(), ops)
         out[f"ensemble.{seed}"] = _run_ensemble(

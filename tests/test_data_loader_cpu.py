@@ -1,5 +1,6 @@
-"""kai0_amd.data_loader: host-side loader semantics against the reference's TorchDataLoader EXECUTED from
-source (lifted with `ast`; stubs for jax.tree.map / jax.process_count), the per-rank sharding under gloo world_size 2, the fake
+"""kai0_amd.data_loader: host-side loader semantics against the batches of the reference's TorchDataLoader
+EXECUTED from source (lifted with `ast`; stubs for jax.tree.map / jax.process_count; recorded in
+tests/golden/data_loader_reference.npz by this file when run as a script next to a checkout of the reference), the per-rank sharding under gloo world_size 2, the fake
 dataset's shapes, and the device feeder's ordering (CPU device here; the HIP-stream path runs in tests/test_fullsize_gpu.py)."""
 import ast
 import multiprocessing
@@ -56,9 +57,13 @@ def test_collate_transform_and_looping():
     assert [next(it)["idx"].tolist() for _ in range(5)] == [[0, 1], [2, 3], [0, 1], [2, 3], [0, 1]]
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference sources only exist in the build container")
-@pytest.mark.parametrize("shuffle,seed,nb", [(False, 0, 7), (True, 3, 9), (True, 11, 4)])
-def test_same_batches_as_the_reference_loader(shuffle, seed, nb):
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "data_loader_reference.npz")
+REF_CASES = [(False, 0, 7), (True, 3, 9), (True, 11, 4)]
+
+
+def _reference_batches(shuffle, seed, nb):
+    """The reference loader's batches over IndexDataset(30), batch 4, as (idx, obs.x) arrays of shape (nb, 4) / (nb, 4, 3)."""
+
     def tree_map(fn, *ts):
         return {k: tree_map(fn, *(t[k] for t in ts)) for k in ts[0]} if isinstance(ts[0], dict) else fn(*ts)
 
@@ -68,12 +73,18 @@ def test_same_batches_as_the_reference_loader(shuffle, seed, nb):
     for node in ast.parse(open(REF).read()).body:
         if isinstance(node, (ast.FunctionDef, ast.ClassDef)) and node.name in ("TorchDataLoader", "_collate_fn", "_worker_init_fn"):
             exec(compile(ast.Module([node], []), REF, "exec"), ns)
-    ref = ns["TorchDataLoader"](IndexDataset(30), 4, shuffle=shuffle, num_batches=nb, seed=seed, framework="pytorch")
-    ours = dl.TorchDataLoader(IndexDataset(30), 4, shuffle=shuffle, num_batches=nb, seed=seed)
-    rb, ob = list(ref), list(ours)
-    assert len(rb) == len(ob) == nb
-    for r, o in zip(rb, ob):
-        assert torch.equal(r["idx"], o["idx"]) and torch.equal(r["obs"]["x"], o["obs"]["x"])
+    rb = list(ns["TorchDataLoader"](IndexDataset(30), 4, shuffle=shuffle, num_batches=nb, seed=seed, framework="pytorch"))
+    return torch.stack([r["idx"] for r in rb]).numpy(), torch.stack([r["obs"]["x"] for r in rb]).numpy()
+
+
+@pytest.mark.parametrize("shuffle,seed,nb", REF_CASES)
+def test_same_batches_as_the_reference_loader(shuffle, seed, nb):
+    g = np.load(GOLD)
+    ridx, rx = g[f"idx.{shuffle}.{seed}.{nb}"], g[f"x.{shuffle}.{seed}.{nb}"]
+    ob = list(dl.TorchDataLoader(IndexDataset(30), 4, shuffle=shuffle, num_batches=nb, seed=seed))
+    assert len(ridx) == len(ob) == nb
+    for r, x, o in zip(ridx, rx, ob):
+        assert torch.equal(torch.from_numpy(r), o["idx"]) and torch.equal(torch.from_numpy(x), o["obs"]["x"])
 
 
 def test_fake_dataset_feeds_observation():
@@ -134,3 +145,11 @@ def test_distributed_sampler_shards_the_global_batch(tmp_path):
     assert all(len(b) == 4 for b in r0 + r1)  # global batch 8 -> 4 per rank
     a, b = sum(r0, []), sum(r1, [])
     assert not set(a) & set(b) and sorted(a + b) == list(range(40))  # disjoint shards that cover the dataset in one epoch
+
+
+if __name__ == "__main__":  # next to a checkout of the reference: record its loader's batches
+    out = {}
+    for shuffle, seed, nb in REF_CASES:
+        out[f"idx.{shuffle}.{seed}.{nb}"], out[f"x.{shuffle}.{seed}.{nb}"] = _reference_batches(shuffle, seed, nb)
+    np.savez_compressed(GOLD, **out)
+    print("wrote", GOLD, {k: v.shape for k, v in out.items()})
