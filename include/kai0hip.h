@@ -25,6 +25,7 @@ extern "C" {
 typedef void* kai0_stream_t; /* hipStream_t */
 
 const char* kai0_last_error(void);
+/* returns 2; what changed since version 1: INTEGRATION.md section 2.  Bindings check it at load time. */
 int kai0_abi_version(void);
 /* device properties probe: writes CU count, LDS bytes/CU, gcnArchName (<=63 chars) */
 int kai0_device_info(int device, int* n_cu, int* lds_bytes, char* arch_name64);
@@ -157,8 +158,6 @@ typedef struct kai0_gemm_desc {
     /* A/B and test hooks, all 0 in production.  They are per CALL: the library keeps no process-wide mutable switches (SURVEY.md §8b
      * "no globals beyond a per-device handle" — what remains static is per-device set-up: kernel LDS attributes, the CU count and
      * the persistent kernel's self-cleaning counter slots).
-     *   tile_cfg          force a tile / schedule configuration: 0 = automatic; 1 / 2 = 128 x 128 with 2 / 4 stages; 3 = 128 x 128 on eight
-     *                     waves (4 stages); 4 = 256 x 256 plain loop; 5 = 256 x 256 two-buffer ping-pong for every layout
      *   persist           persistent NT kernel (one resident block per CU drawing 256 x 256 tiles from an atomic, XCD-grouped ticket queue;
      *                     the next tile's first half-tiles are staged before the current tile's epilogue; bit-identical to one block per
      *                     tile): 0 = the library's rule (K-contiguous one-entry GEMMs of >= 2048 tiles with N >= 8192 or K >= 8192),
@@ -168,8 +167,9 @@ typedef struct kai0_gemm_desc {
      *                     fast path — same bits (tests/test_kernels_gpu.py)
      *   small_w8          the 128 x 128 tile on eight waves (two per SIMD) instead of four: 0 = the library's rule (launches of at most
      *                     one block per CU with K-contiguous operands and act 0 / 1), 1 = never, 2 = every eligible 128 x 128 launch;
-     *                     bit-identical to the four-wave tile */
-    int32_t tile_cfg, persist, general_epilogue, small_w8;
+     *                     bit-identical to the four-wave tile
+     * Out-of-range values are rejected. */
+    int32_t persist, general_epilogue, small_w8, _pad3;
 } kai0_gemm_desc;
 
 int kai0_gemm_bf16(const kai0_gemm_desc* d, kai0_stream_t stream);

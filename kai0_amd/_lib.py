@@ -12,6 +12,7 @@ import pathlib
 
 _HERE = pathlib.Path(__file__).resolve().parent
 LIB_PATH = _HERE / "lib" / "libkai0hip.so"
+ABI_VERSION = 2  # what kai0_abi_version() must return: the version these mirrors and prototypes describe
 
 c_p = C.c_void_p
 c_i = C.c_int
@@ -46,7 +47,7 @@ class GemmDesc(C.Structure):
         ("B2", c_p), ("pre_out2", c_p),
         ("norm_out", c_p), ("norm_w", c_p), ("norm_b", c_p), ("norm_eps", C.c_float), ("norm_kind", C.c_int32),
         ("rope_cos", c_p), ("rope_sin", c_p), ("rope_half", C.c_int32), ("rope_n_end", C.c_int32),
-        ("tile_cfg", C.c_int32), ("persist", C.c_int32), ("general_epilogue", C.c_int32), ("small_w8", C.c_int32),
+        ("persist", C.c_int32), ("general_epilogue", C.c_int32), ("small_w8", C.c_int32), ("_pad3", C.c_int32),
     ]  # fmt: skip
 
 
@@ -223,6 +224,8 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         fn.restype = c_i
         fn.argtypes = args
+    if lib.kai0_abi_version() != ABI_VERSION:
+        raise Kai0HipError(f"{path}: C ABI version {lib.kai0_abi_version()}, this binding expects {ABI_VERSION} (rebuild the library)")
     if lib.kai0_gemm_desc_size() != C.sizeof(GemmDesc):
         raise Kai0HipError(
             f"kai0_gemm_desc layout mismatch: C {lib.kai0_gemm_desc_size()} B vs ctypes {C.sizeof(GemmDesc)} B"

@@ -1,13 +1,13 @@
 // gemm_bf16.hip — the bf16 MFMA GEMM under every Linear and attention matmul of the pi0.5 path.
 //
 // gfx950 design:
-//   * two tile configurations of one template: 256x256x64 (8 waves as 2x4, each a 128x64 sub-tile = 8x4 MFMA
-//     16x16x32 tiles; 128 KiB LDS, 1 block/CU) for problems that fill the chip, and 128x128x64 (4 waves, 64x64
-//     each; 64 KiB, 2 blocks/CU) for small ones.  Measured (KAI0_GEMM_ABLATE): the 128x128 kernel is bound by the
+//   * two tile sizes of one template: 256x256 (8 waves as 2x4, each a 128x64 sub-tile = 8x4 MFMA 16x16x32
+//     tiles; 128 KiB LDS, 1 block/CU) for problems that fill the chip, and 128x128x64 (4 waves, 64x64 each, or 8
+//     waves of 32x64) for small ones.  Measured (KAI0_GEMM_ABLATE): the 128x128 kernel is bound by the
 //     L2->LDS staging rate (~14 TB/s chip-wide), not by MFMA or LDS reads, so the lever is bytes staged per
-//     FLOP = tile size; 256x256 halves it.
+//     FLOP = tile size; 256x256 halves it.  The K loops and the configurations: above gemm_bf16_kernel and launch_cfg.
 //   * operands go HBM -> LDS by LDS-DMA (`global_load_lds_dwordx4`, 1 KiB per wave-instruction), never
-//     through VGPRs; two stages (A+B) double-buffered.
+//     through VGPRs, into 2-4 LDS stages.
 //   * the LDS image is lane-linear (DMA constraint), so the bank-conflict XOR swizzle is applied on the
 //     per-lane GLOBAL source address and undone on the ds_read address (same involution both sides).
 //   * K-contiguous operands are read with ds_read_b128; contraction-strided operands (dgrad's W,
@@ -264,29 +264,26 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// Block tile = (WM*MT*16) x (WN*NT*16) x 64, WM x WN waves, each wave MT x NT MFMA 16x16x32 tiles.
-// PP (ping-pong, 8-wave tile only): the waves of tile-row 0 and tile-row 1 (one wave of each per SIMD) run one barrier
-//   slot apart, so in every slot one group issues its 32 MFMAs while the other issues LDS-DMA and ds_reads.
-// NS = LDS stages of the plain (non-PP) loop.  2: one K-tile of prefetch, enough when a second block on the CU (or the
-//   sheer length of a 256x256 tile's MFMA burst) covers the load latency.  4 (128x128 tile, 128 KiB): three K-tiles in
-//   flight with a counted vmcnt — for grids of <= 1 block per CU (B = 1 inference GEMMs), where a 2-stage loop runs at
-//   one memory latency per K-tile.
-// BKT = K-tile depth.  64 everywhere except the ring schedule (PP, NS = 4, BKT = 32): 4 slots of 32 KiB, three
-//   32-deep sub-tiles in flight, every load slot carries 2 DMA pieces + 12 fragment reads and every MFMA slot 32 MFMAs
-//   + 2 DMA pieces, with nothing conditional inside the loop (tail pieces are issued out of range = zero fill).
-// SCH (PP, NS = 2, BKT = 64): 0 = the two-buffer ping-pong below; 1 / 2 = the quadrant schedule ("8 phases" per
-//   two K-tiles): every K-tile is four phases of [fragment reads of one half-operand + 2 DMA pieces | barrier | 16 MFMAs of one
-//   64x32 quadrant of the wave's 128x64 sub-tile | barrier]; the four half-tiles of a K-tile (A rows / B columns of the two
-//   quadrant halves, 16 KiB each) are staged one per phase, 4-6 phases ahead of their first read, into the half-buffer whose
-//   previous occupant died earliest, with counted waits (never vmcnt(0) inside the loop).  1: pieces issued after the phase's
-//   fragment reads; 2: pieces issued in the middle of the phase's MFMAs.
+// Block tile = (WM*MT*16) x (WN*NT*16) x BKT, WM x WN waves, each wave MT x NT MFMA 16x16x32 tiles.  Three K loops:
+// plain multi-stage (PP = false, SCH = 0): NS LDS stages of BKT = 64.  NS = 2: one K-tile of prefetch, enough when a second
+//   block on the CU (or the sheer length of a 256x256 tile's MFMA burst) covers the load latency.  NS = 4 (128x128 tile,
+//   128 KiB): three K-tiles in flight with a counted vmcnt — for grids of <= 1 block per CU (B = 1 inference GEMMs), where a
+//   2-stage loop runs at one memory latency per K-tile.
+// PP = true (ping-pong, 256x256 tile on 8 waves): the waves of tile-row 0 and tile-row 1 (one wave of each per SIMD) run one
+//   barrier slot apart, so in every slot one group issues its MFMAs while the other issues LDS-DMA and ds_reads.
+//   quadrant (SCH = 1; NS = 2, BKT = 64; "8 phases" per two K-tiles): every K-tile is four phases of [fragment reads of one
+//     half-operand + 2 DMA pieces | barrier | 16 MFMAs of one 64x32 quadrant of the wave's 128x64 sub-tile | barrier]; the four
+//     half-tiles of a K-tile (A rows / B columns of the two quadrant halves, 16 KiB each) are staged one per phase, 4-6 phases
+//     ahead of their first read, into the half-buffer whose previous occupant died earliest, with counted waits (never
+//     vmcnt(0) inside the loop).
+//   ring (SCH = 3; NS = 4, BKT = 32): 4 slots of 32 KiB, three 32-deep sub-tiles in flight, every load slot carries 12
+//     fragment reads and every MFMA slot 32 MFMAs + the 4 DMA pieces of a sub-tile, with nothing conditional inside the loop
+//     (tail pieces are issued out of range = zero fill).
 template <bool A_KC, bool B_KC, int WM, int WN, int MT, int NT, bool PP, int NS = 2, int BKT = 64, int SCH = 0>
-__global__ __launch_bounds__(WM * WN * 64, ((WM * WN * 64) / 256) * ((MT == 8 && WM * WN == 4) ? 2 : 1)) void gemm_bf16_kernel(const GemmArgs p) {  // (256 x 128 on four waves: two blocks per CU)
-    static_assert(!PP || (WM == 2 && WN == 4), "ping-pong schedule: two 4-wave groups");
-    static_assert(SCH == 0 || (SCH == 1 && PP && NS == 2 && BKT == 64 && MT == 8 && NT == 4) || (SCH == 3 && PP && NS == 4), "schedules: 0 plain / two-buffer ping-pong, 1 quadrant (256x256x64), 3 ring (256x256x32)");
-    static_assert(!(PP && NS == 4) || SCH == 3, "the ring runs with every DMA piece between the MFMA rows");
-    static_assert(NS >= 2 && (!PP || NS == 2 || (NS == 4 && BKT == 32)), "stages");
-    static_assert(BKT == 64 || BKT == 32, "K-tile depth");
+__global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_kernel(const GemmArgs p) {
+    static_assert(PP ? (WM == 2 && WN == 4 && MT == 8 && ((SCH == 1 && NS == 2 && BKT == 64) || (SCH == 3 && NS == 4 && BKT == 32)))
+                     : (SCH == 0 && NS >= 2 && BKT == 64),
+                  "K loops: plain multi-stage (SCH 0, 64 deep), quadrant (SCH 1: 256x256x64, 2 stages), ring (SCH 3: 256x256x32, 4 slots)");
     constexpr int BK = BKT;
     constexpr int NWAVES = WM * WN;
     constexpr int TBM = WM * MT * 16, TBN = WN * NT * 16;
@@ -483,20 +480,20 @@ __global__ __launch_bounds__(WM * WN * 64, ((WM * WN * 64) / 256) * ((MT == 8 &&
     };
 
     const int nk = (kend - kbeg + BK - 1) / BK;
-    if constexpr (PP && NS == 4) {
+    if constexpr (SCH == 3) {
         // Ring schedule.  Sub-tile u (32 deep) lives in slot u & 3.  Group g (= wm) runs  L(u) |b| M(u) |b|  at barrier
         // slots 2u+g, 2u+1+g: in every slot one group issues MFMAs while the other reads fragments.
-        //   L(u): fragment reads of sub-tile u, then DMA pieces 0,1 of sub-tile u+3;  M(u): 32 MFMAs with pieces 2,3 of
-        //   sub-tile u+3 dropped in after MFMA rows 2 and 5 (their offsets were computed in L(u)).
+        //   L(u): fragment reads of sub-tile u;  M(u): 32 MFMAs with the four DMA pieces of sub-tile u+3 (and their offset
+        //   arithmetic) dropped in after MFMA rows 0, 2, 4 and 6.
         //  * Why: one LDS-DMA piece costs its wave 100-180 cycles next to ds_reads and ~60 between MFMAs; the former
         //    schedule put all 8 pieces of a 64-deep tile in one load slot (~1300 cycles against the partner's 512 of
         //    MFMA), and the loop without DMA ran at 1.7-2.0 PFLOP/s against 1.1 with it.
         //  * WAR: slot (u+3)&3 held sub-tile u-1, last read in group 1's L(u-1) (slot 2u-1, retired by the lgkmcnt(0)
-        //    in front of its barrier); the earliest piece of u+3 is issued in group 0's L(u) (slot 2u).
+        //    in front of its barrier); the earliest piece of u+3 is issued in group 0's M(u) (slot 2u+1).
         //  * RAW: sub-tile u+1 is first read in slot 2u+2, so every wave drains its pieces of u+1 before the barrier that
         //    ends slot 2u+1 — group 0 at the end of M(u) with pieces of u+2, u+3 (8) still in flight, group 1 at the end
-        //    of L(u) with those of u+2 and the first two of u+3 (6).  Counts stay exact in the tail because pieces past
-        //    the end are still issued (out-of-range offset: zero fill into a slot nobody reads).
+        //    of L(u) with those of u+2 (4).  Counts stay exact in the tail because pieces past the end are still issued
+        //    (out-of-range offset: zero fill into a slot nobody reads).
         constexpr int NP = NA + NB;
         static_assert(NP == 4 && BK == 32, "ring schedule: 4 pieces per 32-deep sub-tile");
         const int grp = wm;
@@ -516,21 +513,8 @@ __global__ __launch_bounds__(WM * WN * 64, ((WM * WN * 64) / 256) * ((MT == 8 &&
             for (int t = 0; t < NT; ++t) bfr[t] = load_frag(tb, B_KC, B_ROWB, wn * (NT * 16) + t * 16, 0);
 #pragma unroll
             for (int t = 0; t < MT; ++t) af[t] = load_frag(ta, A_KC, A_ROWB, wm * (MT * 16) + t * 16, 0);
-            uint32_t poff[NP];
-            if constexpr (SCH == 0) {
-#pragma unroll
-                for (int pi = 0; pi < NP; ++pi) poff[pi] = KAI0_ABL(p) == 1 ? OOB : piece_off(u + 3, pi);
-            }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (SCH == 0) {
-                piece_issue(poff[0], pslot, 0);
-                piece_issue(poff[1], pslot, 1);
-                if (grp == 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            } else {
-                // SCH == 3: all four pieces of u+3 go out between the MFMA rows (a piece costs its wave ~60 cycles there against
-                // 100-180 next to the fragment reads); group 1 therefore ends L(u) with only u+2's four pieces younger than u+1's
-                if (grp == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            }
+            if (grp == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             lds_barrier();
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -538,15 +522,9 @@ __global__ __launch_bounds__(WM * WN * 64, ((WM * WN * 64) / 256) * ((MT == 8 &&
 #pragma unroll
                 for (int j = 0; j < NT; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-                if (SCH == 0 && (i == 2 || i == 5)) {
+                if ((i & 1) == 0) {
                     __builtin_amdgcn_sched_barrier(0);
-                    piece_issue(poff[i == 2 ? 2 : 3], pslot, i == 2 ? 2 : 3);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if (SCH == 3 && (i & 1) == 0) {  // (the offset arithmetic sits in the MFMA shadow too)
-                    __builtin_amdgcn_sched_barrier(0);
-                    poff[i >> 1] = KAI0_ABL(p) == 1 ? OOB : piece_off(u + 3, i >> 1);
-                    piece_issue(poff[i >> 1], pslot, i >> 1);
+                    piece_issue(KAI0_ABL(p) == 1 ? OOB : piece_off(u + 3, i >> 1), pslot, i >> 1);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -557,7 +535,7 @@ __global__ __launch_bounds__(WM * WN * 64, ((WM * WN * 64) / 256) * ((MT == 8 &&
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing zero-fill pieces must land before the slabs reuse LDS
         if (grp == 0) lds_barrier();  // re-align the two groups
         lds_barrier();
-    } else if constexpr (PP && NS == 2 && SCH != 0) {
+    } else if constexpr (SCH == 1) {
         // Quadrant schedule.  Wave (wm, wn) owns rows wm*128 + [0, 128), columns wn*64 + [0, 64) of the tile; half-operand
         // A_a = its rows a*64 + [0, 64) (for both wm: 128 tile rows), B_b = its columns b*32 + [0, 32) (for all four wn: 128 tile
         // columns); 16 KiB = 16 DMA pieces each, two per wave.  Tile t (LDS slot t & 1) runs the quadrants
@@ -660,24 +638,18 @@ __global__ __launch_bounds__(WM * WN * 64, ((WM * WN * 64) / 256) * ((MT == 8 &&
                     bq[j][ks] = B_KC ? load_frag(tb, true, B_ROWB, wn * 64 + (h * 2 + j) * 16, ks)
                                      : load_frag(tb + h * 16384, false, 256, wn * 32 + j * 16, ks);
         };
-        // 16 MFMAs of quadrant (ah, bh); SCH == 2: the phase's two DMA pieces go out after the 8th
-        auto quad = [&](auto ahc, auto bhc, bool isb, int h, int t) {
+        // 16 MFMAs of quadrant (ah, bh)
+        auto quad = [&](auto ahc, auto bhc) {
             constexpr int ah = decltype(ahc)::value, bh = decltype(bhc)::value;
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
+            for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
                         acc[ah * 4 + i][bh * 2 + j] =
                             __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][ks], bq[j][ks], acc[ah * 4 + i][bh * 2 + j], 0, 0, 0);
-                if (SCH == 2 && ks == 0) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    issue_half(isb, h, t);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
             __builtin_amdgcn_s_setprio(0);
         };
         using I0 = std::integral_constant<int, 0>;
@@ -690,84 +662,37 @@ __global__ __launch_bounds__(WM * WN * 64, ((WM * WN * 64) / 256) * ((MT == 8 &&
             __builtin_amdgcn_sched_barrier(0);
             read_a(ta, 0);
             __builtin_amdgcn_sched_barrier(0);
-            if (SCH == 1) issue_half(true, 0, t + 1);
+            issue_half(true, 0, t + 1);
             lds_barrier();
-            quad(I0{}, I0{}, true, 0, t + 1);
+            quad(I0{}, I0{});
             lds_barrier();
             // ---- p1: (A0, B1); stage A1(t+1); A1(t) must have landed one phase from now
             read_b(tb, 1);
             __builtin_amdgcn_sched_barrier(0);
-            if (SCH == 1) {
-                issue_half(false, 1, t + 1);
-                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            } else {  // the phase's own pieces are not issued yet: one half-tile fewer in flight
-                asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            }
+            issue_half(false, 1, t + 1);
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             lds_barrier();
-            quad(I0{}, I1{}, false, 1, t + 1);
+            quad(I0{}, I1{});
             lds_barrier();
             // ---- p2: (A1, B1); stage A0(t+2) (same slot as this tile: A0(t) died in p0)
             read_a(ta, 1);
             __builtin_amdgcn_sched_barrier(0);
-            if (SCH == 1) issue_half(false, 0, t + 2);
+            issue_half(false, 0, t + 2);
             lds_barrier();
-            quad(I1{}, I1{}, false, 0, t + 2);
+            quad(I1{}, I1{});
             lds_barrier();
             // ---- p3: (A1, B0); stage B1(t+2); A0(t+1), B0(t+1) must have landed one phase from now
             read_b(tb, 0);
             __builtin_amdgcn_sched_barrier(0);
-            if (SCH == 1) {
-                issue_half(true, 1, t + 2);
-                asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            }
+            issue_half(true, 1, t + 2);
+            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
             lds_barrier();
-            quad(I1{}, I0{}, true, 1, t + 2);
+            quad(I1{}, I0{});
             lds_barrier();
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing zero-fill pieces must land before the slabs reuse LDS
         if (grp == 0) lds_barrier();  // re-align the two groups
         lds_barrier();
-    } else if constexpr (PP) {
-        // Two-buffer ping-pong (kept for comparison, kai0_gemm_desc.tile_cfg = 5).  Barrier clock b0, b1, ...: per K-tile t group 0 runs
-        // L0(t) |b| M0(t) |b| L1(t) |b| M1(t) |b|  and group 1 the same sequence one barrier later.  Lk = [k = 0: issue the
-        // whole DMA of tile t+1] + the 12 fragment reads of k-half k; Mk = its 32 MFMAs.
-        //  * RAW: tile t+1 is first read after barrier 4t+3 (group 0's L0(t+1)); every wave drains its own DMA before
-        //    that barrier (group 0 at the end of M1(t), group 1 at the end of L1(t)), >= 2 slots after issuing it.
-        //  * WAR: the DMA of tile t+1 overwrites the buffer of tile t-1, last read in group 1's L1(t-1) and retired by
-        //    the lgkmcnt(0) in front of barrier 4t-1; the earliest issue (group 0, L0(t)) comes after that barrier.
-        const int grp = wm;
-        stage(0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        lds_barrier();
-        if (grp == 1) lds_barrier();  // stagger group 1 by one slot
-        for (int kt = 0; kt < nk; ++kt) {
-            const int buf = kt & 1;
-            const char* ta = smem + buf * STAGE;
-            const char* tb = ta + A_TILE;
-#pragma unroll
-            for (int ks = 0; ks < BK / 32; ++ks) {
-                if (ks == 0 && kt + 1 < nk && KAI0_ABL(p) != 1) stage(kt + 1, buf ^ 1);
-                bf16x8 bfr[NT], af[MT];
-#pragma unroll
-                for (int t = 0; t < NT; ++t) bfr[t] = load_frag(tb, B_KC, B_ROWB, wn * (NT * 16) + t * 16, ks);
-#pragma unroll
-                for (int t = 0; t < MT; ++t) af[t] = load_frag(ta, A_KC, A_ROWB, wm * (MT * 16) + t * 16, ks);
-                if (ks == 1 && grp == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                lds_barrier();
-                __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_s_setprio(0);
-                if (ks == 1 && grp == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                lds_barrier();
-            }
-        }
-        if (grp == 0) lds_barrier();  // re-align the two groups
     } else {
         // iteration kt: [tile kt landed (counted vmcnt) | barrier | issue tile kt+NS-1 into the slot tile kt-1 just left |
         // compute tile kt].  The barrier orders both the RAW on tile kt and the WAR on the slot being refilled.
@@ -817,7 +742,7 @@ __global__ __launch_bounds__(WM * WN * 64, ((WM * WN * 64) / 256) * ((MT == 8 &&
     const int64_t rz = z1 * p.sR1 + z2 * p.sR2;
     const int64_t vz = z1 * p.rv_s1 + z2 * p.rv_s2;
     // quadrant schedule with a contraction-strided operand: that operand's sub-tiles are interleaved (see the schedule)
-    constexpr bool ILM = (SCH == 1 || SCH == 2) && !A_KC, ILN = (SCH == 1 || SCH == 2) && !B_KC;
+    constexpr bool ILM = SCH == 1 && !A_KC, ILN = SCH == 1 && !B_KC;
     const int ccol = ILN ? n0 + ((lane & 7) >> 2) * 128 + wn * 32 + ((lane & 7) & 3) * 8 : n0 + wn * 64 + (lane & 7) * 8;
     auto row_base = [&](int h) { return ILM ? m0 + h * 128 + wm * 64 : m0 + wm * (MT * 16) + h * 64; };
     // 8-wide column groups: when N % 8 != 0 the last group's extra columns hold exact zeros (their B rows are
@@ -1865,7 +1790,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_norm_kernel(const GemmArgs 
     }
 }
 
-template <int WM, int WN, int MT, int NT, bool PP, int NS = 2, int BKT = 64, int SCH = 0>
+// The operand layouts (a_kc, b_kc) a configuration is built for, one bit each: NT = (1, 1) the forward y = x W^T, NN = (1, 0)
+// dgrad, TN = (0, 0) wgrad, TT = (0, 1).
+constexpr int layout_bit(bool a_kc, bool b_kc) { return 1 << (2 * a_kc + b_kc); }
+constexpr int L_NT = layout_bit(true, true), L_NN = layout_bit(true, false), L_TT = layout_bit(false, true), L_TN = layout_bit(false, false);
+constexpr int L_ALL = L_NT | L_NN | L_TT | L_TN;
+
+template <int LAYOUTS, int WM, int WN, int MT, int NT, bool PP, int NS = 2, int BKT = 64, int SCH = 0>
 int launch_cfg(const kai0_gemm_desc* d, GemmArgs& p, int batch, hipStream_t s) {
     constexpr int TBM = WM * MT * 16, TBN = WN * NT * 16;
     constexpr int LDS = NS * (TBM + TBN) * BKT * 2;
@@ -1873,31 +1804,29 @@ int launch_cfg(const kai0_gemm_desc* d, GemmArgs& p, int batch, hipStream_t s) {
     p.tiles_n = (p.N + TBN - 1) / TBN;
     dim3 grid(p.tiles_m * p.tiles_n, batch * p.split_k, 1), block(WM * WN * 64, 1, 1);
 #define KAI0_LAUNCH(AK, BK_)                                                                                      \
-    do {                                                                                                          \
-        static bool attr_set = false;                                                                             \
-        auto kern = gemm_bf16_kernel<AK, BK_, WM, WN, MT, NT, PP, NS, BKT, SCH>;                       \
-        if (!attr_set) {                                                                                          \
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); \
-            if (e != hipSuccess) {                                                                                \
-                kai0_set_error("kai0_gemm_bf16: cannot reserve %d B of LDS: %s", LDS, hipGetErrorString(e));      \
-                return -2;                                                                                        \
+    if constexpr ((LAYOUTS & layout_bit(AK, BK_)) != 0)                                                          \
+        if ((d->a_kc != 0) == AK && (d->b_kc != 0) == BK_) {                                                      \
+            static bool attr_set = false;                                                                         \
+            auto kern = gemm_bf16_kernel<AK, BK_, WM, WN, MT, NT, PP, NS, BKT, SCH>;                              \
+            if (!attr_set) {                                                                                      \
+                hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); \
+                if (e != hipSuccess) {                                                                            \
+                    kai0_set_error("kai0_gemm_bf16: cannot reserve %d B of LDS: %s", LDS, hipGetErrorString(e));  \
+                    return -2;                                                                                    \
+                }                                                                                                 \
+                attr_set = true;                                                                                  \
             }                                                                                                     \
-            attr_set = true;                                                                                      \
-        }                                                                                                         \
-        hipLaunchKernelGGL(kern, grid, block, LDS, s, p);                                                         \
-    } while (0)
-    constexpr bool MC_A_OK = (64 % (TBM * 2 / 16)) == 0;  // contraction-strided A tiles need whole k-rows per DMA piece
-    if (d->a_kc && d->b_kc) KAI0_LAUNCH(true, true);
-    else if (d->a_kc && !d->b_kc) KAI0_LAUNCH(true, false);
-    else if constexpr (MC_A_OK) {
-        if (!d->a_kc && d->b_kc) KAI0_LAUNCH(false, true);
-        else KAI0_LAUNCH(false, false);
-    } else {
-        kai0_set_error("kai0_gemm_bf16: this tile configuration needs a K-contiguous A operand");
-        return -3;
-    }
+            hipLaunchKernelGGL(kern, grid, block, LDS, s, p);                                                     \
+            return 0;                                                                                             \
+        }
+    KAI0_LAUNCH(true, true)
+    KAI0_LAUNCH(true, false)
+    KAI0_LAUNCH(false, true)
+    KAI0_LAUNCH(false, false)
 #undef KAI0_LAUNCH
-    return 0;
+    kai0_set_error("kai0_gemm_bf16: the %d x %d tile configuration (%d waves, %d stages) is not built for a_kc=%d b_kc=%d", TBM, TBN,
+                   WM * WN, NS, d->a_kc, d->b_kc);
+    return -3;
 }
 
 }  // namespace
@@ -1930,6 +1859,10 @@ KAI0_API int kai0_gemm_bf16(const kai0_gemm_desc* d, kai0_stream_t stream) {
                  "kai0_gemm_bf16: batch strides must be multiples of 8 elements (16 B)");
     KAI0_REQUIRE(d->gate == nullptr || d->gate_rpb > 0, "kai0_gemm_bf16: gate needs gate_rpb > 0");
     KAI0_REQUIRE(d->act >= 0 && d->act <= 7, "kai0_gemm_bf16: unknown act %d", d->act);
+    KAI0_REQUIRE(d->persist >= 0 && d->persist <= 2 && d->small_w8 >= 0 && d->small_w8 <= 2 && d->general_epilogue >= 0 &&
+                     d->general_epilogue <= 1,
+                 "kai0_gemm_bf16: hook out of range (persist=%d, small_w8=%d: 0..2; general_epilogue=%d: 0..1)", d->persist, d->small_w8,
+                 d->general_epilogue);
     KAI0_REQUIRE(d->act != 7 || (d->rope_cos && d->rope_sin && d->rope_half == 128 && d->rope_n_end > 0 && (d->rope_n_end % 256) == 0 &&
                                  d->rope_n_end <= d->N && (d->N % 128) == 0 && d->a_kc && d->b_kc && d->batch <= 1 && d->split_k <= 1 &&
                                  !d->out_f32 && !d->accumulate && !d->bias && !d->gate && !d->residual && !d->pre_out &&
@@ -2039,34 +1972,21 @@ KAI0_API int kai0_gemm_bf16(const kai0_gemm_desc* d, kai0_stream_t stream) {
     }
     // tile configuration: 256x256 (1 block of 8 waves per CU, half the staged bytes per FLOP) when the problem gives
     // (nearly) every CU a block; 128x128 (2 blocks per CU) for small problems.
-    const int forced = d->tile_cfg;
     const int64_t big_tiles = (int64_t)((d->M + 255) / 256) * ((p.N + 255) / 256) * batch * (split > 1 ? split : 1);
-    const bool big = d->act == 7 ? false : (forced ? forced >= 4 : (big_tiles >= 160 && d->K >= 256));  // (act 7: 128-column tiles)
+    const bool big = d->act != 7 && big_tiles >= 160 && d->K >= 256;  // (act 7: 128-column tiles)
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    // measured on the MLP shapes: the ping-pong schedule wins for NT (+3..8 %) and loses for the transpose-read
-    // layouts (their load slot is longer than the MFMA slot), so only NT uses it
-    const bool pp = forced ? forced == 5 : (d->a_kc && d->b_kc);
     // few 128x128 tiles (at most one block per CU): nothing else hides the load latency -> 4-stage pipeline
     const int64_t small_blocks = (int64_t)((d->M + 127) / 128) * ((p.N + 127) / 128) * batch * (split > 1 ? split : 1);
-    const bool deep = forced ? forced == 2 : (small_blocks <= 256 && p.k_chunk >= 256);
+    const bool deep = small_blocks <= 256 && p.k_chunk >= 256;
     // 128 x 128 on EIGHT waves (4 x 2 wave tiles of 32 x 64; round 6): with at most one block per CU the four-wave loop has one wave per
     // SIMD, so a K-tile is that wave's 8 LDS-DMA issues + 16 fragment reads + 32 MFMAs one after the other (~1470 clocks for 544 of MFMA);
     // two waves per SIMD let one wave's MFMAs run under the other's DMA issue and read latency.  K-contiguous operands, act 0 / 1 / 7 (the
     // epilogues the narrower wave tile implements); kai0_gemm_desc.small_w8: 0 = this rule, 1 = never, 2 = every eligible 128 x 128 launch.
-    const bool w8_ok = !big && d->a_kc && d->b_kc && (d->act <= 1 || d->act == 7) && (forced == 0 || forced == 3);
-    const bool w8 = w8_ok && (forced == 3 || d->small_w8 == 2 || (d->small_w8 == 0 && deep));
-    // forced (kai0_gemm_desc.tile_cfg, A/B runs): 1 / 2 = 128x128 with 2 / 4 stages, 4 = 256x256 plain loop, 5 = 256x256
-    // two-buffer ping-pong for every layout.  Measured (MLP shapes, random data): the 32-deep ring wins +21 % for the transpose-read
-    // layout (TN wgrads: 512-B source rows, so a 32-deep sub-tile still moves whole cache lines) and loses up to 17 % for NT (64-B
-    // source rows = half lines), which runs the quadrant schedule (+6..10 % over the two-buffer ping-pong, 1.37 PFLOP/s at 8192^3).
-    // (Act 6 selects its second weight per DMA piece of a 64-deep K-tile: never on the ring.)  Removed after measurement: a 384x256
-    // plain tile (equal to the ping-pong, spilled), the quadrant schedule with its DMA pieces between the MFMAs, the ring with two
-    // pieces per slot kind (-0.9 %), the ring for NT.
-    const bool ring = !forced && d->act != 6 && !d->a_kc && !d->b_kc;
+    const bool w8 = !big && d->a_kc && d->b_kc && (d->act <= 1 || d->act == 7) && (d->small_w8 == 2 || (d->small_w8 == 0 && deep));
     // persistent NT kernel with the dynamic tile queue (kai0_gemm_desc.persist: 0 = the rule below, 1 = never, 2 = every eligible NT launch)
     const int persist = d->persist == 1 ? 0 : (d->persist == 2 ? 2 : 1);
-    const bool ps_ok = !forced && persist && big && d->a_kc && d->b_kc && batch == 1 && split == 1 &&
+    const bool ps_ok = persist && big && d->a_kc && d->b_kc && batch == 1 && split == 1 &&
                        big_tiles >= (persist == 2 ? 512 : 2048) &&  // (B = 1 prefix MLP, 512 tiles = two per CU: 97 -> 136 us persistent)
                        (p.K % 8) == 0 && !d->rowvec && d->a_rpb == 0 && d->b_rpb == 0;
     // the rule (measured inside the training step with KAI0_GEMM_BREAKDOWN=1, round 4): the wide MLP shapes gain — 30976 x 16384 x 2048 with the GeGLU
@@ -2100,18 +2020,19 @@ KAI0_API int kai0_gemm_bf16(const kai0_gemm_desc* d, kai0_stream_t stream) {
         hipLaunchKernelGGL(gemm_nt_persistent_kernel, dim3(nblk), dim3(512), LDS, s, p, ctr);
         return kai0_check_launch("kai0_gemm_bf16 (persistent)");
     }
-    // A/B configurations with TWO blocks per CU (round 6, VERDICT r5 #2 "two tiles in flight per CU": one block's epilogue under the other's
-    // K loop): 6 = the eight-wave 128 x 128 tile with two stages (64 KiB), 7 = 256 x 128 x 32 on four waves with three stages (72 KiB)
-    if (forced == 6) rc = launch_cfg<4, 2, 2, 4, false, 2>(d, p, batch, s);
-    else if (forced == 7) rc = launch_cfg<2, 2, 8, 4, false, 3, 32>(d, p, batch, s);
-    // TN: ring with every DMA piece (and its offset arithmetic) between the MFMA rows
-    else if (big && ring) rc = launch_cfg<2, 4, 8, 4, true, 4, 32, 3>(d, p, batch, s);
-    else if (big && !pp) rc = launch_cfg<2, 4, 8, 4, false>(d, p, batch, s);
-    else if (big && d->b_kc && forced != 5) rc = launch_cfg<2, 4, 8, 4, true, 2, 64, 1>(d, p, batch, s);  // NT: quadrant schedule
-    else if (big) rc = launch_cfg<2, 4, 8, 4, true>(d, p, batch, s);
-    else if (w8) rc = launch_cfg<4, 2, 2, 4, false, 4>(d, p, batch, s);
-    else if (deep) rc = launch_cfg<2, 2, 4, 4, false, 4>(d, p, batch, s);
-    else rc = launch_cfg<2, 2, 4, 4, false>(d, p, batch, s);
+    // 256 x 256 by layout (measured on the MLP shapes, random data): NT runs the quadrant schedule (+6..10 % over a two-buffer
+    // ping-pong, 1.37 PFLOP/s at 8192^3); TN (weight gradients: 512-B source rows, so a 32-deep sub-tile still moves whole cache
+    // lines) the 32-deep ring (+21 %; it loses up to 17 % for NT, whose 64-B source rows are half lines); the layouts with one
+    // transposed operand the plain two-stage loop (a ping-pong loses there: their load slot is longer than the MFMA slot).  Act 6 (NT
+    // only) selects its second weight per DMA piece of a 64-deep K-tile.  Removed after measurement: a 384x256 plain tile (equal to
+    // the ping-pong, spilled), the quadrant schedule with its DMA pieces between the MFMAs, the ring with two pieces per slot kind
+    // (-0.9 %), the two-buffer ping-pong, two blocks per CU (round 6: 128 x 128 on eight waves x 2 stages, 256 x 128 x 32 x 3 stages).
+    if (big && d->a_kc && d->b_kc) rc = launch_cfg<L_NT, 2, 4, 8, 4, true, 2, 64, 1>(d, p, batch, s);
+    else if (big && !d->a_kc && !d->b_kc) rc = launch_cfg<L_TN, 2, 4, 8, 4, true, 4, 32, 3>(d, p, batch, s);
+    else if (big) rc = launch_cfg<L_NN | L_TT, 2, 4, 8, 4, false>(d, p, batch, s);
+    else if (w8) rc = launch_cfg<L_NT, 4, 2, 2, 4, false, 4>(d, p, batch, s);
+    else if (deep) rc = launch_cfg<L_ALL, 2, 2, 4, 4, false, 4>(d, p, batch, s);
+    else rc = launch_cfg<L_ALL, 2, 2, 4, 4, false>(d, p, batch, s);
     if (rc) return rc;
     rc = kai0_check_launch("kai0_gemm_bf16");
     if (rc || split == 1) return rc;

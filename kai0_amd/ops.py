@@ -48,10 +48,10 @@ def _chk(t: torch.Tensor, dtype, name: str) -> None:
 
 
 # ------------------------------------------------------------------------------------------------ GEMM
-# The A/B and test hooks of kai0_gemm_desc (kai0hip.h: tile_cfg / persist / general_epilogue), all 0 in production.  They travel with
+# The A/B and test hooks of kai0_gemm_desc (kai0hip.h: persist / general_epilogue / small_w8), all 0 in production.  They travel with
 # every call's descriptor — the library itself has no process-wide switch; tests and tools set them through `gemm_tuning(...)`.
 # (KAI0_GEMM_PERSIST=0 / 1 / 2 — never / the library's rule / every eligible NT launch — is read HERE, on the host side of the boundary.)
-GEMM_TUNING = {"tile_cfg": 0, "persist": {"0": 1, "2": 2}.get(os.environ.get("KAI0_GEMM_PERSIST", "1"), 0), "general_epilogue": 0,
+GEMM_TUNING = {"persist": {"0": 1, "2": 2}.get(os.environ.get("KAI0_GEMM_PERSIST", "1"), 0), "general_epilogue": 0,
                "small_w8": {"0": 1, "2": 2}.get(os.environ.get("KAI0_GEMM_W8", "1"), 0)}  # env 0 / 1 / 2 = never / the rule / always, like KAI0_GEMM_PERSIST
 
 
@@ -152,8 +152,7 @@ def gemm(
         if nb is not None:
             _chk(nb, BF16, "gemm: norm bias")
             d.norm_b = nb.data_ptr()
-    d.tile_cfg, d.persist, d.general_epilogue, d.small_w8 = (GEMM_TUNING["tile_cfg"], GEMM_TUNING["persist"], GEMM_TUNING["general_epilogue"],
-                                                               GEMM_TUNING["small_w8"])
+    d.persist, d.general_epilogue, d.small_w8 = GEMM_TUNING["persist"], GEMM_TUNING["general_epilogue"], GEMM_TUNING["small_w8"]
     _lib.call("kai0_gemm_bf16", C.byref(d), _stream())
     return out
 

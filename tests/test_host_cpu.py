@@ -230,8 +230,8 @@ def test_product_never_imports_oracle():
 
 
 # ------------------------------------------------------------------------------------------------ C-ABI
-def test_cabi_exports_every_declared_symbol():
-    """libkai0hip.so loads and exports exactly what include/kai0hip.h declares (no compute call here)."""
+def test_cabi_v2_exports_every_declared_symbol():
+    """libkai0hip.so loads, reports C ABI version 2 and exports exactly what include/kai0hip.h declares (no compute call here)."""
     import ctypes
 
     from kai0_amd import _lib
@@ -242,8 +242,31 @@ def test_cabi_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in kai0hip.h but not exported"
     assert declared == set(_lib.EXPORTED_SYMBOLS), declared ^ set(_lib.EXPORTED_SYMBOLS)
-    assert lib.kai0_abi_version() == 1
+    assert lib.kai0_abi_version() == 2
     assert ctypes.sizeof(_lib.GemmDesc) == lib.kai0_gemm_desc_size()
+
+
+def test_cabi_version_mismatch_is_rejected(monkeypatch):
+    """_lib.load() refuses a library whose kai0_abi_version() differs from the version the binding's mirrors describe."""
+    from kai0_amd import _lib
+
+    monkeypatch.setattr(_lib, "_lib", None)  # no cached handle: load() opens and checks the library again
+    monkeypatch.setattr(_lib, "ABI_VERSION", _lib.ABI_VERSION + 1)
+    with pytest.raises(_lib.Kai0HipError, match="ABI version"):
+        _lib.load()
+    assert _lib._lib is None
+
+
+def test_gemm_tuning_hooks_are_the_descriptor_hooks():
+    """ops.GEMM_TUNING mirrors exactly the hook fields of kai0_gemm_desc; any other name (the removed tile_cfg too) is a KeyError."""
+    from kai0_amd import _lib, ops
+
+    fields = [f for f, _ in _lib.GemmDesc._fields_]
+    assert fields[-4:] == ["persist", "general_epilogue", "small_w8", "_pad3"]
+    assert set(ops.GEMM_TUNING) == {"persist", "general_epilogue", "small_w8"}
+    with pytest.raises(KeyError):
+        with ops.gemm_tuning(tile_cfg=5):
+            pass
 
 
 def test_pack_skinny_weight_layout():
