@@ -594,6 +594,21 @@ int kai0_adamw(float* master, float* m, float* v, const void* grad, int grad_f32
 int kai0_adamw_rows(float* master, float* m, float* v, const void* grad, int grad_f32, void* model_param, int param_f32,
                     int64_t n_rows, int row_len, unsigned char* row_active, float lr, float beta1, float beta2, float eps, float wd,
                     float bias_c1, float bias_c2, const float* clip_coef, kai0_stream_t stream);
+/* kai0_adamw with the parameter EMA in the same pass (the JAX trainer's ema_decay, scripts/train.py:172-177): after the update
+ * that gives the new master p,  ema = ema + (1 - ema_decay) * (p - ema)  in f32 (= d * ema + (1 - d) * p in the form for which
+ * ema == p is a fixed point; no bias correction, no warm-up of the decay).  master, m, v and the model copy come out bit-identical
+ * to kai0_adamw on the same inputs.  ema: f32 [n], non-null; 0 <= ema_decay < 1.  Buffers may start at any element (shard slices):
+ * 16-byte accesses are used when all of them reach their vector alignment at the same element, scalar ones otherwise. */
+int kai0_adamw_ema(float* master, float* m, float* v, float* ema, const void* grad, int grad_f32, void* model_param,
+                   int param_f32, int64_t n, float lr, float beta1, float beta2, float eps, float wd, float bias_c1,
+                   float bias_c2, float ema_decay, const float* clip_coef, kai0_stream_t stream);
+/* kai0_adamw_rows with the EMA: a row with a zero gradient and row_active == 0 is skipped, EMA included — exact when additionally
+ * ema == master on that row, so row_active must be set for every row whose moments may be nonzero OR whose ema may differ from
+ * its master (all 1 is always valid).  Bit-identical to kai0_adamw_ema on the same buffers under that condition. */
+int kai0_adamw_rows_ema(float* master, float* m, float* v, float* ema, const void* grad, int grad_f32, void* model_param,
+                        int param_f32, int64_t n_rows, int row_len, unsigned char* row_active, float lr, float beta1,
+                        float beta2, float eps, float wd, float bias_c1, float bias_c2, float ema_decay,
+                        const float* clip_coef, kai0_stream_t stream);
 /* coef[0] = min(1, max_norm / (sqrt(sumsq[0]) + 1e-6)) ; norm_out[0] = sqrt(sumsq[0])
  * (torch.nn.utils.clip_grad_norm_) */
 int kai0_clip_coef(const float* sumsq, float max_norm, float* coef, float* norm_out, kai0_stream_t stream);

@@ -60,6 +60,44 @@ def adamw_rows_step_(master, m, v, grad, param, row_len: int, row_active, *, lr,
               bc1, bc2, None if clip_coef is None else clip_coef.data_ptr(), _stream())  # fmt: skip
 
 
+def adamw_ema_step_(master, m, v, ema, grad, param, *, lr, beta1, beta2, eps, wd, step: int, ema_decay: float, clip_coef=None):
+    """kai0_adamw_ema: adamw_step_ (bit-identical master / moments / model copy) and, in the same pass over the shard,
+    ema += (1 - ema_decay) * (new master - ema) in f32."""
+    WEIGHT_UPDATES[0] += 1
+    n = master.numel()
+    assert ema.numel() == n and ema.dtype == F32
+    bc1 = 1.0 - beta1**step
+    bc2 = 1.0 - beta2**step
+    _lib.call("kai0_adamw_ema", master.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), grad.data_ptr(), int(grad.dtype == F32),
+              param.data_ptr(), int(param.dtype == F32), n, lr, beta1, beta2, eps, wd, bc1, bc2, float(ema_decay),
+              None if clip_coef is None else clip_coef.data_ptr(), _stream())  # fmt: skip
+
+
+def adamw_rows_ema_step_(master, m, v, ema, grad, param, row_len: int, row_active, *, lr, beta1, beta2, eps, wd, step: int,
+                         ema_decay: float, clip_coef=None):
+    """kai0_adamw_rows_ema: adamw_rows_step_ with the EMA.  An idle row is skipped, EMA included, so `row_active` must also be set
+    for every row whose ema may differ from its master (sharded._sparse_segments builds the flags that way)."""
+    WEIGHT_UPDATES[0] += 1
+    n = master.numel()
+    assert n % row_len == 0 and row_active.numel() == n // row_len and row_active.dtype == torch.uint8
+    assert ema.numel() == n and ema.dtype == F32
+    bc1 = 1.0 - beta1**step
+    bc2 = 1.0 - beta2**step
+    _lib.call("kai0_adamw_rows_ema", master.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), grad.data_ptr(),
+              int(grad.dtype == F32), param.data_ptr(), int(param.dtype == F32), n // row_len, row_len, row_active.data_ptr(), lr,
+              beta1, beta2, eps, wd, bc1, bc2, float(ema_decay), None if clip_coef is None else clip_coef.data_ptr(), _stream())  # fmt: skip
+
+
+def check_ema_decay(ema_decay):
+    """None (EMA off) or a decay in [0, 1) as a float."""
+    if ema_decay is None:
+        return None
+    d = float(ema_decay)
+    if not 0.0 <= d < 1.0:
+        raise ValueError(f"ema_decay must be in [0, 1) or None, got {ema_decay!r}")
+    return d
+
+
 _SUMSQ_SCRATCH: dict = {}
 
 
@@ -87,9 +125,11 @@ class FusedAdamW:
     """torch.optim.AdamW-shaped optimizer (param_groups with "lr", step(), zero_grad(), state_dict()).
 
     step() = [sum of squared grads over all params -> clip coefficient on device] -> fused AdamW per tensor.
-    No host synchronisation: the clip coefficient stays in device memory and is read by the update kernel."""
+    No host synchronisation: the clip coefficient stays in device memory and is read by the update kernel.
+    `ema_decay` (None = off): an f32 EMA of the master copies, state[p]["ema"], updated inside the same kernel (kai0_adamw_ema)."""
 
-    def __init__(self, params, lr=2.5e-5, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-10, max_grad_norm=1.0):
+    def __init__(self, params, lr=2.5e-5, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-10, max_grad_norm=1.0, ema_decay=None):
+        self.ema_decay = check_ema_decay(ema_decay)
         self.params = [p for p in params if p.requires_grad]
         # tied parameters appear once
         seen, uniq = set(), []
@@ -109,12 +149,20 @@ class FusedAdamW:
                 "exp_avg": torch.zeros(p.shape, dtype=F32, device=p.device),
                 "exp_avg_sq": torch.zeros(p.shape, dtype=F32, device=p.device),
             }
+            if self.ema_decay is not None:
+                self.state[p]["ema"] = self.state[p]["master"].clone()
         self._sumsq = torch.zeros(1, dtype=F32, device=dev)
         self._coef = torch.ones(1, dtype=F32, device=dev)
         self._norm = torch.zeros(1, dtype=F32, device=dev)
 
     def master_params(self):
         return [self.state[p]["master"] for p in self.params]
+
+    def ema_params(self):
+        """The f32 EMA of every parameter's master copy, in `params` order (needs ema_decay)."""
+        if self.ema_decay is None:
+            raise RuntimeError("FusedAdamW was built without ema_decay: there is no EMA")
+        return [self.state[p]["ema"] for p in self.params]
 
     def zero_grad(self, set_to_none: bool = True):
         for p in self.params:
@@ -139,6 +187,10 @@ class FusedAdamW:
             coef = self._coef
         for p in live:
             st = self.state[p]
+            if self.ema_decay is not None:
+                adamw_ema_step_(st["master"], st["exp_avg"], st["exp_avg_sq"], st["ema"], p.grad.contiguous(), p.data, lr=lr,
+                                beta1=b1, beta2=b2, eps=eps, wd=wd, step=self.step_count, ema_decay=self.ema_decay, clip_coef=coef)  # fmt: skip
+                continue
             adamw_step_(st["master"], st["exp_avg"], st["exp_avg_sq"], p.grad.contiguous(), p.data, lr=lr, beta1=b1,
                         beta2=b2, eps=eps, wd=wd, step=self.step_count, clip_coef=coef)  # fmt: skip
         return self._norm
@@ -157,3 +209,5 @@ class FusedAdamW:
         for p, st in zip(self.params, sd["state"], strict=True):
             for k in ("master", "exp_avg", "exp_avg_sq"):
                 self.state[p][k].copy_(st[k])
+            if self.ema_decay is not None:  # a state written without EMA: the average starts from the master
+                self.state[p]["ema"].copy_(st["ema"] if "ema" in st else st["master"])

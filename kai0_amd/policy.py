@@ -138,13 +138,15 @@ def create_policy(model, *, norm_stats: Mapping | None, tokenizer, action_dim: i
 
 def create_trained_policy(train_config, checkpoint_dir, *, repack_transforms: _transforms.Group | None = None,
                           sample_kwargs: dict[str, Any] | None = None, default_prompt: str | None = None,
-                          norm_stats: Mapping | None = None, pytorch_device: str | None = None) -> Policy:  # fmt: skip
+                          norm_stats: Mapping | None = None, pytorch_device: str | None = None, ema: bool = False) -> Policy:  # fmt: skip
     """`policy_config.create_trained_policy` (policy_config.py:16-94) for torch checkpoints: `model.safetensors` in
     `checkpoint_dir` -> `train_config.model.load_pytorch` -> bf16 storage -> the transform stack of the reference:
       inputs : repack -> InjectDefaultPrompt -> data transforms -> Normalize -> model transforms
       outputs: model outputs -> Unnormalize -> data outputs -> repack outputs
     Norm stats come from `<checkpoint_dir>/assets/<asset_id>` (the stats the run was trained with) unless given.  A
-    checkpoint directory without `model.safetensors` is a JAX checkpoint: convert it first (kai0_amd.convert)."""
+    checkpoint directory without `model.safetensors` is a JAX checkpoint: convert it first (kai0_amd.convert).
+    `ema=True` serves the averaged weights, `model_ema.safetensors` (written by a trainer that ran with an EMA decay), as the
+    reference's JAX checkpoints do; a checkpoint without that file is an error, never a silent fall-back to the raw weights."""
     import os
     import pathlib
 
@@ -152,7 +154,10 @@ def create_trained_policy(train_config, checkpoint_dir, *, repack_transforms: _t
 
     repack_transforms = repack_transforms or _transforms.Group()
     checkpoint_dir = pathlib.Path(checkpoint_dir)
-    weight_path = os.path.join(checkpoint_dir, "model.safetensors")
+    weight_path = os.path.join(checkpoint_dir, "model_ema.safetensors" if ema else "model.safetensors")
+    if ema and not os.path.exists(weight_path):
+        raise FileNotFoundError(f"{weight_path} not found: this checkpoint holds no EMA weights (it was written by a run without an "
+                                "EMA decay; train with KAI0_EMA=1 / Trainer(ema_decay=...), or serve the raw weights with ema=False)")  # fmt: skip
     if not os.path.exists(weight_path):
         raise FileNotFoundError(f"{weight_path} not found: kai0_amd serves torch checkpoints (model.safetensors); a JAX `params` "
                                 "checkpoint has to go through kai0_amd.convert first")  # fmt: skip

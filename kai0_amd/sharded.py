@@ -35,6 +35,10 @@ stream has to wait for a collective (a parameter gather in pre_forward / pre_bac
 all-reduce in step()) is bracketed by two events on the compute stream, so `comm_exposed_ms` is the time the chip sat in those
 waits — what overlap did NOT hide — next to the bytes each rank moved.
 
+Parameter EMA (`ema_decay`, off by default; the JAX trainer's, scripts/train.py:172-177): a fourth f32 shard per bucket beside master
+and moments, ema += (1 - d) (master - ema) inside the AdamW pass (kai0_adamw_ema: 8 B per element more, no launch more), saved with
+the optimizer state; `ema_weights()` puts the averaged weights into the model for an evaluation / a checkpoint and takes them out again.
+
 The whole optimizer is 3 kernels per bucket on flat shards (sum of squares, clip coefficient kept on device, fused
 AdamW) — no per-tensor launches, no host sync.  The arithmetic is pluggable (`ShardOps`) only so the collective /
 partition logic can be exercised on CPU with gloo; the product default is the HIP kernels and raises without them.
@@ -42,6 +46,7 @@ partition logic can be exercised on CPU with gloo; the product default is the HI
 
 from __future__ import annotations
 
+import contextlib
 import functools
 import os
 
@@ -74,12 +79,30 @@ class HipShardOps:
 
         adamw_step_(master, m, v, grad, param, lr=lr, beta1=beta1, beta2=beta2, eps=eps, wd=wd, step=step, clip_coef=clip_coef)
 
-
     def adamw_rows(self, master, m, v, grad, param, row_len, row_active, *, lr, beta1, beta2, eps, wd, step, clip_coef):
         from .optim import adamw_rows_step_
 
         adamw_rows_step_(master, m, v, grad, param, row_len, row_active, lr=lr, beta1=beta1, beta2=beta2, eps=eps, wd=wd, step=step,
                          clip_coef=clip_coef)  # fmt: skip
+
+    def adamw_ema(self, master, m, v, ema, grad, param, *, lr, beta1, beta2, eps, wd, step, clip_coef, ema_decay):
+        from .optim import adamw_ema_step_
+
+        adamw_ema_step_(master, m, v, ema, grad, param, lr=lr, beta1=beta1, beta2=beta2, eps=eps, wd=wd, step=step,
+                        ema_decay=ema_decay, clip_coef=clip_coef)  # fmt: skip
+
+    def adamw_rows_ema(self, master, m, v, ema, grad, param, row_len, row_active, *, lr, beta1, beta2, eps, wd, step, clip_coef,
+                       ema_decay):
+        from .optim import adamw_rows_ema_step_
+
+        adamw_rows_ema_step_(master, m, v, ema, grad, param, row_len, row_active, lr=lr, beta1=beta1, beta2=beta2, eps=eps, wd=wd,
+                             step=step, ema_decay=ema_decay, clip_coef=clip_coef)  # fmt: skip
+
+
+def ema_lerp_weight(ema_decay: float) -> float:
+    """1 - d as the kernels form it: from the decay rounded to f32 (so the torch fallback `ema.lerp_(master, w)` and kai0_adamw_ema
+    move the average by the same fraction)."""
+    return 1.0 - float(torch.tensor(float(ema_decay), dtype=F32))
 
 
 class _Bucket:
@@ -125,13 +148,15 @@ class _Bucket:
         self.rs_work = None  # in-flight reduce-scatter of the gradients
         self.ag_work = None  # in-flight all-gather of the parameters
 
-    def carve_shards(self):
+    def carve_shards(self, ema: bool = False):
         sl = self.flat_param[self.lo : self.lo + self.shard]
         # fsdp: the shard outlives the full buffer, so it owns its memory; zero2: a slice (in-place all-gather)
         self.param_shard = sl.clone() if self.fsdp else sl
         self.master = sl.to(F32).clone()
         self.exp_avg = torch.zeros(self.shard, dtype=F32, device=sl.device)
         self.exp_avg_sq = torch.zeros(self.shard, dtype=F32, device=sl.device)
+        if ema:  # (a bucket of an engine without EMA has no such attribute)
+            self.ema = self.master.clone()
 
 
 class _AllPairsReduce:
@@ -211,9 +236,17 @@ def plan_partition(units, *, world_size: int, bucket_bytes: int, exclude=()):
 class ShardedDataParallel:
     def __init__(self, params, *, world_size: int, rank: int, group=None, ops=None, betas=(0.9, 0.95), eps=1e-8,
                  weight_decay=1e-10, max_grad_norm=1.0, bucket_bytes: int = 512 << 20, units=None, mode: str = "zero2",
-                 prefetch: int = 1, sync_params: bool = True, rs_algo: str | None = None):  # fmt: skip
+                 prefetch: int = 1, sync_params: bool = True, rs_algo: str | None = None, ema_decay: float | None = None):  # fmt: skip
         """`params`: parameters, or (name, parameter) pairs (names make the checkpoint world-size independent).
-        `units`: [(unit name, [parameters])] in forward-use order; parameters not listed form a last unit "rest"."""
+        `units`: [(unit name, [parameters])] in forward-use order; parameters not listed form a last unit "rest".
+        `ema_decay`: None (default) = no EMA, nothing allocated, the kernels of before; d in [0, 1) = an f32 EMA shard per bucket,
+        initialised from the master, ema += (1 - d) (master - ema) after every update."""
+        if ema_decay is not None:
+            ema_decay = float(ema_decay)
+            if not 0.0 <= ema_decay < 1.0:
+                raise ValueError(f"ema_decay must be in [0, 1) or None, got {ema_decay!r}")
+        self.ema_decay = ema_decay
+        self._in_ema = False  # inside ema_weights(): the model holds the averaged weights
         if mode not in ("zero2", "fsdp"):
             raise ValueError(f"mode must be 'zero2' or 'fsdp', got {mode!r}")
         rs_algo = rs_algo or os.environ.get("KAI0_RS_ALGO", "rccl")
@@ -295,7 +328,7 @@ class ShardedDataParallel:
             for b in self.buckets:
                 dist.broadcast(b.flat_param, src=src, group=group)
         for b in self.buckets:
-            b.carve_shards()
+            b.carve_shards(ema=self.ema_decay is not None)
         self._sumsq = torch.zeros(1, dtype=F32, device=self.device)
         self._coef = torch.ones(1, dtype=F32, device=self.device)
         self._norm = torch.zeros(1, dtype=F32, device=self.device)
@@ -566,7 +599,9 @@ class ShardedDataParallel:
     def sync_master_from_params(self):
         """Adopt weights written into the model after construction (load_state_dict, p.data.copy_, model_arithmetic): the
         f32 master copies (and the fsdp shards) are re-read from the parameters; Adam moments are kept.  Collective in fsdp
-        mode only in the sense that every rank must call it."""
+        mode only in the sense that every rank must call it.  The EMA is left alone: it moves towards the new weights at rate
+        1 - d per step, as after any other jump of the iterate (`reset_ema()` restarts it from them instead)."""
+        self._not_in_ema("sync_master_from_params()")
         self.wait_params()
         self._check_views()
         for b in self.buckets:
@@ -574,8 +609,73 @@ class ShardedDataParallel:
             b.master.copy_(sl)
             if b.fsdp:
                 b.param_shard.copy_(sl)
+            if self.ema_decay is not None:
+                b._sparse_key = None  # rows written here have ema != master: their activity flags are rebuilt at the next step
         if self.mode == "fsdp":
             self.release_params()
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """EMA := master: the average restarts from the current weights (after sync_master_from_params(), model_arithmetic, ...)."""
+        if self.ema_decay is None:
+            raise RuntimeError("the engine was built without ema_decay: there is no EMA")
+        for b in self.buckets:
+            b.ema.copy_(b.master)
+            b._sparse_key = None
+
+    def _not_in_ema(self, what: str):
+        if self._in_ema:
+            raise RuntimeError(f"{what} inside ema_weights(): the model holds the averaged weights, leave the context first")
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model's parameters are the EMA, rounded to each parameter's dtype, complete on every rank (as after
+        `wait_params()`); on exit they are the raw weights again, bit for bit, and fsdp releases the full buffers as step() does.
+        COLLECTIVE: every rank enters and leaves it.  Masters, moments and the EMA are not touched; step(), load_state_dict() and
+        sync_master_from_params() inside the context raise.
+
+        The raw weights are restored from a copy of this rank's parameter shard taken on entry (2 B x parameters / N for the
+        duration), not re-rounded from the masters: after `load_state_dict()` with masters from a file and weights from another the
+        model copy is not guaranteed to be the rounded master, and leaving the context must not change what the model computes."""
+        if self.ema_decay is None:
+            raise RuntimeError("the engine was built without ema_decay: there is no EMA")
+        self._not_in_ema("ema_weights()")
+        self.wait_params()  # every gather in flight has landed (zero2: the ones step() started write into flat_param)
+        self._check_views()
+        fsdp = self.mode == "fsdp"
+        if fsdp:
+            self.release_params()
+        saved = [b.param_shard.clone() for b in self.buckets]
+        self._in_ema = True
+        try:
+            with torch.no_grad():
+                self._fill_param_shards([b.ema for b in self.buckets])
+            yield self
+        finally:
+            self._in_ema = False
+            with torch.no_grad():
+                if fsdp:
+                    self.release_params()
+                    from .optim import WEIGHT_UPDATES
+
+                    WEIGHT_UPDATES[0] += 1
+                    for b, raw in zip(self.buckets, saved):
+                        b.param_shard.copy_(raw)
+                    self._issue_gather(0)  # the next forward starts with group 0
+                else:
+                    self._fill_param_shards(saved)
+
+    def _fill_param_shards(self, srcs):
+        """param_shard := src (rounded to the bucket's dtype) for every bucket, then every parameter complete on this rank
+        (zero2: the shard is a slice of the full buffer, all-gathered in place; fsdp: the normal gathers out of the shards)."""
+        from .optim import WEIGHT_UPDATES
+
+        WEIGHT_UPDATES[0] += 1  # the weights change under a captured inference engine (infer.InferenceEngine._fingerprint)
+        for b, src in zip(self.buckets, srcs):
+            b.param_shard.copy_(src)
+            if not b.fsdp:
+                b.ag_work = self._all_gather(b)
+        self.wait_params()
 
     # ------------------------------------------------------------------------------------------------- step
     @torch.no_grad()
@@ -583,6 +683,7 @@ class ShardedDataParallel:
         """Finish the gradient reduction, clip by the global norm, update the local shards, start the parameter all-gathers
         (zero2; waited for by the next forward, unit by unit).  Returns the global (pre-clip) gradient norm as a 1-element
         device tensor."""
+        self._not_in_ema("step()")
         self.step_count += 1
         self._check_views()
         self._join_streams()  # gradients written by backward nodes on the second stream
@@ -661,7 +762,14 @@ class ShardedDataParallel:
                 # a row is active once its moments may be nonzero: rebuilt from them, so a loaded checkpoint needs nothing extra
                 mm = b.exp_avg[first : first + (r1 - r0) * rl].view(r1 - r0, rl)
                 vv = b.exp_avg_sq[first : first + (r1 - r0) * rl].view(r1 - r0, rl)
-                active = ((mm != 0).any(1) | (vv != 0).any(1)).to(torch.uint8)
+                active = (mm != 0).any(1) | (vv != 0).any(1)
+                if self.ema_decay is not None:
+                    # ... or its EMA may differ from its master: skipping a row is exact for the EMA only at its fixed point
+                    # ema == master (weights written into idle rows by sync_master_from_params(), an EMA loaded from a file)
+                    ee = b.ema[first : first + (r1 - r0) * rl].view(r1 - r0, rl)
+                    pp = b.master[first : first + (r1 - r0) * rl].view(r1 - r0, rl)
+                    active = active | (ee != pp).any(1)
+                active = active.to(torch.uint8)
                 segs.append((first, r1 - r0, rl, active))
         b._sparse_key, b._sparse_segs = key, segs
         return segs
@@ -669,7 +777,21 @@ class ShardedDataParallel:
     def _update_bucket(self, b: _Bucket, lr: float, coef):
         kw = dict(lr=lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, wd=self.wd, step=self.step_count, clip_coef=coef)
         segs = []
-        if self._sparse_rows and hasattr(self.ops, "adamw_rows"):
+        ema_on = self.ema_decay is not None
+        fused = ema_on and hasattr(self.ops, "adamw_ema")
+
+        def dense(lo, hi):
+            args = (b.exp_avg[lo:hi], b.exp_avg_sq[lo:hi])
+            if fused:
+                self.ops.adamw_ema(b.master[lo:hi], *args, b.ema[lo:hi], b.grad_shard[lo:hi], b.param_shard[lo:hi],
+                                   ema_decay=self.ema_decay, **kw)  # fmt: skip
+                return
+            self.ops.adamw(b.master[lo:hi], *args, b.grad_shard[lo:hi], b.param_shard[lo:hi], **kw)
+            if ema_on:  # an ops object without the fused form (the torch oracle of the CPU tests): the same update as a second pass
+                b.ema[lo:hi].lerp_(b.master[lo:hi], ema_lerp_weight(self.ema_decay))
+
+        # with EMA the row-sparse form must know about it (an ops object that does not falls back to the dense update)
+        if self._sparse_rows and hasattr(self.ops, "adamw_rows_ema" if ema_on else "adamw_rows"):
             from .optim import sparse_rows_ok
 
             if sparse_rows_ok(lr, self.wd):  # an idle row must be a fixed point of the update (1 - lr*wd rounds to 1)
@@ -682,14 +804,17 @@ class ShardedDataParallel:
         cur = 0
         for first, rows, rl, active in segs:
             if first > cur:
-                self.ops.adamw(b.master[cur:first], b.exp_avg[cur:first], b.exp_avg_sq[cur:first], b.grad_shard[cur:first],
-                               b.param_shard[cur:first], **kw)  # fmt: skip
+                dense(cur, first)
             end = first + rows * rl
-            self.ops.adamw_rows(b.master[first:end], b.exp_avg[first:end], b.exp_avg_sq[first:end], b.grad_shard[first:end],
-                                b.param_shard[first:end], rl, active, **kw)  # fmt: skip
+            if ema_on:
+                self.ops.adamw_rows_ema(b.master[first:end], b.exp_avg[first:end], b.exp_avg_sq[first:end], b.ema[first:end],
+                                        b.grad_shard[first:end], b.param_shard[first:end], rl, active, ema_decay=self.ema_decay, **kw)  # fmt: skip
+            else:
+                self.ops.adamw_rows(b.master[first:end], b.exp_avg[first:end], b.exp_avg_sq[first:end], b.grad_shard[first:end],
+                                    b.param_shard[first:end], rl, active, **kw)  # fmt: skip
             cur = end
         if cur < b.shard:
-            self.ops.adamw(b.master[cur:], b.exp_avg[cur:], b.exp_avg_sq[cur:], b.grad_shard[cur:], b.param_shard[cur:], **kw)
+            dense(cur, b.shard)
 
     # ------------------------------------------------------------------------------------------ checkpointing
     @torch.no_grad()
@@ -697,12 +822,12 @@ class ShardedDataParallel:
         """World-size independent optimizer state, shaped like `torch.optim.AdamW.state_dict()` (the reference's
         `optimizer.pt`, train_pytorch.py:170-180): state[i] = {step, exp_avg, exp_avg_sq} for parameter i of `param_order`
         (names in `model.named_parameters()` order — the order torch indexes them in; default: this engine's bucket order),
-        plus this engine's f32 `master` copy and the name list.  Parameters the engine does not train have no entry, as in
-        torch.  COLLECTIVE: every rank calls it; rank 0 gets the dictionary (CPU tensors), the others None."""
+        plus this engine's f32 `master` copy (and, with EMA, the f32 `ema`) and the name list.  Parameters the engine does not train
+        have no entry, as in torch.  COLLECTIVE: every rank calls it; rank 0 gets the dictionary (CPU tensors), the others None."""
         by_name = {}
         for b in self.buckets:
             fulls = {}
-            for key in ("master", "exp_avg", "exp_avg_sq"):
+            for key in ("master", "exp_avg", "exp_avg_sq") + (("ema",) if self.ema_decay is not None else ()):
                 sh = getattr(b, key)
                 if self.collectives:
                     full = torch.empty(b.numel, dtype=F32, device=self.device)
@@ -732,7 +857,9 @@ class ShardedDataParallel:
         optimizer.pt: index = position in model.parameters(), bf16 moments, no master, no entry for parameters that never
         received a gradient) therefore loads too: moments are widened to f32, master copies missing from the file are taken
         from the current parameters, parameters without an entry start from zero moments.  The model weights must already be in
-        place (load them first): the fsdp shards are re-read from them."""
+        place (load them first): the fsdp shards are re-read from them.  With EMA: `ema` is taken by name like the rest; an entry
+        without it (a state written without EMA, the reference's optimizer.pt) starts the average from the master as loaded."""
+        self._not_in_ema("load_state_dict()")
         pnames = sd.get("param_names", param_order)
         if pnames is None:
             raise ValueError("optimizer state without `param_names` needs param_order (names in model.named_parameters() order)")
@@ -745,6 +872,7 @@ class ShardedDataParallel:
         # A missing entry = "never updated": zero moments, master copy = the current parameter.  Master copies are adopted per
         # parameter — an entry without `master` (torch-shaped file) does not discard the f32 masters other entries carry.
         from_params: list[tuple[_Bucket, int, int]] = []  # (bucket, lo, hi) slices whose master comes from the parameters
+        ema_from_master: list[tuple[_Bucket, int, int]] = []  # slices whose EMA starts from the master, once that is settled
         absent = []
         for b in self.buckets:
             for p, o, n in zip(b.params, b.offsets, b.names):
@@ -753,11 +881,13 @@ class ShardedDataParallel:
                 if ent is None:
                     absent.append(n)
                     ent = {}
-                for key in ("exp_avg", "exp_avg_sq", "master"):
+                for key in ("exp_avg", "exp_avg_sq", "master") + (("ema",) if self.ema_decay is not None else ()):
                     if key not in ent:
                         if lo < hi:
                             if key == "master":
                                 from_params.append((b, lo, hi))
+                            elif key == "ema":
+                                ema_from_master.append((b, lo, hi))
                             else:
                                 getattr(b, key)[lo - b.lo : hi - b.lo].zero_()
                         continue
@@ -777,6 +907,8 @@ class ShardedDataParallel:
         self._check_views()
         for b, lo, hi in from_params:  # the alignment padding between parameters keeps whatever the master held (zeros)
             b.master[lo - b.lo : hi - b.lo].copy_(b.flat_param[lo:hi])
+        for b, lo, hi in ema_from_master:  # after the masters, the ones just taken from the parameters included
+            b.ema[lo - b.lo : hi - b.lo].copy_(b.master[lo - b.lo : hi - b.lo])
         for b in self.buckets:
             if b.fsdp:
                 b.param_shard.copy_(b.flat_param[b.lo : b.lo + b.shard])
@@ -784,4 +916,4 @@ class ShardedDataParallel:
             self.release_params()
 
     def optimizer_state_bytes(self) -> int:
-        return sum(3 * 4 * b.shard for b in self.buckets)
+        return sum((3 if self.ema_decay is None else 4) * 4 * b.shard for b in self.buckets)

@@ -6,7 +6,9 @@ One process per GPU; `Trainer.train_step(observation, actions)` = LR schedule ->
 for its own parameter all-gather) -> backward (gradient reduce-scatter per bucket, issued from inside backward) -> global-norm
 clip -> sharded fused AdamW -> parameter all-gathers started (zero2) / shards kept (fsdp).  Checkpoints follow the reference
 layout (train_pytorch.py:149-194): `model.safetensors` + ONE world-size independent `optimizer.pt` + `metadata.pt`, written to
-`tmp_<step>` then renamed atomically; a checkpoint resumes on any number of GPUs.
+`tmp_<step>` then renamed atomically; a checkpoint resumes on any number of GPUs.  With a parameter EMA (`Trainer(ema_decay=...)`,
+`KAI0_EMA=1` for `train_loop`; the JAX trainer's scripts/train.py:172-177) the f32 average rides in `optimizer.pt` and its rounded
+copy is written beside the raw weights as `model_ema.safetensors` — the file `create_trained_policy(..., ema=True)` serves.
 
 Weights must be in the model BEFORE the Trainer is built (it moves every parameter into flat buffers and cuts its f32 master
 copies from them); weights written in place afterwards (`load_state_dict`, `p.data.copy_`, model_arithmetic) are adopted
@@ -15,6 +17,7 @@ with `Trainer.sync_weights()`.  Rebinding `p.data` afterwards (dtype casts, `.to
 
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import logging
 import os
@@ -34,11 +37,13 @@ from .sharded import ShardedDataParallel
 class Trainer:
     def __init__(self, model, *, world_size: int = 1, rank: int = 0, group=None, peak_lr=2.5e-5, warmup_steps=1000,
                  decay_steps=30000, end_lr=2.5e-6, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-10, clip_norm=1.0,
-                 shard_ops=None, bucket_bytes: int | None = None, mode: str | None = None, prefetch: int | None = None):  # fmt: skip
+                 shard_ops=None, bucket_bytes: int | None = None, mode: str | None = None, prefetch: int | None = None,
+                 ema_decay: float | None = None):  # fmt: skip
         """`bucket_bytes` / `prefetch` default per mode: zero2 512 MB buckets (few, large collectives; nothing waits on them
         inside forward / backward); fsdp 256 MB (~ one joint Gemma-2B + expert layer, SURVEY.md §8e's unit) gathered two
         buckets ahead, so that a bucket's gather has two layers of compute to hide behind and ~0.75 GB of full parameters
-        are live at a time."""
+        are live at a time.  `ema_decay`: None = no parameter EMA (default); else the engine keeps an f32 EMA of the master weights,
+        updated inside the AdamW pass (sharded.ShardedDataParallel)."""
         self.model = model
         self.world, self.rank = world_size, rank
         self.sched = dict(warmup_steps=warmup_steps, peak_lr=peak_lr, decay_steps=decay_steps, end_lr=end_lr)
@@ -57,7 +62,7 @@ class Trainer:
             prefetch = int(os.environ.get("KAI0_FSDP_PREFETCH", "2" if mode == "fsdp" else "1"))
         self.engine = ShardedDataParallel(named, world_size=world_size, rank=rank, group=group, ops=shard_ops, betas=betas,
                                           eps=eps, weight_decay=weight_decay, max_grad_norm=clip_norm,
-                                          bucket_bytes=bucket_bytes, units=units, mode=mode, prefetch=prefetch)  # fmt: skip
+                                          bucket_bytes=bucket_bytes, units=units, mode=mode, prefetch=prefetch, ema_decay=ema_decay)  # fmt: skip
         # the model announces its units (pre_forward / post_forward): parameter gathers are awaited layer by layer
         self._hooked = hasattr(model, "set_unit_hooks")
         if self._hooked:
@@ -90,6 +95,26 @@ class Trainer:
         if getattr(self.model, "_engine", None) is not None:
             self.model.invalidate_inference_engine()
 
+    @property
+    def ema_decay(self):
+        return self.engine.ema_decay
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """The model computes with the averaged (EMA) weights inside the context and with the raw ones again after it (every rank
+        enters and leaves it; no train_step inside).  A captured inference engine is dropped on both edges: a graph captured on
+        raw weights is never replayed on averaged ones, nor the reverse."""
+        self._invalidate_inference()
+        with self.engine.ema_weights():
+            try:
+                yield self
+            finally:
+                self._invalidate_inference()
+
+    def _invalidate_inference(self):
+        if getattr(self.model, "_engine", None) is not None:
+            self.model.invalidate_inference_engine()
+
     def params_ready(self):
         """All parameters complete on this GPU (before sample_actions / a state_dict() read between steps)."""
         self.engine.wait_params()
@@ -117,6 +142,13 @@ class Trainer:
                 shutil.rmtree(tmp)
             os.makedirs(tmp, exist_ok=True)
             save_model_safetensors(self.model, os.path.join(tmp, "model.safetensors"))
+        if self.engine.ema_decay is not None:
+            # the averaged weights in the layout of model.safetensors (same keys, dtypes, tied lm_head): what a policy is served from.
+            # model.safetensors keeps the raw weights and stays what load_checkpoint resumes from; the f32 EMA is in optimizer.pt
+            with self.ema_weights():  # (collective: every rank)
+                if self.rank == 0:
+                    save_model_safetensors(self.model, os.path.join(tmp, "model_ema.safetensors"))
+        if self.rank == 0:
             torch.save(opt_sd, os.path.join(tmp, "optimizer.pt"))
             # (not in the reference's metadata) the ranks' RNG states: with them and `skip_batches` a resumed run draws the same
             # noise / time / augmentation and sees the same batches as the run that was interrupted
@@ -281,9 +313,12 @@ def train_loop(config, *, device=None, shard_ops=None, model=None, log=None):
         model = build_model(config, device)
     model.train()
     sch, opt = config.lr_schedule, config.optimizer
+    # `config.ema_decay` (0.99 in every kai0 entry) is what the reference's JAX trainer averages with; its torch trainer ignores it
+    # (train_pytorch.py:510) and so does this loop unless KAI0_EMA=1, so that existing runs do not change
+    ema_decay = config.ema_decay if os.environ.get("KAI0_EMA", "0") == "1" else None
     trainer = Trainer(model, world_size=world, rank=rank, peak_lr=sch.peak_lr, warmup_steps=sch.warmup_steps,
                       decay_steps=sch.decay_steps, end_lr=sch.decay_lr, betas=(opt.b1, opt.b2), eps=opt.eps,
-                      weight_decay=opt.weight_decay, clip_norm=opt.clip_gradient_norm, shard_ops=shard_ops)  # fmt: skip
+                      weight_decay=opt.weight_decay, clip_norm=opt.clip_gradient_norm, shard_ops=shard_ops, ema_decay=ema_decay)  # fmt: skip
     if resuming:
         step = trainer.load_checkpoint(str(ckpt_dir))
         exact = _restore_rng_state(getattr(trainer, "resumed_rng_state", None), world, rank, device)
@@ -291,6 +326,12 @@ def train_loop(config, *, device=None, shard_ops=None, model=None, log=None):
         say(f"Resumed training from step {step}" + ("" if exact else " (no RNG state for this world size: noise / augmentation restart from the seed)"))
     say(f"world_size={world} batch_size={config.batch_size} (per GPU {config.batch_size // world}) num_train_steps={config.num_train_steps} "
         f"mode={trainer.engine.mode} lr: warmup={sch.warmup_steps} peak={sch.peak_lr:.2e} decay_steps={sch.decay_steps} end={sch.decay_lr:.2e}")  # fmt: skip
+
+    if ema_decay is not None:
+        say(f"parameter EMA on: decay={ema_decay} (KAI0_EMA=1); checkpoints carry model_ema.safetensors beside the raw weights")
+    else:
+        say("parameter EMA off" + (" (KAI0_EMA=1, but config.ema_decay is None)" if os.environ.get("KAI0_EMA", "0") == "1"
+                                   else f" (config.ema_decay={config.ema_decay} is ignored unless KAI0_EMA=1)"))  # fmt: skip
 
     records, pending, t0 = [], [], time.time()
     while trainer.global_step < config.num_train_steps:
