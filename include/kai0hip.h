@@ -609,6 +609,15 @@ int kai0_adamw_rows_ema(float* master, float* m, float* v, float* ema, const voi
                         int param_f32, int64_t n_rows, int row_len, unsigned char* row_active, float lr, float beta1,
                         float beta2, float eps, float wd, float bias_c1, float bias_c2, float ema_decay,
                         const float* clip_coef, kai0_stream_t stream);
+/* Gradient accumulation over the micro-batches of one step (kai0_amd.sharded, end_micro_batch):
+ * acc[i] = (first ? 0.f : acc[i]) + (float)grad[i]     one f32 add, grad bf16 or f32, acc f32 [n]
+ * sumsq_out != NULL: additionally sumsq_out[0] += sum_i acc_new[i]^2, from per-block partials added in a fixed order by a
+ * second launch (as kai0_sumsq: no atomics, reproducible bit for bit); scratch: 4096 floats, required iff sumsq_out.
+ * first != 0 OVERWRITES: acc's previous bytes (uninitialised memory, NaN) must not reach the result.
+ * Buffers may start at any element (shard slices), like kai0_adamw_ema: 16-byte accesses where acc and grad reach their
+ * vector alignment at the same element, scalar head / tail / fallback otherwise. */
+int kai0_grad_accum(float* acc, const void* grad, int grad_f32, int64_t n, int first,
+                    float* sumsq_out, float* scratch, kai0_stream_t stream);
 /* coef[0] = min(1, max_norm / (sqrt(sumsq[0]) + 1e-6)) ; norm_out[0] = sqrt(sumsq[0])
  * (torch.nn.utils.clip_grad_norm_) */
 int kai0_clip_coef(const float* sumsq, float max_norm, float* coef, float* norm_out, kai0_stream_t stream);

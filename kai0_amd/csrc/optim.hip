@@ -291,6 +291,56 @@ __global__ __launch_bounds__(256) void adamw_rows_ema_kernel(float* __restrict__
     }
 }
 
+// ---- gradient accumulation over micro-batches (kai0_grad_accum) ---------------------------------------------------------------------
+// acc = (FIRST ? 0 : acc) + grad, one f32 add per element; FIRST never reads acc (it may hold NaN / uninitialised memory).
+template <bool GF32, bool FIRST>
+__device__ __forceinline__ float grad_accum_one(float* __restrict__ acc, const void* __restrict__ grad, int64_t i) {
+    const float g = GF32 ? reinterpret_cast<const float*>(grad)[i] : bf2f(reinterpret_cast<const bf16_t*>(grad)[i]);
+    const float a = FIRST ? g : acc[i] + g;
+    acc[i] = a;
+    return a * a;
+}
+
+// elements [i, i + 4): acc 16-byte aligned at i, a bf16 gradient 8-byte aligned (host-checked).  Returns the sum of the four squares.
+template <bool GF32, bool FIRST>
+__device__ __forceinline__ float grad_accum_vec4(float* __restrict__ acc, const void* __restrict__ grad, int64_t i) {
+    f32x4 g;
+    if constexpr (GF32) {
+        g = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(grad) + i);
+    } else {
+        const bf16x4 gb = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16_t*>(grad) + i);
+        g = f32x4{bf2f(gb[0]), bf2f(gb[1]), bf2f(gb[2]), bf2f(gb[3])};
+    }
+    if constexpr (!FIRST) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(acc + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) g[j] = a[j] + g[j];
+    }
+    *reinterpret_cast<f32x4*>(acc + i) = g;
+    return ((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]) + g[3] * g[3];
+}
+
+// adamw_ema_kernel's layout (its comment has the measurement): scalar head, [head, head + 4 * n4) four at a time with every block on ONE
+// contiguous run of vectors — one per lane up to 2^22 blocks without SUMSQ; with SUMSQ the grid is capped at the 4096 partials the
+// scratch buffer holds, so a block's run is longer and its lanes walk it 256 vectors at a time — scalar tail.  SUMSQ: partial[block] =
+// the block's sum of the squares of the NEW accumulator; sumsq_finish_kernel adds the partials in a fixed order.
+template <bool GF32, bool FIRST, bool SUMSQ>
+__global__ __launch_bounds__(256) void grad_accum_kernel(float* __restrict__ acc, const void* __restrict__ grad, int64_t n, int64_t head,
+                                                         float* __restrict__ partial) {
+    __shared__ float red[4];
+    float sq = 0.f;
+    const int64_t n4 = (n - head) >> 2;
+    const int64_t per = (n4 + gridDim.x - 1) / gridDim.x, lo = per * blockIdx.x, hi = lo + per < n4 ? lo + per : n4;
+    for (int64_t j = lo + threadIdx.x; j < hi; j += 256) sq += grad_accum_vec4<GF32, FIRST>(acc, grad, head + 4 * j);
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = tid; i < head; i += stride) sq += grad_accum_one<GF32, FIRST>(acc, grad, i);
+    for (int64_t i = head + 4 * n4 + tid; i < n; i += stride) sq += grad_accum_one<GF32, FIRST>(acc, grad, i);
+    if constexpr (SUMSQ) {
+        sq = block_sum<4>(sq, red);
+        if (threadIdx.x == 0) partial[blockIdx.x] = sq;
+    }
+}
+
 inline int opt_grid(int64_t n) {
     int64_t b = (n + 255) / 256;
     if (b > 4096) b = 4096;
@@ -407,6 +457,43 @@ KAI0_API int kai0_adamw_ema(float* master, float* m, float* v, float* ema, const
     else LAUNCH(false, false);
 #undef LAUNCH
     return kai0_check_launch("kai0_adamw_ema");
+}
+
+KAI0_API int kai0_grad_accum(float* acc, const void* grad, int grad_f32, int64_t n, int first, float* sumsq_out, float* scratch,
+                            kai0_stream_t stream) {
+    if (n <= 0) return 0;
+    KAI0_REQUIRE(acc && grad, "kai0_grad_accum: null buffer");
+    KAI0_REQUIRE(sumsq_out == nullptr || scratch != nullptr, "kai0_grad_accum: sumsq_out needs a scratch buffer of 4096 floats");
+    const int gsz = grad_f32 ? 4 : 2;
+    KAI0_REQUIRE(((uintptr_t)acc % 4) == 0 && ((uintptr_t)grad % gsz) == 0 && (sumsq_out == nullptr || ((uintptr_t)sumsq_out % 4) == 0) &&
+                     (scratch == nullptr || ((uintptr_t)scratch % 4) == 0),
+                 "kai0_grad_accum: a buffer is not aligned to its element size");
+    // elements before the first 16-byte boundary of `acc`; the gradient must reach its vector alignment at the same element
+    int64_t head = (int64_t)(((16 - ((uintptr_t)acc & 15)) & 15) / 4);
+    if (head > n) head = n;
+    if (!aligned4(grad, head, gsz)) head = n;  // no common head: scalar accesses throughout
+    const int64_t n4 = (n - head) >> 2, rest = n - 4 * n4;
+    // one vector per lane (see adamw_ema_kernel); with the sum of squares one partial per block, and the scratch buffer holds 4096
+    const int64_t cap = sumsq_out ? 4096 : ((int64_t)1 << 22);
+    int64_t blocks = (n4 + 255) / 256;
+    if (blocks > cap) blocks = cap;
+    if (blocks < opt_grid(rest)) blocks = opt_grid(rest);  // the scalar elements are grid-strided: all of them if there is no common head
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((unsigned)blocks), block(256);
+#define LAUNCH(G, F, S) hipLaunchKernelGGL((grad_accum_kernel<G, F, S>), grid, block, 0, s, acc, grad, n, head, scratch)
+#define LAUNCH_GF(G, F)             \
+    do {                            \
+        if (sumsq_out) LAUNCH(G, F, true); \
+        else LAUNCH(G, F, false);   \
+    } while (0)
+    if (grad_f32 && first) LAUNCH_GF(true, true);
+    else if (grad_f32) LAUNCH_GF(true, false);
+    else if (first) LAUNCH_GF(false, true);
+    else LAUNCH_GF(false, false);
+#undef LAUNCH_GF
+#undef LAUNCH
+    if (sumsq_out) hipLaunchKernelGGL(sumsq_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)scratch, (int)blocks, sumsq_out);
+    return kai0_check_launch("kai0_grad_accum");
 }
 
 KAI0_API int kai0_adamw_rows_ema(float* master, float* m, float* v, float* ema, const void* grad, int grad_f32, void* model_param,

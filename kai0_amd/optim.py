@@ -110,6 +110,20 @@ def sumsq_accumulate_(grad, out):
     _lib.call("kai0_sumsq", grad.data_ptr(), int(grad.dtype == F32), grad.numel(), out.data_ptr(), scratch.data_ptr(), _stream())
 
 
+def grad_accum_(acc, grad, *, first: bool, sumsq_out=None):
+    """kai0_grad_accum: acc = (0 if first else acc) + grad in f32 (acc f32, grad bf16 or f32, same length; `first` never reads acc);
+    with `sumsq_out` also sumsq_out[0] += sum(acc_new^2), deterministic like sumsq_accumulate_, in the same pass."""
+    assert acc.dtype == F32 and grad.dtype in (F32, BF16) and acc.numel() == grad.numel()
+    scratch = None
+    if sumsq_out is not None:
+        key = (grad.device.index, _stream())
+        scratch = _SUMSQ_SCRATCH.get(key)
+        if scratch is None:
+            scratch = _SUMSQ_SCRATCH[key] = torch.empty(4096, dtype=F32, device=grad.device)
+    _lib.call("kai0_grad_accum", acc.data_ptr(), grad.data_ptr(), int(grad.dtype == F32), acc.numel(), int(bool(first)),
+              None if sumsq_out is None else sumsq_out.data_ptr(), None if scratch is None else scratch.data_ptr(), _stream())  # fmt: skip
+
+
 def sum_chunks_(src, chunks: int, out):
     """out[i] = sum_j src[j * out.numel() + i] in f32, one rounding (the local half of the all-pairs reduce-scatter)."""
     n = out.numel()

@@ -66,6 +66,28 @@ class Observation:
         )
 
 
+def slice_observation(obs, lo: int, hi: int):
+    """Samples [lo, hi) of a batched observation, as a shallow copy of whatever object `obs` is (`Observation`, any container of
+    attributes): every tensor attribute whose leading dimension is the batch (that of `state`) is sliced, and so is every dict of
+    such tensors (`images`, `image_masks`, ...); everything else (None, scalars, 0-d tensors) passes through.  The slices are views.
+    What the Trainer feeds the model per micro-batch (`micro_batch`), so `progress` and the other extra fields travel with it."""
+    import copy
+
+    batch = obs.state.shape[0]
+
+    def cut(v):
+        if isinstance(v, torch.Tensor):
+            return v[lo:hi] if v.dim() >= 1 and v.shape[0] == batch else v
+        if isinstance(v, dict):
+            return {k: cut(x) for k, x in v.items()}
+        return v
+
+    out = copy.copy(obs)
+    for name, v in vars(obs).items():
+        setattr(out, name, cut(v))
+    return out
+
+
 def resize_with_pad_torch(images: torch.Tensor, height: int, width: int, mode: str = "bilinear") -> torch.Tensor:
     """shared/image_tools.py:55-126: aspect-preserving resize, pad with black (-1 for f32, 0 for uint8)."""
     channels_last = images.shape[-1] <= 4

@@ -39,6 +39,12 @@ Parameter EMA (`ema_decay`, off by default; the JAX trainer's, scripts/train.py:
 and moments, ema += (1 - d) (master - ema) inside the AdamW pass (kai0_adamw_ema: 8 B per element more, no launch more), saved with
 the optimizer state; `ema_weights()` puts the averaged weights into the model for an evaluation / a checkpoint and takes them out again.
 
+Gradient accumulation (`end_micro_batch()`, off unless called): a step made of several backward passes.  After every pass but the
+last the gradient reduction is finished as in step() and every bucket's gradient shard is added into an f32 accumulator shard
+(kai0_grad_accum; 4 B x parameters / N, allocated on first use, dead between steps); step() adds the last pass — with the sum of
+squares of the result from the same launch — and clips / updates from the accumulator.  Every pass is reduce-scattered, only the
+1/N shard is accumulated: the full-size gradient buffers stay staging buffers (fsdp).
+
 The whole optimizer is 3 kernels per bucket on flat shards (sum of squares, clip coefficient kept on device, fused
 AdamW) — no per-tensor launches, no host sync.  The arithmetic is pluggable (`ShardOps`) only so the collective /
 partition logic can be exercised on CPU with gloo; the product default is the HIP kernels and raises without them.
@@ -73,6 +79,11 @@ class HipShardOps:
         from .optim import sum_chunks_
 
         sum_chunks_(src, chunks, out)
+
+    def grad_accum(self, acc, grad, *, first, sumsq_out=None):
+        from .optim import grad_accum_
+
+        grad_accum_(acc, grad, first=first, sumsq_out=sumsq_out)
 
     def adamw(self, master, m, v, grad, param, *, lr, beta1, beta2, eps, wd, step, clip_coef):
         from .optim import adamw_step_
@@ -333,6 +344,7 @@ class ShardedDataParallel:
         self._coef = torch.ones(1, dtype=F32, device=self.device)
         self._norm = torch.zeros(1, dtype=F32, device=self.device)
         self._in_backward = False
+        self._micro = 0  # micro-batches of the current step already added into the buckets' `acc` (end_micro_batch)
         # KAI0_SPARSE_EMBED=0: the embedding table's rows all go through the dense update (A/B; the result is bit-identical)
         self._sparse_rows = os.environ.get("KAI0_SPARSE_EMBED", "1") != "0"
         self._rs_inflight: list[_Bucket] = []  # fsdp: buckets whose reduce-scatter runs out of a staging buffer
@@ -468,6 +480,7 @@ class ShardedDataParallel:
         """Called at the start of every training step: state that an aborted backward (an exception, an evaluation with
         gradients but no step()) may have left behind does not leak into this step."""
         self._in_backward = False
+        self._micro = 0  # a half-finished accumulation is dropped: the next add overwrites the accumulators
         # a backward that did not reach step(): drop its collectives and its bucket bookkeeping, or this step would raise "a
         # parameter received two gradients", launch a reduce-scatter on stale counts, or retire a dead work handle (ADVICE r3)
         for b in self._rs_inflight:
@@ -678,13 +691,9 @@ class ShardedDataParallel:
         self.wait_params()
 
     # ------------------------------------------------------------------------------------------------- step
-    @torch.no_grad()
-    def step(self, lr: float):
-        """Finish the gradient reduction, clip by the global norm, update the local shards, start the parameter all-gathers
-        (zero2; waited for by the next forward, unit by unit).  Returns the global (pre-clip) gradient norm as a 1-element
-        device tensor."""
-        self._not_in_ema("step()")
-        self.step_count += 1
+    def _finish_reduction(self):
+        """End of a backward pass: every bucket's gradient shard complete on the current stream (late reduce-scatters of buckets
+        with parameters that got no gradient included)."""
         self._check_views()
         self._join_streams()  # gradients written by backward nodes on the second stream
         for b in self.buckets:
@@ -700,19 +709,9 @@ class ShardedDataParallel:
                 self._wait(b.rs_work, "reduce_scatter_wait")
                 b.rs_work = None
         self._rs_inflight.clear()
-        coef = None
-        if self.max_grad_norm is not None:
-            self._sumsq.zero_()
-            for b in self.buckets:
-                self.ops.sumsq(b.grad_shard, self._sumsq)
-            if self.world > 1:
-                self._wait(dist.all_reduce(self._sumsq, op=dist.ReduceOp.SUM, group=self.group, async_op=True), "norm_all_reduce")
-            self.ops.clip_coef(self._sumsq, self.max_grad_norm, self._coef, self._norm)
-            coef = self._coef
-        for b in self.buckets:  # forward-use order: the first layers' parameters are complete first
-            self._update_bucket(b, lr, coef)
-            if not b.fsdp:
-                b.ag_work = self._all_gather(b)  # not waited for here: pre_forward / wait_params do
+
+    def _end_backward(self):
+        """The buckets' bookkeeping is ready for the next backward pass (of the next step, or of the step's next micro-batch)."""
         # Every gradient producer overwrites its parameter's whole slice, so the 7 GB of flat gradients are NOT cleared per
         # step: a slice is zeroed only if its producer accumulates into it (the embedding scatter: `_kai0_grad_accumulates`)
         # or, lazily in the next step(), if it holds an old gradient and no new one arrived.
@@ -738,6 +737,68 @@ class ShardedDataParallel:
         if self.mode == "fsdp":
             self.release_params()
             self._issue_gather(0)  # the next forward starts with group 0
+
+    def _accumulate(self, sumsq_out=None):
+        """acc (+)= grad_shard for every bucket: `first` (overwrite, the accumulator is never read) on the step's first micro-batch;
+        `sumsq_out` (the step's last one, with clipping): the accumulated gradient's sum of squares from the same pass."""
+        first = self._micro == 0
+        fused = hasattr(self.ops, "grad_accum")
+        for b in self.buckets:
+            if not hasattr(b, "acc"):  # f32 [shard], on first use (an engine that never accumulates has no such attribute); dead
+                b.acc = torch.empty(b.shard, dtype=F32, device=self.device)  # between steps: not optimizer state, not checkpointed
+            if fused:
+                self.ops.grad_accum(b.acc, b.grad_shard, first=first, sumsq_out=sumsq_out)
+                continue
+            # an ops object without the kernel (the torch oracle of the CPU tests): the same single f32 add per element
+            if first:
+                b.acc.copy_(b.grad_shard)
+            else:
+                b.acc.add_(b.grad_shard.to(F32))
+            if sumsq_out is not None:
+                self.ops.sumsq(b.acc, sumsq_out)
+        self._micro += 1
+
+    @torch.no_grad()
+    def end_micro_batch(self):
+        """Gradient accumulation: called after the backward of every micro-batch of a step except the last (`step(lr)` follows that
+        one).  Finishes the gradient reduction as step() does (every micro-batch is reduce-scattered: only the 1/N shard is
+        accumulated, the full-size buffers stay staging buffers in fsdp mode), adds the shard into the f32 accumulator `acc` of
+        every bucket (kai0_grad_accum) and resets the backward bookkeeping.  No optimizer update, no parameter all-gather,
+        `step_count` unchanged; the loss of each of the k micro-batches carries 1/k."""
+        self._not_in_ema("end_micro_batch()")
+        self._finish_reduction()
+        self._accumulate()
+        self._end_backward()
+
+    @torch.no_grad()
+    def step(self, lr: float):
+        """Finish the gradient reduction, clip by the global norm, update the local shards, start the parameter all-gathers
+        (zero2; waited for by the next forward, unit by unit).  Returns the global (pre-clip) gradient norm as a 1-element
+        device tensor.  After `end_micro_batch()` calls the gradient is the accumulated one (this backward's added last)."""
+        self._not_in_ema("step()")
+        self.step_count += 1
+        self._finish_reduction()
+        accumulated = self._micro > 0
+        coef = None
+        if self.max_grad_norm is not None:
+            self._sumsq.zero_()
+            if accumulated:
+                self._accumulate(sumsq_out=self._sumsq)
+            else:
+                for b in self.buckets:
+                    self.ops.sumsq(b.grad_shard, self._sumsq)
+            if self.world > 1:
+                self._wait(dist.all_reduce(self._sumsq, op=dist.ReduceOp.SUM, group=self.group, async_op=True), "norm_all_reduce")
+            self.ops.clip_coef(self._sumsq, self.max_grad_norm, self._coef, self._norm)
+            coef = self._coef
+        elif accumulated:
+            self._accumulate()
+        for b in self.buckets:  # forward-use order: the first layers' parameters are complete first
+            self._update_bucket(b, lr, coef, b.acc if accumulated else b.grad_shard)
+            if not b.fsdp:
+                b.ag_work = self._all_gather(b)  # not waited for here: pre_forward / wait_params do
+        self._micro = 0
+        self._end_backward()
         return self._norm
 
     # ---- optimizer update of one bucket's shard ---------------------------------------------------------------
@@ -774,7 +835,8 @@ class ShardedDataParallel:
         b._sparse_key, b._sparse_segs = key, segs
         return segs
 
-    def _update_bucket(self, b: _Bucket, lr: float, coef):
+    def _update_bucket(self, b: _Bucket, lr: float, coef, grad):
+        """`grad`: the bucket's gradient shard, or its f32 accumulator after micro-batches."""
         kw = dict(lr=lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, wd=self.wd, step=self.step_count, clip_coef=coef)
         segs = []
         ema_on = self.ema_decay is not None
@@ -783,10 +845,10 @@ class ShardedDataParallel:
         def dense(lo, hi):
             args = (b.exp_avg[lo:hi], b.exp_avg_sq[lo:hi])
             if fused:
-                self.ops.adamw_ema(b.master[lo:hi], *args, b.ema[lo:hi], b.grad_shard[lo:hi], b.param_shard[lo:hi],
+                self.ops.adamw_ema(b.master[lo:hi], *args, b.ema[lo:hi], grad[lo:hi], b.param_shard[lo:hi],
                                    ema_decay=self.ema_decay, **kw)  # fmt: skip
                 return
-            self.ops.adamw(b.master[lo:hi], *args, b.grad_shard[lo:hi], b.param_shard[lo:hi], **kw)
+            self.ops.adamw(b.master[lo:hi], *args, grad[lo:hi], b.param_shard[lo:hi], **kw)
             if ema_on:  # an ops object without the fused form (the torch oracle of the CPU tests): the same update as a second pass
                 b.ema[lo:hi].lerp_(b.master[lo:hi], ema_lerp_weight(self.ema_decay))
 
@@ -808,9 +870,9 @@ class ShardedDataParallel:
             end = first + rows * rl
             if ema_on:
                 self.ops.adamw_rows_ema(b.master[first:end], b.exp_avg[first:end], b.exp_avg_sq[first:end], b.ema[first:end],
-                                        b.grad_shard[first:end], b.param_shard[first:end], rl, active, ema_decay=self.ema_decay, **kw)  # fmt: skip
+                                        grad[first:end], b.param_shard[first:end], rl, active, ema_decay=self.ema_decay, **kw)  # fmt: skip
             else:
-                self.ops.adamw_rows(b.master[first:end], b.exp_avg[first:end], b.exp_avg_sq[first:end], b.grad_shard[first:end],
+                self.ops.adamw_rows(b.master[first:end], b.exp_avg[first:end], b.exp_avg_sq[first:end], grad[first:end],
                                     b.param_shard[first:end], rl, active, **kw)  # fmt: skip
             cur = end
         if cur < b.shard:

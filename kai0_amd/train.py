@@ -38,12 +38,20 @@ class Trainer:
     def __init__(self, model, *, world_size: int = 1, rank: int = 0, group=None, peak_lr=2.5e-5, warmup_steps=1000,
                  decay_steps=30000, end_lr=2.5e-6, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-10, clip_norm=1.0,
                  shard_ops=None, bucket_bytes: int | None = None, mode: str | None = None, prefetch: int | None = None,
-                 ema_decay: float | None = None):  # fmt: skip
+                 ema_decay: float | None = None, micro_batch: int | None = None):  # fmt: skip
         """`bucket_bytes` / `prefetch` default per mode: zero2 512 MB buckets (few, large collectives; nothing waits on them
         inside forward / backward); fsdp 256 MB (~ one joint Gemma-2B + expert layer, SURVEY.md §8e's unit) gathered two
         buckets ahead, so that a bucket's gather has two layers of compute to hide behind and ~0.75 GB of full parameters
         are live at a time.  `ema_decay`: None = no parameter EMA (default); else the engine keeps an f32 EMA of the master weights,
-        updated inside the AdamW pass (sharded.ShardedDataParallel)."""
+        updated inside the AdamW pass (sharded.ShardedDataParallel).  `micro_batch`: None = env KAI0_MICRO_BATCH (unset / 0 = off);
+        m = `train_step` runs the rank's batch of B samples as B // m forward / backward passes of m samples whose gradients the
+        engine accumulates in f32 (`end_micro_batch`), then ONE optimizer step: the trajectory of the batch size the recipe was
+        written for, at the activation memory of m samples."""
+        if micro_batch is None:
+            micro_batch = int(os.environ.get("KAI0_MICRO_BATCH", "0") or 0)
+        if micro_batch < 0:
+            raise ValueError(f"micro_batch must be a positive number of samples (or None / 0 = off), got {micro_batch!r}")
+        self.micro_batch = int(micro_batch) or None
         self.model = model
         self.world, self.rank = world_size, rank
         self.sched = dict(warmup_steps=warmup_steps, peak_lr=peak_lr, decay_steps=decay_steps, end_lr=end_lr)
@@ -78,6 +86,11 @@ class Trainer:
         lr = self.lr()
         if getattr(self.model, "_engine", None) is not None:
             self.model.invalidate_inference_engine()  # the step below rewrites the weights through raw pointers
+        B, m = actions.shape[0], self.micro_batch
+        if m is not None and m < B:
+            if B % m:
+                raise ValueError(f"micro_batch={m} does not divide the rank's batch of {B} samples")
+            return self._train_step_split(observation, actions, noise, time, lr, B // m, m)
         self.engine.begin_step()
         if not self._hooked:
             self.engine.wait_params()
@@ -88,6 +101,35 @@ class Trainer:
         self.last_grad_norm = self.engine.step(lr)
         self.global_step += 1
         return loss.detach()
+
+    def _train_step_split(self, observation, actions, noise, time, lr, k: int, m: int) -> torch.Tensor:
+        """The step as k forward / backward passes over consecutive slices of m samples: each loss carries 1 / (k * world) (the mean
+        over the global batch), the engine adds the k reduce-scattered gradients in f32, one update.  One schedule tick, one
+        global_step, one EMA update; returns the mean of the k losses."""
+        from .preprocessing import slice_observation
+
+        # drawn once for the whole batch, noise then time, as the unsplit forward draws them: the same random stream either way
+        if noise is None and hasattr(self.model, "sample_noise"):
+            noise = self.model.sample_noise(actions.shape, actions.device)
+        if time is None and hasattr(self.model, "sample_time"):
+            time = self.model.sample_time(actions.shape[0], actions.device)
+        self.engine.begin_step()
+        scale = 1.0 / (k * self.world)
+        total = None
+        for i in range(k):
+            lo, hi = i * m, (i + 1) * m
+            if not self._hooked:
+                self.engine.wait_params()
+            losses = self.model(slice_observation(observation, lo, hi), actions[lo:hi], noise=None if noise is None else noise[lo:hi],
+                                time=None if time is None else time[lo:hi])  # fmt: skip
+            loss = losses.mean()
+            (loss * scale).backward()
+            total = loss.detach() if total is None else total + loss.detach()
+            if i < k - 1:
+                self.engine.end_micro_batch()
+        self.last_grad_norm = self.engine.step(lr)
+        self.global_step += 1
+        return total / k
 
     def sync_weights(self):
         """Adopt weights written into the model in place after construction (see the module docstring)."""
@@ -318,13 +360,20 @@ def train_loop(config, *, device=None, shard_ops=None, model=None, log=None):
     ema_decay = config.ema_decay if os.environ.get("KAI0_EMA", "0") == "1" else None
     trainer = Trainer(model, world_size=world, rank=rank, peak_lr=sch.peak_lr, warmup_steps=sch.warmup_steps,
                       decay_steps=sch.decay_steps, end_lr=sch.decay_lr, betas=(opt.b1, opt.b2), eps=opt.eps,
-                      weight_decay=opt.weight_decay, clip_norm=opt.clip_gradient_norm, shard_ops=shard_ops, ema_decay=ema_decay)  # fmt: skip
+                      weight_decay=opt.weight_decay, clip_norm=opt.clip_gradient_norm, shard_ops=shard_ops, ema_decay=ema_decay,
+                      micro_batch=int(os.environ.get("KAI0_MICRO_BATCH", "0") or 0) or None)  # fmt: skip
     if resuming:
         step = trainer.load_checkpoint(str(ckpt_dir))
         exact = _restore_rng_state(getattr(trainer, "resumed_rng_state", None), world, rank, device)
         loader.skip_batches(step)  # every step consumed one batch of the seeded stream
         say(f"Resumed training from step {step}" + ("" if exact else " (no RNG state for this world size: noise / augmentation restart from the seed)"))
-    say(f"world_size={world} batch_size={config.batch_size} (per GPU {config.batch_size // world}) num_train_steps={config.num_train_steps} "
+    per_gpu, mb = config.batch_size // world, trainer.micro_batch
+    accum = ""
+    if mb is not None and mb < per_gpu:
+        if per_gpu % mb:
+            raise ValueError(f"KAI0_MICRO_BATCH={mb} does not divide the per-GPU batch of {per_gpu} samples")
+        accum = f" micro_batch={mb} (KAI0_MICRO_BATCH: {per_gpu // mb} forward/backward passes per optimizer step)"
+    say(f"world_size={world} batch_size={config.batch_size} (per GPU {per_gpu}){accum} num_train_steps={config.num_train_steps} "
         f"mode={trainer.engine.mode} lr: warmup={sch.warmup_steps} peak={sch.peak_lr:.2e} decay_steps={sch.decay_steps} end={sch.decay_lr:.2e}")  # fmt: skip
 
     if ema_decay is not None:
