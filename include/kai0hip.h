@@ -618,6 +618,24 @@ int kai0_adamw_rows_ema(float* master, float* m, float* v, float* ema, const voi
  * vector alignment at the same element, scalar head / tail / fallback otherwise. */
 int kai0_grad_accum(float* acc, const void* grad, int grad_f32, int64_t n, int first,
                     float* sumsq_out, float* scratch, kai0_stream_t stream);
+/* Model arithmetic (model_arithmetic/common.py:11-19; arithmetic_torch.py:188-195,206-214): merge fine-tuned checkpoints that are
+ * RESIDENT in device memory, and project a gradient onto them, without the host.
+ * kai0_mix: dst[j] = w0 x0[j] + w1 x1[j] + ... in source order — acc = w0 * x0; acc = acc + w1 * x1; ... with every product and
+ * every sum rounded to f32 on its own (no fused multiply-add) and ONE rounding to dst's dtype, so the result can be restated bit
+ * for bit.  srcs / weights: HOST arrays of n_src (1..8) device pointers / finite floats, read at call time; every source is bf16 or
+ * f32 (src_f32), dst bf16 or f32 (dst_f32).  dst may be one of the sources; it is overwritten and never read (NaN does not leak).
+ * Buffers may start at any element: 16-byte accesses where dst and all sources reach a 16-byte boundary at the same element,
+ * scalar head / tail / fallback otherwise.  No allocation, no host synchronisation, no atomics. */
+int kai0_mix(const void* const* srcs, int src_f32, const float* weights, int n_src, void* dst, int dst_f32, int64_t n,
+             kai0_stream_t stream);
+/* kai0_multi_dot: out[k] += sum_j g[j] * srcs[k][j] for every k < n_src (1..8) from ONE pass over g (the caller zeroes out, as for
+ * kai0_sumsq).  g and the sources bf16 or f32 (g_f32 / src_f32); srcs: HOST array of device pointers.  Products and the per-lane /
+ * per-block sums are f32: 256 lanes x 4 elements per block trip, at most 4096 blocks, a lane adds its products in element order;
+ * one partial per block and source in scratch (n_src x 4096 floats: scratch[k * 4096 + block]), which a second launch adds in a
+ * fixed order in f64 into out (f64 so that the sum over a model's per-tensor calls loses nothing).  No atomics: reproducible bit
+ * for bit.  Alignment as kai0_grad_accum: 4-element accesses where g and all sources reach their boundary at the same element. */
+int kai0_multi_dot(const void* g, int g_f32, const void* const* srcs, int src_f32, int n_src, int64_t n, double* out,
+                   float* scratch, kai0_stream_t stream);
 /* coef[0] = min(1, max_norm / (sqrt(sumsq[0]) + 1e-6)) ; norm_out[0] = sqrt(sumsq[0])
  * (torch.nn.utils.clip_grad_norm_) */
 int kai0_clip_coef(const float* sumsq, float max_norm, float* coef, float* norm_out, kai0_stream_t stream);

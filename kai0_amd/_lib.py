@@ -192,6 +192,8 @@ _PROTOS: dict[str, list] = {
     "kai0_adamw_ema": [c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p],
     "kai0_adamw_rows_ema": [c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i64, c_i, c_p, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p],
     "kai0_grad_accum": [c_p, c_p, c_i, c_i64, c_i, c_p, c_p, c_p],
+    "kai0_mix": [C.POINTER(c_p), c_i, C.POINTER(c_f), c_i, c_p, c_i, c_i64, c_p],
+    "kai0_multi_dot": [c_p, c_i, C.POINTER(c_p), c_i, c_i, c_i64, c_p, c_p, c_p],
 }  # fmt: skip
 
 EXPORTED_SYMBOLS = ("kai0_last_error", "kai0_skinny_workspace_bytes", "kai0_attn_decode_workspace_bytes", "kai0_gemm_f32_workspace_bytes",

@@ -18,12 +18,14 @@ def _tied_groups(model: torch.nn.Module):
     return [sorted(names) for names in by_id.values()]
 
 
-def save_model_safetensors(model: torch.nn.Module, path: str) -> None:
+def save_model_safetensors(model: torch.nn.Module, path: str, dtype: torch.dtype | None = None) -> None:
+    """`dtype` (None: untouched) converts every floating-point tensor on the way out, e.g. float32 for model_arithmetic's files."""
     sd = model.state_dict()
     out, meta = {}, {"format": "pt"}
     for names in _tied_groups(model):
         keep = names[0]
-        out[keep] = sd[keep].detach().clone().contiguous()
+        t = sd[keep].detach()
+        out[keep] = (t.to(dtype) if dtype is not None and t.is_floating_point() else t).clone().contiguous()
         for alias in names[1:]:
             meta[alias] = keep  # same convention as safetensors.torch.save_model
     save_file(out, path, metadata=meta)

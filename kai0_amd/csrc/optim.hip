@@ -341,6 +341,155 @@ __global__ __launch_bounds__(256) void grad_accum_kernel(float* __restrict__ acc
     }
 }
 
+// ---- model arithmetic: mix resident checkpoints, project a gradient onto them (kai0_mix / kai0_multi_dot) ----------------------------
+// The per-source pointers and weights travel by value and are read into locals once (rules learned): N is a
+// template parameter, every loop over the sources is unrolled and the locals stay in registers.
+struct MixK {
+    const void* src[8];
+    float w[8];
+};
+
+template <bool F32>
+__device__ __forceinline__ float load_one(const void* p, int64_t i) {
+    return F32 ? reinterpret_cast<const float*>(p)[i] : bf2f(reinterpret_cast<const bf16_t*>(p)[i]);
+}
+
+// V elements at i, V = 4 or 8: 16-byte accesses (two of them for 8 f32 elements), 8-byte for 4 bf16 elements; the caller guarantees
+// the alignment
+template <bool F32, int V>
+__device__ __forceinline__ void load_vec(const void* p, int64_t i, float (&x)[V]) {
+    if constexpr (F32) {
+#pragma unroll
+        for (int q = 0; q < V / 4; ++q) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p) + i + 4 * q);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[4 * q + e] = v[e];
+        }
+    } else if constexpr (V == 8) {
+        const bf16x8 v = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16_t*>(p) + i);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = bf2f(v[e]);
+    } else {
+        const bf16x4 v = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16_t*>(p) + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = bf2f(v[e]);
+    }
+}
+
+// dst = w0 x0 + w1 x1 + ... in source order, every product and every sum rounded to f32 on its own (-ffp-contract=off), one rounding
+// to dst's dtype (model_arithmetic/common.py:11-19, arithmetic_torch.py:188-195: the reference's per-tensor sum of w_i * p_i).
+// Every lane reads all its sources' elements before it writes the same elements of dst, so dst may be one of the sources (no
+// __restrict__ here); dst is never read.  Layout: adamw_ema_kernel's — scalar head, one contiguous run of V-element vectors per
+// block (V = 4 when everything is f32, else 8), scalar tail.
+template <bool SF32, bool DF32, int N>
+__global__ __launch_bounds__(256) void mix_kernel(MixK a, void* dst, int64_t n, int64_t head) {
+    constexpr int V = (SF32 && DF32) ? 4 : 8;
+    const void* src[N];
+    float w[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        src[k] = a.src[k];
+        w[k] = a.w[k];
+    }
+    const int64_t nv = (n - head) / V;
+    const int64_t per = (nv + gridDim.x - 1) / gridDim.x, lo = per * blockIdx.x, hi = lo + per < nv ? lo + per : nv;
+    for (int64_t j = lo + threadIdx.x; j < hi; j += 256) {
+        const int64_t i = head + V * j;
+        float x[N][V], acc[V];
+#pragma unroll
+        for (int k = 0; k < N; ++k) load_vec<SF32, V>(src[k], i, x[k]);
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc[e] = w[0] * x[0][e];
+#pragma unroll
+        for (int k = 1; k < N; ++k)
+#pragma unroll
+            for (int e = 0; e < V; ++e) acc[e] = acc[e] + w[k] * x[k][e];
+        if constexpr (DF32) {
+#pragma unroll
+            for (int q = 0; q < V / 4; ++q)
+                *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(dst) + i + 4 * q) =
+                    f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
+        } else {
+            bf16x8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = f2bf(acc[e]);
+            *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16_t*>(dst) + i) = o;
+        }
+    }
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    const int64_t tail = head + V * nv;
+    for (int64_t i = tid; i < head + (n - tail); i += stride) {
+        const int64_t e = i < head ? i : tail + (i - head);
+        float x[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) x[k] = load_one<SF32>(src[k], e);
+        float acc = w[0] * x[0];
+#pragma unroll
+        for (int k = 1; k < N; ++k) acc = acc + w[k] * x[k];
+        if constexpr (DF32) reinterpret_cast<float*>(dst)[e] = acc;
+        else reinterpret_cast<bf16_t*>(dst)[e] = f2bf(acc);
+    }
+}
+
+// partial[k * 4096 + block] = the block's sum of g[j] * src_k[j] for every source k, from ONE pass over g
+// (arithmetic_torch.py:206-214: the reference's (param.grad * p_i).sum() per checkpoint).  Products and sums f32; a lane adds its
+// products in element order, the block adds its lanes through block_sum.  Layout: grad_accum_kernel's with its sum of squares —
+// scalar head, one contiguous run of 4-element vectors per block (at most 4096 blocks, one partial each and source), scalar tail.
+template <bool GF32, bool SF32, int N>
+__global__ __launch_bounds__(256) void multi_dot_kernel(const void* __restrict__ g, MixK a, int64_t n, int64_t head,
+                                                        float* __restrict__ partial) {
+    __shared__ float red[4];
+    const void* src[N];
+    float acc[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        src[k] = a.src[k];
+        acc[k] = 0.f;
+    }
+    const int64_t n4 = (n - head) >> 2;
+    const int64_t per = (n4 + gridDim.x - 1) / gridDim.x, lo = per * blockIdx.x, hi = lo + per < n4 ? lo + per : n4;
+    for (int64_t j = lo + threadIdx.x; j < hi; j += 256) {
+        const int64_t i = head + 4 * j;
+        float gv[4], x[N][4];
+        load_vec<GF32, 4>(g, i, gv);
+#pragma unroll
+        for (int k = 0; k < N; ++k) load_vec<SF32, 4>(src[k], i, x[k]);
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[k] = acc[k] + gv[e] * x[k][e];
+    }
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    const int64_t tail = head + 4 * n4;
+    for (int64_t i = tid; i < head + (n - tail); i += stride) {
+        const int64_t e = i < head ? i : tail + (i - head);
+        const float gs = load_one<GF32>(g, e);
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[k] = acc[k] + gs * load_one<SF32>(src[k], e);
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const float s = block_sum<4>(acc[k], red);
+        if (threadIdx.x == 0) partial[k * 4096 + blockIdx.x] = s;
+    }
+}
+
+// out[k] += the sum of source k's `blocks` partials in f64, always in the same order (block k of the grid takes source k): a lane
+// adds every 256th partial, then a fixed tree over the 256 lanes
+__global__ __launch_bounds__(256) void multi_dot_finish_kernel(const float* __restrict__ partial, int blocks, double* __restrict__ out) {
+    __shared__ double red[256];
+    const float* p = partial + (int64_t)blockIdx.x * 4096;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < blocks; i += 256) acc += (double)p[i];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] += red[0];
+}
+
 inline int opt_grid(int64_t n) {
     int64_t b = (n + 255) / 256;
     if (b > 4096) b = 4096;
@@ -525,3 +674,103 @@ KAI0_API int kai0_adamw_rows_ema(float* master, float* m, float* v, float* ema, 
 #undef LAUNCH
     return kai0_check_launch("kai0_adamw_rows_ema");
 }
+
+namespace {
+inline bool aligned16(const void* p, int64_t head, int esz) { return (((uintptr_t)p + (uintptr_t)(head * esz)) & 15) == 0; }
+}  // namespace
+
+// N = n_src as a template parameter (1..8, checked by the callers)
+#define KAI0_FOR_NSRC(n_src, LAUNCH_N) \
+    switch (n_src) {                   \
+        case 1: LAUNCH_N(1); break;    \
+        case 2: LAUNCH_N(2); break;    \
+        case 3: LAUNCH_N(3); break;    \
+        case 4: LAUNCH_N(4); break;    \
+        case 5: LAUNCH_N(5); break;    \
+        case 6: LAUNCH_N(6); break;    \
+        case 7: LAUNCH_N(7); break;    \
+        default: LAUNCH_N(8); break;   \
+    }
+
+KAI0_API int kai0_mix(const void* const* srcs, int src_f32, const float* weights, int n_src, void* dst, int dst_f32, int64_t n,
+                      kai0_stream_t stream) {
+    if (n <= 0) return 0;
+    KAI0_REQUIRE(n_src >= 1 && n_src <= 8, "kai0_mix: n_src = %d outside 1..8", n_src);
+    KAI0_REQUIRE(srcs && weights && dst, "kai0_mix: null buffer");
+    const int ssz = src_f32 ? 4 : 2, dsz = dst_f32 ? 4 : 2;
+    KAI0_REQUIRE(((uintptr_t)dst % dsz) == 0, "kai0_mix: a buffer is not aligned to its element size");
+    MixK k{};
+    for (int i = 0; i < n_src; ++i) {
+        KAI0_REQUIRE(srcs[i] != nullptr, "kai0_mix: null buffer (source %d)", i);
+        KAI0_REQUIRE(((uintptr_t)srcs[i] % ssz) == 0, "kai0_mix: a buffer is not aligned to its element size (source %d)", i);
+        KAI0_REQUIRE(__builtin_isfinite(weights[i]), "kai0_mix: weight %d is not finite", i);
+        k.src[i] = srcs[i];
+        k.w[i] = weights[i];
+    }
+    // elements before dst's first 16-byte boundary; every source must reach a 16-byte boundary at the same element
+    const int V = (src_f32 && dst_f32) ? 4 : 8;
+    int64_t head = (int64_t)(((16 - ((uintptr_t)dst & 15)) & 15) / dsz);
+    if (head > n) head = n;
+    for (int i = 0; i < n_src; ++i)
+        if (!aligned16(srcs[i], head, ssz)) head = n;  // no common head: scalar accesses throughout
+    const int64_t nv = (n - head) / V, rest = n - V * nv;
+    int64_t blocks = (nv + 255) / 256;  // one vector per lane (see adamw_ema_kernel)
+    if (blocks > ((int64_t)1 << 22)) blocks = (int64_t)1 << 22;
+    if (blocks < opt_grid(rest)) blocks = opt_grid(rest);  // the scalar elements are grid-strided: all of them if there is no common head
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((unsigned)blocks), block(256);
+#define LAUNCH_SD(S, D, N) hipLaunchKernelGGL((mix_kernel<S, D, N>), grid, block, 0, s, k, dst, n, head)
+#define LAUNCH_N(N)                                        \
+    do {                                                   \
+        if (src_f32 && dst_f32) LAUNCH_SD(true, true, N);  \
+        else if (src_f32) LAUNCH_SD(true, false, N);       \
+        else if (dst_f32) LAUNCH_SD(false, true, N);       \
+        else LAUNCH_SD(false, false, N);                   \
+    } while (0)
+    KAI0_FOR_NSRC(n_src, LAUNCH_N)
+#undef LAUNCH_N
+#undef LAUNCH_SD
+    return kai0_check_launch("kai0_mix");
+}
+
+KAI0_API int kai0_multi_dot(const void* g, int g_f32, const void* const* srcs, int src_f32, int n_src, int64_t n, double* out,
+                            float* scratch, kai0_stream_t stream) {
+    if (n <= 0) return 0;
+    KAI0_REQUIRE(n_src >= 1 && n_src <= 8, "kai0_multi_dot: n_src = %d outside 1..8", n_src);
+    KAI0_REQUIRE(g && srcs && out, "kai0_multi_dot: null buffer");
+    KAI0_REQUIRE(scratch != nullptr, "kai0_multi_dot: needs a scratch buffer of n_src * 4096 floats");
+    const int gsz = g_f32 ? 4 : 2, ssz = src_f32 ? 4 : 2;
+    KAI0_REQUIRE(((uintptr_t)g % gsz) == 0 && ((uintptr_t)out % 8) == 0 && ((uintptr_t)scratch % 4) == 0,
+                 "kai0_multi_dot: a buffer is not aligned to its element size");
+    MixK k{};
+    for (int i = 0; i < n_src; ++i) {
+        KAI0_REQUIRE(srcs[i] != nullptr, "kai0_multi_dot: null buffer (source %d)", i);
+        KAI0_REQUIRE(((uintptr_t)srcs[i] % ssz) == 0, "kai0_multi_dot: a buffer is not aligned to its element size (source %d)", i);
+        k.src[i] = srcs[i];
+    }
+    // elements before g's first 4-element boundary; every source must reach its own at the same element
+    int64_t head = (int64_t)(((4 * gsz - ((uintptr_t)g % (4 * gsz))) % (4 * gsz)) / gsz);
+    if (head > n) head = n;
+    for (int i = 0; i < n_src; ++i)
+        if (!aligned4(srcs[i], head, ssz)) head = n;  // no common head: scalar accesses throughout
+    const int64_t n4 = (n - head) >> 2, rest = n - 4 * n4;
+    int64_t blocks = (n4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;  // one partial per block and source in the scratch buffer
+    if (blocks < opt_grid(rest)) blocks = opt_grid(rest);
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((unsigned)blocks), block(256);
+#define LAUNCH_GS(G, S, N) hipLaunchKernelGGL((multi_dot_kernel<G, S, N>), grid, block, 0, s, g, k, n, head, scratch)
+#define LAUNCH_N(N)                                      \
+    do {                                                 \
+        if (g_f32 && src_f32) LAUNCH_GS(true, true, N);  \
+        else if (g_f32) LAUNCH_GS(true, false, N);       \
+        else if (src_f32) LAUNCH_GS(false, true, N);     \
+        else LAUNCH_GS(false, false, N);                 \
+    } while (0)
+    KAI0_FOR_NSRC(n_src, LAUNCH_N)
+#undef LAUNCH_N
+#undef LAUNCH_GS
+    hipLaunchKernelGGL(multi_dot_finish_kernel, dim3(n_src), dim3(256), 0, s, (const float*)scratch, (int)blocks, out);
+    return kai0_check_launch("kai0_multi_dot");
+}
+#undef KAI0_FOR_NSRC

@@ -124,6 +124,45 @@ def grad_accum_(acc, grad, *, first: bool, sumsq_out=None):
               None if sumsq_out is None else sumsq_out.data_ptr(), None if scratch is None else scratch.data_ptr(), _stream())  # fmt: skip
 
 
+MAX_MIX_SOURCES = 8  # what one kai0_mix / kai0_multi_dot launch takes
+
+
+def _src_pointers(srcs, like_numel: int):
+    import ctypes as C
+
+    assert 1 <= len(srcs) and all(s.dtype == srcs[0].dtype and s.numel() == like_numel and s.is_contiguous() for s in srcs)
+    assert srcs[0].dtype in (F32, BF16)
+    return (C.c_void_p * len(srcs))(*(s.data_ptr() for s in srcs))
+
+
+def mix_(dst, srcs, weights):
+    """kai0_mix: dst = w0 * srcs[0] + w1 * srcs[1] + ... in source order, every product and sum rounded to f32 on its own, one rounding
+    to dst's dtype.  1..8 sources of one dtype (bf16 or f32) and dst's length; dst (bf16 or f32) may be one of them and is never read."""
+    import ctypes as C
+
+    WEIGHT_UPDATES[0] += 1  # dst is usually a model parameter: the write bypasses autograd's version counter
+    assert dst.dtype in (F32, BF16) and dst.is_contiguous() and len(weights) == len(srcs)
+    ptrs = _src_pointers(srcs, dst.numel())
+    w = (C.c_float * len(srcs))(*(float(x) for x in weights))
+    _lib.call("kai0_mix", ptrs, int(srcs[0].dtype == F32), w, len(srcs), dst.data_ptr(), int(dst.dtype == F32), dst.numel(), _stream())
+
+
+_MULTI_DOT_SCRATCH: dict = {}
+
+
+def multi_dot_(grad, srcs, out):
+    """kai0_multi_dot: out[k] += sum(grad * srcs[k]) for the 1..8 sources from one pass over grad; out f64 [len(srcs)] (the caller zeroes
+    it), products and block partials f32, partials added in f64 in a fixed order: reproducible bit for bit."""
+    assert grad.dtype in (F32, BF16) and grad.is_contiguous() and out.dtype == torch.float64 and out.numel() >= len(srcs) and out.is_contiguous()
+    ptrs = _src_pointers(srcs, grad.numel())
+    key = (grad.device.index, _stream())
+    scratch = _MULTI_DOT_SCRATCH.get(key)
+    if scratch is None:
+        scratch = _MULTI_DOT_SCRATCH[key] = torch.empty(MAX_MIX_SOURCES * 4096, dtype=F32, device=grad.device)
+    _lib.call("kai0_multi_dot", grad.data_ptr(), int(grad.dtype == F32), ptrs, int(srcs[0].dtype == F32), len(srcs), grad.numel(),
+              out.data_ptr(), scratch.data_ptr(), _stream())  # fmt: skip
+
+
 def sum_chunks_(src, chunks: int, out):
     """out[i] = sum_j src[j * out.numel() + i] in f32, one rounding (the local half of the all-pairs reduce-scatter)."""
     n = out.numel()
