@@ -314,6 +314,14 @@ int kai0_rope_table(const int32_t* pos, const float* inv_freq, void* cos_out, vo
  * torch restatement (kai0_amd.model.build_mask_codes).  ncam <= 8. */
 int kai0_prefix_codes(const void* const* img_masks, int ncam, const void* lang_mask, int B, int n_img, int T, int Hs, int32_t* qcode,
                       int32_t* kcode, int32_t* pos, kai0_stream_t stream);
+/* The same for a pi0 request (pi05=False, pi0_pytorch.py:243-261,307): n_state continuous state tokens stand between the prompt and the
+ * action tokens,   [cam 0 | ... | cam ncam-1 | T prompt tokens | n_state state tokens | Hs action tokens],   S = ncam n_img + T + n_state + Hs.
+ * pad is true for state and action tokens; att = 0 over the prefix, 1 for every state token and [1, 0, 0, ...] over the actions, so
+ * cumsum(att) = 0 (prefix) / s + 1 (state token s) / n_state + 1 (actions): the prefix sees the prefix, a state token the prefix and the
+ * state tokens up to itself, the actions everything.  Same outputs and bit-exactness as kai0_prefix_codes, which it equals at
+ * n_state = 0.  n_state <= 16. */
+int kai0_prefix_state_codes(const void* const* img_masks, int ncam, const void* lang_mask, int B, int n_img, int T, int n_state, int Hs,
+                            int32_t* qcode, int32_t* kcode, int32_t* pos, kai0_stream_t stream);
 
 /* f32 MFMA GEMM, fully strided: C[m,n] = sum_k A[m*sam + k*sak] * B[k*sbk + n*sbn] (+ bias[n]) (+ C).
  * split_k > 1 slices the contraction over grid.z into raw partial tiles workspace[split_k][M][N] (f32; size from
@@ -567,6 +575,29 @@ int kai0_euler_step(float* x, const float* v, float dt, int64_t n, kai0_stream_t
 int kai0_denoise_glue(const void* xs, const float* mod, int64_t mod_ld, int rows_per_batch, float eps, const float* w_out,
                       const float* b_out, float* x_t, float dt, const float* w_in, const float* b_in, void* xs_next,
                       int64_t rows, int D, int A, float* rowsq_next, kai0_stream_t stream);
+/* The same seam for suffix buffers that hold more than the action rows (pi0, pi05=False: every sample's suffix is its state token + Hs
+ * action tokens, pi0_pytorch.py:243-261, and the step's output is `suffix_out[:, -action_horizon:]`, :459): action row r of x_t is row
+ *   (r / map_rpb) * map_bs + r % map_rpb + map_off
+ * of xs, xs_next and rowsq_next (pi0: map_rpb = Hs, map_bs = Hs + 1, map_off = 1; the request's state row, written once: rows = B,
+ * map_rpb = 1, map_bs = Hs + 1, map_off = 0 with w_in = state_proj).  The plain GemmaRMSNorm of pi0's expert (modeling_gemma.py:77-81,
+ * x_hat (1 + w)) is the adaRMS arithmetic with the constant modulation row [scale = w | shift = 0]: (x_hat (1 + w)) + 0.0 rounds nowhere
+ * (compare :80 with :102), so a closing call passes that row with rows_per_batch >= rows. */
+int kai0_denoise_glue_rows(const void* xs, const float* mod, int64_t mod_ld, int rows_per_batch, float eps, const float* w_out,
+                           const float* b_out, float* x_t, float dt, const float* w_in, const float* b_in, void* xs_next, int64_t rows,
+                           int D, int A, float* rowsq_next, int map_rpb, int64_t map_bs, int64_t map_off, kai0_stream_t stream);
+/* out = act(x W^T + bias) in exact f32 (v_mfma_f32_16x16x4_f32; the contraction split over four waves, added in wave order) for a few
+ * rows: 1 <= M <= 128, x f32 [M][ldx], W f32 [N][ldw] (a column slice of a wider weight is ldw > K), bias f32 [N] or NULL, act 0
+ * none / 1 SiLU; N % 16 == 0, K % 64 == 0.  The Linears of pi0's suffix embedding inside the Euler loop (pi0_pytorch.py:270-285):
+ *   h = silu(action_time_mlp_in.weight[:, :De] a + tvec[step])   -> out_f32 [M][ldo_f32]   (tvec: the weight's time half applied to
+ *                                                                   the step's time embedding + bias, hoisted out of the loop)
+ *   y = action_time_mlp_out(h)                                   -> out_bf16
+ * out_bf16 (either output may be NULL) takes ONE bf16 rounding of the f32 result at row (r / out_rpb) * out_bs + r % out_rpb + out_off
+ * (out_rpb = 0: row r) of a bf16 [..][ldo_bf16] buffer — rows 1 .. Hs of every sample's Hs + 1 suffix rows — and, with rowsq_out,
+ * the sums of squares of the stored bf16 values per 16-column tile, rowsq_out[N / 16][rowsq_ld] indexed by the mapped row: the
+ * statistic the first layer's folded projection consumes (kai0_skinny_desc.rowsq_in with rowsq_parts = N / 16). */
+int kai0_linear_f32_rows(const float* x, int64_t ldx, const float* W, int64_t ldw, const float* bias, int M, int N, int K, int act,
+                         float* out_f32, int64_t ldo_f32, void* out_bf16, int64_t ldo_bf16, int out_rpb, int64_t out_bs, int64_t out_off,
+                         float* rowsq_out, int64_t rowsq_ld, kai0_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimizer (train_pytorch.py:469-475,557-561; optimizer.py:15-85).

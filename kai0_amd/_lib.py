@@ -139,6 +139,7 @@ _PROTOS: dict[str, list] = {
     "kai0_transpose_strided_bf16": [c_p, c_p, c_i, c_i, c_i64, c_i64, c_i, c_i64, c_i64, c_p],
     "kai0_rope_table": [c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_p],
     "kai0_prefix_codes": [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
+    "kai0_prefix_state_codes": [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
     "kai0_gemm_f32": [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_i64, c_p],
     "kai0_linear_rows_f32": [c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_p],
     "kai0_rmsnorm_fwd": [c_p, c_p, c_p, c_p, c_i64, c_i, c_f, c_p],
@@ -184,6 +185,8 @@ _PROTOS: dict[str, list] = {
     "kai0_mse_bwd": [c_p, c_p, c_p, c_p, c_i64, c_p],
     "kai0_euler_step": [c_p, c_p, c_f, c_i64, c_p],
     "kai0_denoise_glue": [c_p, c_p, c_i64, c_i, c_f, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_i64, c_i, c_i, c_p, c_p],
+    "kai0_denoise_glue_rows": [c_p, c_p, c_i64, c_i, c_f, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_i64, c_i, c_i, c_p, c_i, c_i64, c_i64, c_p],
+    "kai0_linear_f32_rows": [c_p, c_i64, c_p, c_i64, c_p, c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_i64, c_i, c_i64, c_i64, c_p, c_i64, c_p],
     "kai0_sumsq": [c_p, c_i, c_i64, c_p, c_p, c_p],
     "kai0_sum_chunks": [c_p, c_i, c_i, c_i64, c_i64, c_p, c_p],
     "kai0_clip_coef": [c_p, c_f, c_p, c_p, c_p],

@@ -53,7 +53,9 @@ class SiglipConfig:
 
 @dataclasses.dataclass
 class Pi0Config:
-    """`openpi.models.pi0_config.Pi0Config` fields (pi0_config.py:19-40). Only pi05=True is implemented."""
+    """`openpi.models.pi0_config.Pi0Config` fields (pi0_config.py:19-40).  pi05=True: pi0.5 (200 prompt slots, the state discretised
+    into the prompt, adaRMS expert); pi05=False: pi0 (48 slots, `state` a model input — one state token in front of the action tokens,
+    plain RMSNorm expert).  Both run on the HIP path (kai0_amd.model.PI0Pytorch)."""
 
     dtype: str = "bfloat16"
     paligemma_variant: str = "gemma_2b"

@@ -14,6 +14,10 @@ trees themselves — each rule cites the JAX definition whose einsum / matmul fi
     layers/mlp/linear [L, F, D]  dot(a, w)              -> down_proj.weight [D, F]                                 :273-278
     layers/pre_attention_norm/scale [L, D], pre_ffw_norm/scale, final_norm/scale   -> *.weight ((1 + w) on both sides) :121-125
     layers/pre_attention_norm_1/Dense_0/{kernel [L, D, 3D], bias [L, 3D]} (adaRMS) -> *.dense.{weight [3D, D], bias}   :128
+    pi0 (pi05=False): the expert's RMSNorm is called with cond = None (embed_suffix returns `adarms_cond = None`, pi0.py:139-177), so it creates
+    `scale` and no `Dense_0` (:119-125): layers/pre_attention_norm_1/scale, pre_ffw_norm_1/scale [L, D], final_norm_1/scale [D]
+                                                         -> gemma_expert.model.{layers.i.*layernorm, norm}.weight
+    Which form a tower has is read off the tree (JAX: `final_norm{sfx}/Dense_0/kernel` present; torch: `norm.dense.weight`).
   PaliGemma/img (src/openpi/models/siglip.py, big_vision ViT; encoder blocks scanned under "encoderblock" :133-141)
     embedding/{kernel [p, p, 3, W], bias}                 -> embeddings.patch_embedding.{weight [W, 3, p, p], bias}   :216-222
     pos_embedding [1, n, W]                               -> embeddings.position_embedding.weight [n, W]             :229
@@ -24,7 +28,9 @@ trees themselves — each rule cites the JAX definition whose einsum / matmul fi
     .../MlpBlock_0/Dense_{0,1}/{kernel, bias}             -> mlp.fc{1,2}.{weight = kernel^T, bias}                   :69-72
     Transformer/encoder_norm/{scale, bias}                -> post_layernorm.{weight, bias}                            :161
     head/{kernel [W, D], bias}                            -> multi_modal_projector.linear.{weight [D, W], bias}       :286
-  top level nnx.Linear (src/openpi/models/pi0.py:93-101): {action_in_proj, action_out_proj, time_mlp_in, time_mlp_out}/
+  top level nnx.Linear (src/openpi/models/pi0.py:92-100): action_in_proj, action_out_proj and, pi0.5 (:94-95), time_mlp_in,
+    time_mlp_out; pi0 (:97-99), state_proj [A, De], action_time_mlp_in [2 De, De] (its input is concatenate([action_tokens,
+    time_tokens], axis=-1), :170-176 — the order of torch's cat, pi0_pytorch.py:277), action_time_mlp_out [De, De]:
     {kernel [in, out], bias}                              -> *.{weight = kernel^T, bias}
 
 No entry exists on the JAX side for `gemma_expert.lm_head.weight` (dead weight of the torch module tree, SURVEY.md §8 a16);
@@ -47,7 +53,8 @@ LM = PWE + "paligemma.model.language_model."
 EX = PWE + "gemma_expert.model."
 VT = PWE + "paligemma.model.vision_tower.vision_model."
 PROJ = PWE + "paligemma.model.multi_modal_projector.linear."
-HEADS = ("action_in_proj", "action_out_proj", "time_mlp_in", "time_mlp_out")
+HEADS = ("action_in_proj", "action_out_proj", "time_mlp_in", "time_mlp_out",  # pi0.5
+         "state_proj", "action_time_mlp_in", "action_time_mlp_out")  # pi0 (whichever the tree holds are converted)
 
 
 def flatten_params(tree: Mapping, sep: str = "/") -> dict:
@@ -91,7 +98,8 @@ def jax_to_torch(params: Mapping, *, fill_missing: bool = False, vocab_size: int
     sd[LM + "embed_tokens.weight"] = _t(emb)
     sd[PWE + "paligemma.lm_head.weight"] = sd[LM + "embed_tokens.weight"]  # tied
 
-    for sfx, dst, ada in (("", LM, False), ("_1", EX, True)):
+    for sfx, dst in (("", LM), ("_1", EX)):
+        ada = f"{llm}final_norm{sfx}/Dense_0/kernel" in p  # the pi0.5 expert; pi0's expert and the PaliGemma tower carry `scale`
         q = p[f"{llm}layers/attn/q_einsum{sfx}/w"]            # [L, N, D, H]
         kv = p[f"{llm}layers/attn/kv_einsum{sfx}/w"]          # [L, 2, K, D, H]
         o = p[f"{llm}layers/attn/attn_vec_einsum{sfx}/w"]     # [L, N, H, D]
@@ -153,7 +161,7 @@ def jax_to_torch(params: Mapping, *, fill_missing: bool = False, vocab_size: int
             sd[name + ".bias"] = _t(p[f"{name}/bias"])
     if fill_missing:
         width = p[f"{llm}layers/attn/q_einsum_1/w"].shape[2]
-        sd[PWE + "gemma_expert.lm_head.weight"] = torch.zeros((vocab_size or emb.shape[0], width), dtype=sd[EX + "norm.dense.bias"].dtype)
+        sd[PWE + "gemma_expert.lm_head.weight"] = torch.zeros((vocab_size or emb.shape[0], width), dtype=sd[EX + "layers.0.self_attn.q_proj.weight"].dtype)
     return sd
 
 
@@ -167,7 +175,8 @@ def torch_to_jax(sd: Mapping[str, torch.Tensor], *, num_heads: int = 8, num_kv_h
     def depth_of(prefix):
         return 1 + max(int(k[len(prefix) :].split(".")[1]) for k in sd if k.startswith(prefix + "layers."))
 
-    for sfx, src, ada in (("", LM, False), ("_1", EX, True)):
+    for sfx, src in (("", LM), ("_1", EX)):
+        ada = src + "norm.dense.weight" in sd
         L = depth_of(src)
         g = lambda i, name: _np(sd[f"{src}layers.{i}.{name}"])  # noqa: E731
         D = g(0, "self_attn.q_proj.weight").shape[1]

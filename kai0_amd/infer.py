@@ -15,7 +15,10 @@ MI355X-first choices:
     (round 5: the switch that recomputed it inside every call is gone — one way to do it);
   * the last prefix layer stops after its K/V projection — nothing reads its attention/MLP output;
   * the whole call (SigLIP -> prefix -> all denoise steps) is recorded once into a hipGraph
-    (torch.cuda.CUDAGraph on ROCm is hipGraph) and replayed per request: no per-op Python or launch cost.
+    (torch.cuda.CUDAGraph on ROCm is hipGraph) and replayed per request: no per-op Python or launch cost;
+  * pi0 (`pi05=False`): `state` is a request input (a static buffer of the graph), the suffix has Hs + 1 rows per
+    sample (state token | action tokens, mask codes 0 / 1 / 2), the time half of `action_time_mlp_in` is hoisted per step like the
+    modulation table, and the expert's plain RMSNorms run through the same folded stack as the constant modulation [w | 0 | 1].
 """
 
 from __future__ import annotations
@@ -76,7 +79,10 @@ class InferenceEngine:
         self.P = n_cam * self.n_img + n_lang
         self.Hs = model.config.action_horizon
         self.A = model.config.action_dim
-        self.S = self.P + self.Hs
+        self.pi05 = bool(model.pi05)
+        self.n_state = 0 if self.pi05 else 1  # pi0: one continuous state token in front of the action tokens
+        self.Ss = self.Hs + self.n_state  # suffix rows per sample
+        self.S = self.P + self.Ss
         self.S_ld = round_up(self.S, 32)  # padded rows: 32-key groups of the decode attention never leave the buffers
         cfg = pe.vlm_cfg
         self.H, self.HD = cfg.num_heads, cfg.head_dim
@@ -98,7 +104,8 @@ class InferenceEngine:
         # adaRMS as a projection prologue) and their switches are gone.
         ecfg = pe.exp_cfg
         self.F = ecfg.mlp_dim
-        self.fast = (not self.force_generic and B * self.Hs <= 128 and ecfg.width == 1024 and NQ_ok(H * HD) and self.F in (1024, 2048, 4096) and HD == 256
+        # pi0 takes the same stack: a plain GemmaRMSNorm is the adaRMS arithmetic with the constant modulation [w | 0 | 1] (`_build_fast`)
+        self.fast = (not self.force_generic and B * self.Ss <= 128 and ecfg.width == 1024 and NQ_ok(H * HD) and self.F in (1024, 2048, 4096) and HD == 256
                      and self.S <= 1024 and self.P % 8 == 0)  # fmt: skip
         self._weights_tag = self._fingerprint()
         if self.fast:
@@ -186,10 +193,15 @@ class InferenceEngine:
         for l in vt.encoder.layers:
             at = l.self_attn
             srcs += [at.q_proj.weight, at.k_proj.weight, at.v_proj.weight, at.q_proj.bias, at.k_proj.bias, at.v_proj.bias]
-        srcs += [m for l in ex.layers for d in (l.input_layernorm.dense, l.post_attention_layernorm.dense) for m in (d.weight, d.bias)]
-        srcs += [ex.norm.dense.weight, ex.norm.dense.bias]
-        m = self.model  # the cached modulation table is cut from these too
-        srcs += [m.time_mlp_in.weight, m.time_mlp_in.bias, m.time_mlp_out.weight, m.time_mlp_out.bias]
+        m = self.model
+        if self.pi05:
+            srcs += [m for l in ex.layers for d in (l.input_layernorm.dense, l.post_attention_layernorm.dense) for m in (d.weight, d.bias)]
+            srcs += [ex.norm.dense.weight, ex.norm.dense.bias]
+            # the cached modulation table is cut from these too
+            srcs += [m.time_mlp_in.weight, m.time_mlp_in.bias, m.time_mlp_out.weight, m.time_mlp_out.bias]
+        else:  # pi0: the cached per-step time vectors are cut from action_time_mlp_in; the other heads are listed for the content stamp
+            srcs += [w for l in ex.layers for w in (l.input_layernorm.weight, l.post_attention_layernorm.weight)] + [ex.norm.weight]
+            srcs += [p for h in (m.state_proj, m.action_time_mlp_in, m.action_time_mlp_out) for p in (h.weight, h.bias)]
         self._fp_srcs = srcs  # (the parameter OBJECTS are stable: load_state_dict / optimizer steps / .to() change data_ptr or _version)
         return (optim.WEIGHT_UPDATES[0], *((p.data_ptr(), p._version) for p in srcs))
 
@@ -310,12 +322,29 @@ class InferenceEngine:
         self.w_gu_raw = [torch.cat([l.mlp.gate_proj.weight, l.mlp.up_proj.weight], 0).contiguous() for l in ex.layers]
         self.w_o = [ops.pack_skinny_weight(l.self_attn.o_proj.weight) for l in ex.layers]
         self.w_d = [ops.pack_skinny_weight(l.mlp.down_proj.weight) for l in ex.layers]
+        # decode attention: needs the value cache transposed ([HD][keys])
+        self.vt_all = torch.zeros((self.L, B, HD, self.S_ld), dtype=BF16, device=dev)
+        if not self.pi05:
+            # pi0: the expert's norms are plain GemmaRMSNorms, x_hat (1 + w) (modeling_gemma.py:77-81) — the adaRMS arithmetic with the
+            # constant modulation row [scale = w | shift = 0 | gate = 1]: (x_hat (1 + w)) + 0.0 and x + y * 1.0 round nowhere (compare :80
+            # with :102, and `_gated_residual` :209-227 with gate None).  Folded: W' = bf16(W (1 + w)), cvec = 0 — ONE packed set per
+            # layer for all steps (0.4 GB against pi0.5's per-(step, layer) 4 GB), no gates (the kernels' plain residual epilogue).
+            per_layer = []
+            for l, layer in enumerate(ex.layers):
+                ent = []
+                for w, nw in ((self.w_qkv_raw[l], layer.input_layernorm.weight), (self.w_gu_raw[l], layer.post_attention_layernorm.weight)):
+                    wp = (w.float() * (1.0 + nw.float())[None, :]).to(BF16)
+                    ent.append((ops.pack_skinny_weight(wp), torch.zeros(w.shape[0], dtype=F32, device=dev)))
+                per_layer.append(ent)
+            self._plain_fold = per_layer
+            De = self.De
+            self._mod_final = torch.cat([ex.norm.weight.float(), torch.zeros(De, dtype=F32, device=dev),
+                                         torch.ones(De, dtype=F32, device=dev)]).reshape(1, 3 * De).contiguous()
+            return
         # all 37 adaRMS `dense` layers stacked: the modulations of every layer and step come out of ONE f32 GEMM
         dens = [m for l in ex.layers for m in (l.input_layernorm.dense, l.post_attention_layernorm.dense)] + [ex.norm.dense]
         self.w_mod = torch.cat([m.weight for m in dens], 0).contiguous()
         self.b_mod = torch.cat([m.bias for m in dens], 0).contiguous()
-        # decode attention: needs the value cache transposed ([HD][keys])
-        self.vt_all = torch.zeros((self.L, B, HD, self.S_ld), dtype=BF16, device=dev)
 
     # ---------------------------------------------------------------------------------------------- attention
     def _attend(self, l: int, q0: int, Sq: int, Sk: int, qcode, kcode):
@@ -378,7 +407,8 @@ class InferenceEngine:
         prefix = self._embed_prefix(images, img_masks, lang_tokens, lang_masks)
         # mask codes and position ids of the whole request (prefix + action tokens) in one launch: what build_mask_codes makes of
         # embed_prefix's / embed_suffix's pad and att masks, bit for bit (tests/test_kernels_gpu.py::test_prefix_codes_...)
-        qcode, kcode, pos = ops.prefix_codes([m.to(torch.bool) for m in img_masks], lang_masks.to(torch.bool), self.n_img, Hs)
+        qcode, kcode, pos = ops.prefix_codes([m.to(torch.bool) for m in img_masks], lang_masks.to(torch.bool), self.n_img, Hs,
+                                             n_state=self.n_state)
         self.qcode, self.kcode, self.pos = qcode, kcode, pos
         self.pos_prefix = pos[:, :P].contiguous()
         self.pos_suffix = pos[:, P:].contiguous()
@@ -484,13 +514,15 @@ class InferenceEngine:
         gated residual], [gate|up + GeGLU], [down_proj + gated residual], with the adaRMS norms folded into the weights: the projections
         read the raw residual stream, the producers (denoise glue, o_proj, down_proj) hand the rows' partial sums of squares along (`sq`:
         [parts, M] f32); the gates are precomputed for all steps (`_gate`).  Returns (xs, sq, parts) for the next layer."""
-        B, P, Hs, De, H, HD, S_ld, F = self.B, self.P, self.Hs, self.De, self.H, self.HD, self.S_ld, self.F
+        B, P, De, H, HD, S_ld, F = self.B, self.P, self.De, self.H, self.HD, self.S_ld, self.F
+        Hs = self.Ss  # suffix rows per sample (pi0: the state token + the action tokens)
         M, dev = B * Hs, self.dev
         cos, sin = self._rope_cs
         layer = self.pe.gemma_expert.model.layers[l]
         NQ = H * HD
-        ld = self._mod_ld
-        (wq, cq), (wg, cg) = folded[step][l]
+        ada = self.pi05  # pi0: plain residuals (no gate operand), one folded weight set for all steps
+        ld = self._mod_ld if ada else 0
+        (wq, cq), (wg, cg) = folded[step][l] if ada else folded[l]
         ops.skinny_gemm(xs, wq, M=M, N=NQ + 2 * HD, K=De, lda=De, ldw=De, mode=1, pair_stride=HD // 2, split_k=-1,
                         segs=[(self.q_buf, NQ, 0, NQ, 1), (self.k_cache[l], HD, NQ, NQ + HD, 1),
                               (self.vt_all[l], S_ld, NQ + HD, NQ + 2 * HD, 2)],
@@ -502,8 +534,8 @@ class InferenceEngine:
         x1 = torch.empty((M, De), dtype=BF16, device=dev)
         sq1 = torch.empty((De // 16, M), dtype=F32, device=dev)
         ops.skinny_gemm(self.att_buf, self.w_o[l], M=M, N=De, K=NQ, lda=NQ, ldw=NQ, split_k=-1,
-                        a_map=(Hs, S_ld, P), segs=[(x1, De, 0, De, 0)], gate=self._gate(2 * l, rows), gate_rpb=Hs, gate_ld=ld,
-                        residual=xs, ldr=De, w_packed=True, rowsq_out=sq1)  # fmt: skip
+                        a_map=(Hs, S_ld, P), segs=[(x1, De, 0, De, 0)], gate=self._gate(2 * l, rows) if ada else None, gate_rpb=Hs,
+                        gate_ld=ld, residual=xs, ldr=De, w_packed=True, rowsq_out=sq1)  # fmt: skip
         h = torch.empty((M, F), dtype=BF16, device=dev)
         ops.skinny_gemm(x1, wg, M=M, N=2 * F, K=De, lda=De, ldw=De, mode=2, pair_stride=F, split_k=-1,
                         segs=[(h, F, 0, F, 0)], eps=layer.post_attention_layernorm.eps, w_packed=True,
@@ -511,16 +543,69 @@ class InferenceEngine:
         xs = torch.empty((M, De), dtype=BF16, device=dev)
         sq = torch.empty((De // 16, M), dtype=F32, device=dev)
         ops.skinny_gemm(h, self.w_d[l], M=M, N=De, K=F, lda=F, ldw=F, split_k=-1, segs=[(xs, De, 0, De, 0)],
-                        gate=self._gate(2 * l + 1, rows), gate_rpb=Hs, gate_ld=ld, residual=x1, ldr=De, w_packed=True,
+                        gate=self._gate(2 * l + 1, rows) if ada else None, gate_rpb=Hs, gate_ld=ld, residual=x1, ldr=De, w_packed=True,
                         rowsq_out=sq)  # fmt: skip
         return xs, sq, De // 16
 
     def _expert_stack_folded(self, xs, sq, step: int, rows, folded):
         """All expert layers of one denoise step (the step seam, kai0_denoise_glue, applies the final norm)."""
-        parts = 1  # the step's first rows come from the glue kernel: one partial per row
+        parts = sq.shape[0]  # the step's first rows come from the glue kernel (one partial per row) / pi0's suffix embedding (De / 16)
         for l in range(self.L):
             xs, sq, parts = self._expert_layer_folded(l, xs, sq, parts, step, rows, folded)
         return xs
+
+    def _time_vectors(self, times: list[float]):
+        """pi0: the time half of `action_time_mlp_in` for every step of the schedule, tvec[step] = W_in[:, De:2De] time_emb(t_step) + b_in
+        (f32 [steps, De]) — a function of the weights and the schedule only, like pi0.5's modulation table: once per engine, through
+        the library's exact-f32 GEMM.  The action half W_in[:, :De] is kept as a contiguous copy next to it."""
+        model, De, n = self.model, self.De, len(times)
+        tt = torch.tensor(times, dtype=F32).to(self.dev)
+        te = torch.empty((n, De), dtype=F32, device=self.dev)
+        _lib.call("kai0_time_sincos", tt.data_ptr(), te.data_ptr(), n, De, 4e-3, 4.0, ops._stream())
+        w = model.action_time_mlp_in.weight
+        tvec = ops.linear_f32(te, w[:, De:].contiguous(), model.action_time_mlp_in.bias)
+        return tvec, w[:, :De].contiguous()
+
+    def _pi0_suffix_embed(self, x_t, step: int, tv, xs):
+        """pi0 embed_suffix of one denoise step (pi0_pytorch.py:263-285) into the action rows 1 .. Hs of every sample's Hs + 1 suffix rows
+        `xs` (row 0, the state token, is constant for a request: `_run` writes it once): action_in_proj, the action half of
+        action_time_mlp_in + the step's hoisted time vector, SiLU, action_time_mlp_out — f32, one bf16 rounding at the store."""
+        model, B, Hs, De = self.model, self.B, self.Hs, self.De
+        tvec, w_act = tv
+        a = ops.linear_f32(x_t.view(B * Hs, self.A), model.action_in_proj.weight, model.action_in_proj.bias)
+        h = ops.silu_f32(ops.linear_f32(a, w_act, tvec[step].contiguous()))
+        y = ops.linear_f32(h, model.action_time_mlp_out.weight, model.action_time_mlp_out.bias)
+        ops._copy_rows(ops.cast(y, BF16), xs, B, Hs, De, Hs * De, 0, De, self.Ss * De, 1, De)
+
+    def _denoise_step_plain(self, x_t, step: int, tv, xs):
+        """One Euler step of pi0 on the generic path: `_denoise_step` with plain RMSNorms and ungated residuals over Hs + 1 suffix rows
+        (the state token's layers are recomputed every step, as the reference does); action_out_proj reads the last Hs rows."""
+        model, pe = self.model, self.pe
+        B, P, Hs, Ss, De = self.B, self.P, self.Hs, self.Ss, self.De
+        H, HD, S_ld = self.H, self.HD, self.S_ld
+        ex = pe.gemma_expert.model
+        inv_freq = self._inv_freq
+        self._pi0_suffix_embed(x_t, step, tv, xs)
+        for l, layer in enumerate(ex.layers):
+            hs = ops.rmsnorm(xs, layer.input_layernorm.weight, layer.input_layernorm.eps)
+            at = layer.self_attn
+            self._proj_into(hs, at.q_proj, self.q_buf, Ss, P, H * HD)
+            self._proj_into(hs, at.k_proj, self.k_cache[l], Ss, P, HD)
+            self._proj_into(hs, at.v_proj, self.v_cache[l], Ss, P, HD)
+            ops.rope_(self.q_buf, self.pos_suffix, inv_freq, B, Ss, S_ld, P, H, HD)
+            ops.rope_(self.k_cache[l], self.pos_suffix, inv_freq, B, Ss, S_ld, P, 1, HD)
+            self._attend(l, P, Ss, P + Ss, self.qcode, self.kcode)
+            xs = self._oproj(at.o_proj, Ss, P, residual=xs)
+            hs = ops.rmsnorm(xs, layer.post_attention_layernorm.weight, layer.post_attention_layernorm.eps)
+            g = ops.linear_fwd(hs, layer.mlp.gate_proj.weight)
+            u = ops.linear_fwd(hs, layer.mlp.up_proj.weight)
+            _lib.call("kai0_geglu_fwd", g.data_ptr(), u.data_ptr(), g.data_ptr(), g.numel(), ops._stream())
+            xs = ops.linear_fwd(g, layer.mlp.down_proj.weight, residual=xs)
+        out = ops.rmsnorm(xs, ex.norm.weight, ex.norm.eps)
+        act = torch.empty((B * Hs, De), dtype=BF16, device=self.dev)
+        ops._copy_rows(out, act, B, Hs, De, Ss * De, Ss - Hs, De, Hs * De, 0, De)
+        v = ops.linear_f32(ops.cast(act, F32), model.action_out_proj.weight, model.action_out_proj.bias)
+        return v.view(B, Hs, self.A)
 
     def _denoise_step(self, x_t, step: int, mods, mf):
         """One Euler step on the generic path (shapes the production stack was not built for): per layer adaRMS, three projection
@@ -553,7 +638,63 @@ class InferenceEngine:
         v = ops.linear_f32(ops.cast(out, F32), model.action_out_proj.weight, model.action_out_proj.bias)
         return v.view(B, Hs, self.A)
 
-    def _run(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int):
+    def _run_pi0(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, state):
+        """pi0 chunk: prefix pass, the request's state token once, then the Euler loop over Hs + 1 suffix rows."""
+        times = euler_times(num_steps)
+        dt = float(np.float32(-1.0 / num_steps))
+        tv = self._mods_cache.get(tuple(times))
+        if tv is None:  # first (warm-up) run of this schedule: outside graph capture
+            tv = self._mods_cache[tuple(times)] = self._time_vectors(times)
+        model, B, De = self.model, self.B, self.De
+        x_t = noise.clone().contiguous()
+        self._prefix_pass(images, img_masks, lang_tokens, lang_masks)
+        if self.fast:
+            return self._denoise_pi0_folded(x_t, state, tv, len(times), dt)
+        xs0 = torch.empty((B * self.Ss, De), dtype=BF16, device=self.dev)
+        s = ops.linear_f32(state.to(F32).contiguous(), model.state_proj.weight, model.state_proj.bias)
+        ops._copy_rows(ops.cast(s, BF16), xs0, B, 1, De, De, 0, De, self.Ss * De, 0, De)  # row 0 of every sample: constant over the steps
+        for step in range(len(times)):
+            v_t = self._denoise_step_plain(x_t, step, tv, xs0)
+            ops.euler_step_(x_t, v_t, dt)
+        self._content_stamp()
+        return x_t
+
+    def _denoise_pi0_folded(self, x_t, state, tv, n: int, dt: float):
+        """pi0's Euler loop on the production stack.  One suffix buffer xs [B (Hs + 1), De] + its sums of squares [De / 16, B (Hs + 1)]
+        for all steps: row 0 of every sample = bf16(state_proj(state)), written once per request (kai0_denoise_glue_rows' opening half
+        with w_in = state_proj); rows 1 .. Hs by `ops.pi0_suffix_embed` at the start of every step.  The seam behind a step is
+        kai0_denoise_glue_rows' closing half on the action rows: the final plain RMSNorm as the constant modulation row `_mod_final`,
+        action_out_proj, the Euler update of x_t.  The state token's layers are recomputed every step, as the reference does."""
+        model, B, Hs, Ss, De, P, HD, S_ld = self.model, self.B, self.Hs, self.Ss, self.De, self.P, self.HD, self.S_ld
+        M = B * Hs
+        x2 = x_t.view(M, self.A)
+        tvec, _ = tv
+        self._rope_cs = ops.rope_table(self.pos_suffix, self._inv_freq)
+        # prefix value rows of every layer -> transposed cache, one launch
+        ops.transpose_strided(self.v_all, self.vt_all, R=P, C=HD, src_ld=HD, dst_ld=S_ld, batch=self.L * B, src_bs=S_ld * HD,
+                              dst_bs=HD * S_ld)
+        xs = torch.empty((B * Ss, De), dtype=BF16, device=self.dev)
+        sq = torch.zeros((De // 16, B * Ss), dtype=F32, device=self.dev)  # the state rows keep ONE partial (row 0 of sq), the rest 0
+        ops.denoise_glue(state.to(F32).contiguous(), w_in=model.state_proj.weight, b_in=model.state_proj.bias, xs_next=xs, rowsq_next=sq,
+                         row_map=(1, Ss, 0))
+        ex_norm = self.pe.gemma_expert.model.norm
+        w_a, b_a = model.action_in_proj.weight, model.action_in_proj.bias
+        w_in, w_out, b_out = model.action_time_mlp_in.weight, model.action_time_mlp_out.weight, model.action_time_mlp_out.bias
+        for step in range(n):
+            ops.pi0_suffix_embed(x2, w_a, b_a, w_in, tvec[step], w_out, b_out, xs, sq, Hs, Ss)
+            last = self._expert_stack_folded(xs, sq, step, None, self._plain_fold)
+            ops.denoise_glue(x2, xs=last, mod=self._mod_final, mod_ld=3 * De, rows_per_batch=M, eps=ex_norm.eps,
+                             w_out=model.action_out_proj.weight, b_out=model.action_out_proj.bias, dt=dt, row_map=(Hs, Ss, Ss - Hs))
+        self._content_stamp()
+        return x_t
+
+    def _run(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, state=None):
+        if not self.pi05:
+            if state is None and self._static_in is not None:
+                state = self._static_in["state"]  # the captured request's (a stage timed on the static inputs)
+            if state is None:
+                raise ValueError("a pi0 engine needs the request's `state`")
+            return self._run_pi0(images, img_masks, lang_tokens, lang_masks, noise, num_steps, state)
         times = euler_times(num_steps)
         dt = float(np.float32(-1.0 / num_steps))
         if tuple(times) not in self._times_dev:  # H2D copy: must happen outside graph capture (warm-up run)
@@ -613,18 +754,23 @@ class InferenceEngine:
 
     # -------------------------------------------------------------------------------------------------- API
     @torch.no_grad()
-    def sample_actions(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int = 10):
+    def sample_actions(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int = 10, state=None):
+        """`state`: the request's robot state f32 [B, action_dim] — a model input of pi0 (ignored by pi0.5, whose state is in the prompt)."""
+        if self.pi05:
+            state = None
         if not self.use_graph:
-            return self._run(images, img_masks, lang_tokens, lang_masks, noise, num_steps)
+            return self._run(images, img_masks, lang_tokens, lang_masks, noise, num_steps, state)
         if self._graph is None or self._graph_steps != num_steps:
-            self._capture(images, img_masks, lang_tokens, lang_masks, noise, num_steps)
+            self._capture(images, img_masks, lang_tokens, lang_masks, noise, num_steps, state)
         if self._graph is None:  # capture refused: stay on eager HIP launches
-            return self._run(images, img_masks, lang_tokens, lang_masks, noise, num_steps)
-        self._replay(images, img_masks, lang_tokens, lang_masks, noise)
+            return self._run(images, img_masks, lang_tokens, lang_masks, noise, num_steps, state)
+        self._replay(images, img_masks, lang_tokens, lang_masks, noise, state)
         return self._static_out.clone()
 
-    def _replay(self, images, img_masks, lang_tokens, lang_masks, noise):
+    def _replay(self, images, img_masks, lang_tokens, lang_masks, noise, state=None):
         si = self._static_in
+        if si["state"] is not None:
+            si["state"].copy_(state)
         for dst, src in zip(si["images"], images, strict=True):
             dst.copy_(src)
         for dst, src in zip(si["img_masks"], img_masks, strict=True):
@@ -635,34 +781,35 @@ class InferenceEngine:
         self._graph.replay()
 
     @torch.no_grad()
-    def replay_then_verify(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int):
+    def replay_then_verify(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, state=None):
         """The serving fast path: queue the captured chunk first, THEN check that the weights are still the ones the engine was built
         from (the check is host work; the chunk only writes engine-owned buffers).  Returns the chunk, or None when there is no graph for
         this schedule yet or the weights changed (the queued result is then dropped: the caller rebuilds the engine and runs again)."""
         if not self.use_graph or self._graph is None or self._graph_steps != num_steps:
             return None
-        self._replay(images, img_masks, lang_tokens, lang_masks, noise)
+        self._replay(images, img_masks, lang_tokens, lang_masks, noise, None if self.pi05 else state)
         if not self.weights_unchanged():
             return None
         return self._static_out.clone()
 
-    def _capture(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int):
+    def _capture(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, state=None):
         si = {
             "images": [im.clone().contiguous() for im in images],
             "img_masks": [m.clone() for m in img_masks],
             "lang_tokens": lang_tokens.clone().contiguous(),
             "lang_masks": lang_masks.clone().contiguous(),
             "noise": noise.clone().contiguous(),
+            "state": state.to(F32).clone().contiguous() if state is not None else None,  # pi0: a static buffer inside the graph
         }
         try:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture requires
-                self._run(si["images"], si["img_masks"], si["lang_tokens"], si["lang_masks"], si["noise"], num_steps)
+                self._run(si["images"], si["img_masks"], si["lang_tokens"], si["lang_masks"], si["noise"], num_steps, si["state"])
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                out = self._run(si["images"], si["img_masks"], si["lang_tokens"], si["lang_masks"], si["noise"], num_steps)
+                out = self._run(si["images"], si["img_masks"], si["lang_tokens"], si["lang_masks"], si["noise"], num_steps, si["state"])
             self._graph, self._graph_steps, self._static_in, self._static_out = graph, num_steps, si, out
         except Exception as e:  # noqa: BLE001 - capture problems must not take serving down
             logger.warning("hipGraph capture failed (%s); running eager HIP launches", e)

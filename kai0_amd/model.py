@@ -1,4 +1,8 @@
-"""PI0Pytorch-shaped pi0.5 model whose arithmetic runs on the MI355X HIP kernels (libkai0hip.so).
+"""PI0Pytorch-shaped pi0.5 / pi0 model whose arithmetic runs on the MI355X HIP kernels (libkai0hip.so).
+
+Both branches of the reference class are here: pi0.5 (`pi05=True`: adaRMS expert conditioned on the time MLP, state discretised
+into the prompt) and pi0 (`pi05=False`: one continuous state token in front of the action tokens, time mixed into the action
+tokens by `action_time_mlp_in/out`, plain RMSNorm expert; pi0_pytorch.py:96-109, 243-297).
 
 Boundary mirrored: `PI0Pytorch(config)`, `.forward(observation, actions, noise=None, time=None)
 -> loss [B, H, A]`, `.sample_actions(device, observation, noise=None, num_steps=10) -> [B, H, A]`,
@@ -301,7 +305,7 @@ class PaliGemmaWithExpertModel(nn.Module):
         if use_adarms is None:
             use_adarms = [False, False]
         if use_adarms[0]:
-            raise NotImplementedError("adaRMS on the PaliGemma tower is not part of pi0.5")
+            raise NotImplementedError("adaRMS on the PaliGemma tower is not part of pi0 / pi0.5")
         self.vlm_cfg, self.exp_cfg = vlm_config, action_expert_config
         self.siglip_cfg = siglip or SiglipConfig()
         if self.siglip_cfg.projection_dim != vlm_config.width:
@@ -377,10 +381,12 @@ class PaliGemmaWithExpertModel(nn.Module):
         return fn(*args)
 
     # ---- joint, layer-interleaved forward (gemma_pytorch.py:126-279) ---------------------------------------
-    def forward_joint(self, prefix: torch.Tensor, suffix: torch.Tensor, qcode, kcode, pos, cond: torch.Tensor,
+    def forward_joint(self, prefix: torch.Tensor, suffix: torch.Tensor, qcode, kcode, pos, cond: torch.Tensor | None,
                       B: int, P: int, Hs: int) -> torch.Tensor:  # fmt: skip
-        """prefix bf16 [B*P, Dp], suffix bf16 [B*Hs, De], cond f32 [B, De] -> suffix output after the expert's
-        final adaRMS norm, bf16 [B*Hs, De].  (The prefix's final norm has no consumer in training.)"""
+        """prefix bf16 [B*P, Dp], suffix bf16 [B*Hs, De] (Hs suffix rows per sample: pi0 counts its state token), cond f32 [B, De]
+        -> suffix output after the expert's final norm, bf16 [B*Hs, De].  cond = None (pi0): the expert's norms are plain
+        GemmaRMSNorms and its residuals ungated (modeling_gemma.py:77-81, 209-227) — the PaliGemma side's arithmetic.
+        (The prefix's final norm has no consumer in training.)"""
         lm, ex = self.paligemma.model.language_model, self.gemma_expert.model
         cfg = self.vlm_cfg
         H, HD = cfg.num_heads, cfg.head_dim
@@ -410,8 +416,11 @@ class PaliGemmaWithExpertModel(nn.Module):
         def layer_fn(xp, xs, lp, le, last=False):
             ap, ae = lp.self_attn, le.self_attn
             with on_side():
-                mod1 = ops.linear_f32(cond, le.input_layernorm.dense.weight, le.input_layernorm.dense.bias)
-                xs, hs, gate1 = ops.adarms_res(xs, mod1, Hs, le.input_layernorm.eps)
+                if cond is None:
+                    xs, hs = ops.rmsnorm_res(xs, le.input_layernorm.weight, le.input_layernorm.eps)
+                else:
+                    mod1 = ops.linear_f32(cond, le.input_layernorm.dense.weight, le.input_layernorm.dense.bias)
+                    xs, hs, gate1 = ops.adarms_res(xs, mod1, Hs, le.input_layernorm.eps)
                 qkv_s = ops.linear_multi(hs, [ae.q_proj.weight, ae.k_proj.weight, ae.v_proj.weight])
             xp, hp = ops.rmsnorm_res(xp, lp.input_layernorm.weight, lp.input_layernorm.eps)
             qkv_p = ops.linear_multi(hp, [ap.q_proj.weight, ap.k_proj.weight, ap.v_proj.weight])
@@ -424,11 +433,16 @@ class PaliGemmaWithExpertModel(nn.Module):
                 hand((att_s,), side)
             # suffix (action expert): gated residuals (modeling_gemma.py:209-227)
             with on_side():
-                xs = ops.gated_residual(xs, _lin(att_s, ae.o_proj), gate1, Hs)
-                mod2 = ops.linear_f32(cond, le.post_attention_layernorm.dense.weight, le.post_attention_layernorm.dense.bias)
-                xs, hs, gate2 = ops.adarms_res(xs, mod2, Hs, le.post_attention_layernorm.eps)
-                ys = ops.geglu_mlp(hs, le.mlp.gate_proj.weight, le.mlp.up_proj.weight, le.mlp.down_proj.weight)
-                xs = ops.gated_residual(xs, ys, gate2, Hs)
+                if cond is None:  # plain residuals, as on the prefix side
+                    xs = _lin(att_s, ae.o_proj, residual=xs)
+                    xs, hs = ops.rmsnorm_res(xs, le.post_attention_layernorm.weight, le.post_attention_layernorm.eps)
+                    xs = ops.geglu_mlp(hs, le.mlp.gate_proj.weight, le.mlp.up_proj.weight, le.mlp.down_proj.weight, residual=xs)
+                else:
+                    xs = ops.gated_residual(xs, _lin(att_s, ae.o_proj), gate1, Hs)
+                    mod2 = ops.linear_f32(cond, le.post_attention_layernorm.dense.weight, le.post_attention_layernorm.dense.bias)
+                    xs, hs, gate2 = ops.adarms_res(xs, mod2, Hs, le.post_attention_layernorm.eps)
+                    ys = ops.geglu_mlp(hs, le.mlp.gate_proj.weight, le.mlp.up_proj.weight, le.mlp.down_proj.weight)
+                    xs = ops.gated_residual(xs, ys, gate2, Hs)
             if last and _SKIP_DEAD_PREFIX:
                 # nothing reads the prefix stream after the last joint attention (the model's output is the suffix; the prefix's
                 # final norm has no consumer either): its o_proj, post-attention norm and MLP in the LAST layer are dead values —
@@ -445,7 +459,7 @@ class PaliGemmaWithExpertModel(nn.Module):
         hk = self.unit_hooks
         if dual:
             side.wait_stream(main)
-            hand((xs, cond), side)
+            hand((xs,) if cond is None else (xs, cond), side)
         for l, (lp, le) in enumerate(zip(lm.layers, ex.layers, strict=True)):
             gathered = hk.pre_forward(f"joint.{l}")
             if dual and gathered:
@@ -455,35 +469,41 @@ class PaliGemmaWithExpertModel(nn.Module):
                 side.wait_stream(main)
             xp, xs = self._maybe_remat(layer_fn, xp, xs, lp, le, l == n_layers - 1)
             xp, xs = hk.post_forward(f"joint.{l}", xp, xs)
-        hk.pre_forward("head")  # final adaRMS norm, action_out_proj (and the estimator's value head): never released early
+        hk.pre_forward("head")  # final (ada)RMS norm, action_out_proj (and the estimator's value head): never released early
         if dual:
             main.wait_stream(side)
             hand((xs,), main)
+        if cond is None:
+            return ops.rmsnorm(xs, ex.norm.weight, ex.norm.eps)
         modf = ops.linear_f32(cond, ex.norm.dense.weight, ex.norm.dense.bias)
         out, _ = ops.adarms(xs, modf, Hs, ex.norm.eps)
         return out
 
 
 class PI0Pytorch(nn.Module):
-    """Drop-in for openpi's `PI0Pytorch` (pi0_pytorch.py:84-461), pi0.5 branch."""
+    """Drop-in for openpi's `PI0Pytorch` (pi0_pytorch.py:84-461): the pi0.5 branch (`config.pi05=True`) and the pi0 branch
+    (`pi05=False`: `state_proj`, `action_time_mlp_in/out` instead of `time_mlp_in/out`, a non-adaptive expert)."""
 
     def __init__(self, config: Pi0Config):
         super().__init__()
         self.config = config
         self.pi05 = config.pi05
-        if not self.pi05:
-            raise NotImplementedError("only the pi0.5 branch (pi05=True) is on the hot path")
         vlm = get_config(config.paligemma_variant)
         exp = get_config(config.action_expert_variant)
         siglip = getattr(config, "siglip", None) or SiglipConfig()
         self.paligemma_with_expert = PaliGemmaWithExpertModel(
-            vlm, exp, use_adarms=[False, True], precision=config.dtype, vocab=getattr(config, "vocab_size", 257_152),
+            vlm, exp, use_adarms=[False, True] if self.pi05 else [False, False], precision=config.dtype, vocab=getattr(config, "vocab_size", 257_152),
             siglip=siglip,
         )  # fmt: skip
         self.action_in_proj = Linear(config.action_dim, exp.width)
         self.action_out_proj = Linear(exp.width, config.action_dim)
-        self.time_mlp_in = Linear(exp.width, exp.width)
-        self.time_mlp_out = Linear(exp.width, exp.width)
+        if self.pi05:
+            self.time_mlp_in = Linear(exp.width, exp.width)
+            self.time_mlp_out = Linear(exp.width, exp.width)
+        else:  # pi0_pytorch.py:106-109
+            self.state_proj = Linear(config.action_dim, exp.width)
+            self.action_time_mlp_in = Linear(2 * exp.width, exp.width)
+            self.action_time_mlp_out = Linear(exp.width, exp.width)
         self.gradient_checkpointing_enabled = False
         # the reference hard-codes train=True (random crop/rotate/colour) in forward (pi0_pytorch.py:318);
         # parity tests switch it off and inject noise/time.
@@ -553,13 +573,19 @@ class PI0Pytorch(nn.Module):
 
         units += [(f"siglip.{l}", siglip_layer(layer)) for l, layer in enumerate(vt.encoder.layers)]
         units.append(("prefix", [*vt.post_layernorm.parameters(), *pe.paligemma.model.multi_modal_projector.parameters(),
-                                 lm.embed_tokens.weight, *self.action_in_proj.parameters(), *self.time_mlp_in.parameters(),
-                                 *self.time_mlp_out.parameters()]))  # fmt: skip
+                                 lm.embed_tokens.weight, *self.action_in_proj.parameters(),
+                                 *(p for m in self._time_heads() for p in m.parameters())]))  # fmt: skip
         units += [(f"joint.{l}", [*lp.parameters(), *le.parameters()]) for l, (lp, le) in enumerate(zip(lm.layers, ex.layers))]
         taken = {id(p) for _, ps in units for p in ps}
         dead = pe.gemma_expert.lm_head.weight
         units.append(("head", [p for p in self.parameters() if id(p) not in taken and p is not dead]))
         return units
+
+    def _time_heads(self):
+        """the f32 heads in front of the expert besides action_in_proj: the time MLP (pi0.5) / state_proj + action-time MLP (pi0)"""
+        if self.pi05:
+            return [self.time_mlp_in, self.time_mlp_out]
+        return [self.state_proj, self.action_time_mlp_in, self.action_time_mlp_out]
 
     def set_unit_hooks(self, hooks):
         self.paligemma_with_expert.unit_hooks = hooks if hooks is not None else _NoUnitHooks()
@@ -639,11 +665,24 @@ class PI0Pytorch(nn.Module):
         return embs.view(B, P, D), pad, att
 
     def embed_suffix(self, state, noisy_actions, timestep):
-        """pi0_pytorch.py:237-314 (pi0.5): -> (action embs f32 [B, H, De], pad, att, adarms_cond f32 [B, De])."""
+        """pi0_pytorch.py:237-314 -> (suffix embs f32, pad, att, adarms_cond).  pi0.5: [B, H, De] action tokens, att [1, 0, ...],
+        cond f32 [B, De].  pi0: [B, 1 + H, De] = state token | action-time tokens, att [1, 1, 0, ...], cond None."""
         B, Hs, A = noisy_actions.shape
         De = self.action_in_proj.out_features
         te = torch.empty((B, De), dtype=F32, device=noisy_actions.device)
         _lib.call("kai0_time_sincos", timestep.contiguous().data_ptr(), te.data_ptr(), B, De, 4e-3, 4.0, ops._stream())
+        if not self.pi05:
+            a = ops.linear_f32(noisy_actions.reshape(B * Hs, A).contiguous(), self.action_in_proj.weight, self.action_in_proj.bias)
+            # cat([action_emb, time_emb]) -> action_time_mlp_in -> SiLU -> action_time_mlp_out, all f32 (:275-285); cat is host glue
+            at = torch.cat([a.view(B, Hs, De), te[:, None, :].expand(B, Hs, De)], dim=2).reshape(B * Hs, 2 * De)
+            x = ops.silu_f32(ops.linear_f32(at, self.action_time_mlp_in.weight, self.action_time_mlp_in.bias))
+            y = ops.linear_f32(x, self.action_time_mlp_out.weight, self.action_time_mlp_out.bias)
+            s = ops.linear_f32(state.to(F32).contiguous(), self.state_proj.weight, self.state_proj.bias)
+            embs = torch.cat([s[:, None, :], y.view(B, Hs, De)], dim=1)
+            pad = torch.ones((B, Hs + 1), dtype=torch.bool, device=a.device)
+            att = torch.zeros((B, Hs + 1), dtype=torch.bool, device=a.device)
+            att[:, :2] = True
+            return embs, pad, att, None
         x = ops.silu_f32(ops.linear_f32(te, self.time_mlp_in.weight, self.time_mlp_in.bias))
         cond = ops.silu_f32(ops.linear_f32(x, self.time_mlp_out.weight, self.time_mlp_out.bias))
         a = ops.linear_f32(noisy_actions.reshape(B * Hs, A).contiguous(), self.action_in_proj.weight, self.action_in_proj.bias)
@@ -655,8 +694,8 @@ class PI0Pytorch(nn.Module):
     # ---- training forward ---------------------------------------------------------------------------------
     def _trunk(self, images, img_masks, lang_tokens, lang_masks, state, actions, noise, time, x_t=None):
         """Everything of the training forward up to the expert's output: -> (u_t f32 [B*H, A], suffix_out f32 [B*H, De],
-        v_t f32 [B*H, A]) with suffix_out already through the final adaRMS norm (pi0_pytorch.py:326-368).  With `x_t`
-        given the flow-matching mix is skipped (u_t = None): the suffix is embedded from x_t as is."""
+        v_t f32 [B*H, A]) with suffix_out already through the final norm and cut to the action rows (pi0_pytorch.py:326-368).
+        With `x_t` given the flow-matching mix is skipped (u_t = None): the suffix is embedded from x_t as is."""
         u_t = None
         if x_t is None:
             actions = actions.to(F32).contiguous()
@@ -667,15 +706,21 @@ class PI0Pytorch(nn.Module):
             lang_tokens, lang_masks = self._trim_prompt(lang_tokens, lang_masks)
         prefix, ppad, patt = self.embed_prefix(images, img_masks, lang_tokens, lang_masks)
         suffix, spad, satt, cond = self.embed_suffix(state, x_t, time)
-        prefix, suffix, cond = self.paligemma_with_expert.unit_hooks.post_forward("prefix", prefix, suffix, cond)
+        if cond is None:
+            prefix, suffix = self.paligemma_with_expert.unit_hooks.post_forward("prefix", prefix, suffix)
+        else:
+            prefix, suffix, cond = self.paligemma_with_expert.unit_hooks.post_forward("prefix", prefix, suffix, cond)
         B, P, Dp = prefix.shape
         Hs, De = suffix.shape[1], suffix.shape[2]
         qcode, kcode, pos = build_mask_codes(torch.cat([ppad, spad], dim=1), torch.cat([patt, satt], dim=1))
         suffix_bf = ops.cast_ag(suffix.reshape(B * Hs, De), BF16)
         out = self.paligemma_with_expert.forward_joint(prefix.reshape(B * P, Dp), suffix_bf, qcode, kcode, pos, cond, B, P, Hs)
-        out32 = ops.cast_ag(out, F32)
+        H = x_t.shape[1]
+        if Hs != H:  # pi0: the state token's row is dropped (suffix_out[:, -action_horizon:], :364)
+            out = out.view(B, Hs, De)[:, Hs - H :].reshape(B * H, De)
+        out32 = ops.cast_ag(out.contiguous(), F32)
         v_t = ops.linear_f32(out32, self.action_out_proj.weight, self.action_out_proj.bias)
-        return (u_t.view(B * Hs, -1) if u_t is not None else None), out32, v_t
+        return (u_t.view(B * H, -1) if u_t is not None else None), out32, v_t
 
     def forward(self, observation, actions, noise=None, time=None) -> torch.Tensor:
         """pi0_pytorch.py:316-373 -> un-reduced flow-matching loss f32 [B, H, A]."""
@@ -715,7 +760,7 @@ class PI0Pytorch(nn.Module):
         if eng is not None and eng.shape_matches(*key):
             # the common serving case: same request shape as the last call.  The captured chunk is queued BEFORE the weights are checked
             # (0.13 ms of host work that would otherwise stand in front of every chunk); a failed check falls through to the rebuild
-            out = eng.replay_then_verify(images, img_masks, lang_tokens, lang_masks, noise.to(F32), num_steps)
+            out = eng.replay_then_verify(images, img_masks, lang_tokens, lang_masks, noise.to(F32), num_steps, state=state)
             if out is not None:
                 return out
         if eng is None or not eng.compatible(*key):
@@ -727,12 +772,13 @@ class PI0Pytorch(nn.Module):
             while len(lru) > self._ENGINE_SLOTS:
                 lru.pop(next(iter(lru)))
             self.__dict__["_engine_cur"] = eng
-        return eng.sample_actions(images, img_masks, lang_tokens, lang_masks, noise.to(F32), num_steps)
+        return eng.sample_actions(images, img_masks, lang_tokens, lang_masks, noise.to(F32), num_steps, state=state)
 
 
 class AdvantageEstimator(PI0Pytorch):
     """The advantage / progress estimator of Stage-Advantage (pi0_pytorch.py:464-644): the pi0.5 trunk plus a value head
-    (Linear-SiLU-Linear-SiLU-Linear-Tanh, f32) on the first suffix token's final representation.
+    (Linear-SiLU-Linear-SiLU-Linear-Tanh, f32) on the first suffix token's final representation.  pi0.5 only: a pi0 config
+    (`pi05=False`) raises NotImplementedError (its first suffix token would be the state token; no kai0 task trains one).
       forward      -> loss [B, H] = loss_action_weight * mean_d mse(u_t, v_t) + loss_value_weight * mse(value, clamp(progress, +-1))
       sample_values-> value [B, 1] from one joint forward with sampled (or given) noise / time
     State-dict keys follow nn.Sequential numbering: value_head.{0,2,4}.{weight,bias}.  Observations may carry up to six
@@ -740,6 +786,8 @@ class AdvantageEstimator(PI0Pytorch):
     (preprocess_observation_pytorch_custom(..., apply_aug=False))."""
 
     def __init__(self, config):
+        if not config.pi05:
+            raise NotImplementedError("AdvantageEstimator is built on the pi0.5 trunk only (config.pi05 must be True)")
         super().__init__(config)
         self.loss_value_weight = getattr(config, "loss_value_weight", 0.0)
         self.loss_action_weight = getattr(config, "loss_action_weight", 1.0)

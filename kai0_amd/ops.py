@@ -299,9 +299,10 @@ def rope_table(pos, inv_freq, bf16: bool = False):
     return cos, sin
 
 
-def prefix_codes(img_masks, lang_mask, n_img: int, Hs: int):
+def prefix_codes(img_masks, lang_mask, n_img: int, Hs: int, n_state: int = 0):
     """kai0_prefix_codes: (qcode, kcode, pos) int32 [B, ncam n_img + T + Hs] of one pi0.5 request from its camera masks (bool [B] each) and
-    prompt mask (bool [B, T]) in one launch — bit for bit `model.build_mask_codes` on embed_prefix's / embed_suffix's pad and att masks."""
+    prompt mask (bool [B, T]) in one launch — bit for bit `model.build_mask_codes` on embed_prefix's / embed_suffix's pad and att masks.
+    n_state > 0 (pi0: kai0_prefix_state_codes): that many state tokens between the prompt and the actions, [B, ... + n_state + Hs]."""
     B, T = lang_mask.shape
     ms = [m.contiguous() for m in img_masks]
     lm = lang_mask.contiguous()
@@ -310,9 +311,13 @@ def prefix_codes(img_masks, lang_mask, n_img: int, Hs: int):
             raise TypeError("prefix_codes: bool CUDA (HIP) masks expected")
     if any(m.shape != (B,) for m in ms):
         raise ValueError("prefix_codes: camera masks must be [B]")
-    S = len(ms) * n_img + T + Hs
+    S = len(ms) * n_img + T + n_state + Hs
     q, k, p = (torch.empty((B, S), dtype=torch.int32, device=lm.device) for _ in range(3))
     ptrs = (C.c_void_p * len(ms))(*[m.data_ptr() for m in ms])
+    if n_state:
+        _lib.call("kai0_prefix_state_codes", C.addressof(ptrs), len(ms), lm.data_ptr(), B, n_img, T, n_state, Hs, q.data_ptr(), k.data_ptr(),
+                  p.data_ptr(), _stream())  # fmt: skip
+        return q, k, p
     _lib.call("kai0_prefix_codes", C.addressof(ptrs), len(ms), lm.data_ptr(), B, n_img, T, Hs, q.data_ptr(), k.data_ptr(), p.data_ptr(), _stream())
     return q, k, p
 
@@ -1676,16 +1681,67 @@ def mse_loss(u, v):
 
 
 def denoise_glue(x_t, *, xs=None, mod=None, mod_ld=0, rows_per_batch=1, eps=1e-6, w_out=None, b_out=None, dt=0.0, w_in=None,
-                 b_in=None, xs_next=None, rowsq_next=None):
+                 b_in=None, xs_next=None, rowsq_next=None, row_map=None):
     """kai0_denoise_glue: close a denoise step (final adaRMS -> action_out_proj -> Euler update of x_t, in place) and / or open
-    the next one (action_in_proj -> bf16 suffix embedding) in one launch.  x_t: f32 [rows, A] contiguous."""
+    the next one (action_in_proj -> bf16 suffix embedding) in one launch.  x_t: f32 [rows, A] contiguous.
+    row_map = (rpb, bs, off) (kai0_denoise_glue_rows): row r of x_t is row (r // rpb) * bs + r % rpb + off of xs / xs_next / rowsq_next."""
     rows, A = x_t.shape[0], x_t.shape[1]
     D = (xs if xs is not None else xs_next).shape[1]
     for t in (x_t, w_out, b_out, w_in, b_in, mod):
         if t is not None and t.dtype != F32:
             raise TypeError("denoise_glue: x_t, weights, biases and modulations are f32")
+    if row_map is not None:
+        rpb, bs, off = row_map
+        last = ((rows - 1) // rpb) * bs + (rows - 1) % rpb + off  # the last suffix row touched: inside every mapped buffer
+        for t in (xs, xs_next):
+            if t is not None and (t.shape[0] <= last or not t.is_contiguous()):
+                raise ValueError(f"denoise_glue: row map {row_map} reaches row {last} of a buffer of {t.shape[0]} rows")
+        if rowsq_next is not None and rowsq_next.numel() <= last:
+            raise ValueError("denoise_glue: rowsq_next is shorter than the mapped rows")
+        _lib.call("kai0_denoise_glue_rows", _p(xs), _p(mod), mod_ld, rows_per_batch, eps, _p(w_out), _p(b_out), x_t.data_ptr(), dt, _p(w_in),
+                  _p(b_in), _p(xs_next), rows, D, A, _p(rowsq_next), rpb, bs, off, _stream())  # fmt: skip
+        return
     _lib.call("kai0_denoise_glue", _p(xs), _p(mod), mod_ld, rows_per_batch, eps, _p(w_out), _p(b_out), x_t.data_ptr(), dt, _p(w_in),
               _p(b_in), _p(xs_next), rows, D, A, _p(rowsq_next), _stream())
+
+
+def linear_f32_rows(x, w, bias=None, *, K=None, act=0, out_f32=None, out_bf16=None, row_map=None, rowsq_out=None):
+    """kai0_linear_f32_rows: act(x w[:, :K]^T + bias) in exact f32 for M <= 128 rows (act 1: SiLU), into `out_f32` [M, N] and / or as
+    one bf16 rounding into rows (r // rpb) * bs + r % rpb + off of `out_bf16` [rows, N] (row_map = (rpb, bs, off); None: row r) with the
+    stored rows' sums of squares per 16-column tile in `rowsq_out` [N // 16, >= rows of out_bf16]."""
+    M = x.shape[0]
+    N = w.shape[0]
+    K = x.shape[1] if K is None else K
+    for t in (x, w, bias, out_f32, rowsq_out):
+        if t is not None and (t.dtype != F32 or not t.is_cuda):
+            raise TypeError("linear_f32_rows: f32 CUDA (HIP) tensors expected")
+    if x.stride(1) != 1 or w.stride(1) != 1 or w.shape[1] < K or x.shape[1] < K:
+        raise ValueError("linear_f32_rows: x [M, >= K] and w [N, >= K] with unit inner stride")
+    rpb, bs, off = row_map if row_map is not None else (0, 0, 0)
+    if out_bf16 is not None:
+        last = ((M - 1) // rpb) * bs + (M - 1) % rpb + off if rpb else M - 1
+        if out_bf16.dtype != BF16 or not out_bf16.is_contiguous() or out_bf16.shape[1] != N or out_bf16.shape[0] <= last:
+            raise ValueError(f"linear_f32_rows: out_bf16 must be contiguous bf16 [> {last}, {N}]")
+        if rowsq_out is not None and (not rowsq_out.is_contiguous() or rowsq_out.shape[0] < N // 16 or rowsq_out.shape[1] <= last):
+            raise ValueError(f"linear_f32_rows: rowsq_out must be contiguous f32 [>= {N // 16}, > {last}]")
+    if out_f32 is not None and (tuple(out_f32.shape) != (M, N) or out_f32.stride(1) != 1):
+        raise ValueError("linear_f32_rows: out_f32 must be [M, N]")
+    _lib.call("kai0_linear_f32_rows", x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), _p(bias), M, N, K, act, _p(out_f32),
+              out_f32.stride(0) if out_f32 is not None else 0, _p(out_bf16), N, rpb, bs, off, _p(rowsq_out),
+              rowsq_out.stride(0) if rowsq_out is not None else 0, _stream())  # fmt: skip
+
+
+def pi0_suffix_embed(x_t, w_a, b_a, w_in, tvec, w_out, b_out, xs, rowsq, Hs: int, Ss: int):
+    """pi0's action-time tokens of one denoise step (pi0_pytorch.py:270-285 with the time half of action_time_mlp_in hoisted into
+    `tvec` [De] = W_in[:, De:] time_emb(t) + b_in): a = action_in_proj(x_t); h = silu(W_in[:, :De] a + tvec); y = W_out h + b_out, all
+    f32 — the library's exact-f32 GEMM for the A-wide first Linear, kai0_linear_f32_rows for the two De-wide ones — then one bf16
+    rounding into rows 1 .. Hs of every sample's Ss suffix rows of `xs` [B * Ss, De], with their sums of squares per 16-column tile in
+    `rowsq` [De // 16, B * Ss].  Row 0 (the state token) is not touched."""
+    M, De = x_t.shape[0], w_a.shape[0]
+    a = linear_f32(x_t, w_a, b_a)
+    h = torch.empty((M, De), dtype=F32, device=x_t.device)
+    linear_f32_rows(a, w_in, tvec, K=De, act=1, out_f32=h)
+    linear_f32_rows(h, w_out, b_out, out_bf16=xs, row_map=(Hs, Ss, Ss - Hs), rowsq_out=rowsq)
 
 
 def euler_step_(x, v, dt: float):
