@@ -176,6 +176,26 @@ int kai0_gemm_bf16(const kai0_gemm_desc* d, kai0_stream_t stream);
 /* sizeof(kai0_gemm_desc) as compiled: lets a foreign-language binding verify its struct mirror */
 int kai0_gemm_desc_size(void);
 
+/* Which kernel kai0_gemm_bf16 runs for a descriptor: the same validation and the same selection function as the launch, nothing
+ * launched, no device touched (pointers are only checked for null / alignment).  For tests and tools that must know they reach a
+ * given tile instead of restating the rule.  Returns 0 and fills *out, or the error kai0_gemm_bf16 would return. */
+#define KAI0_GEMM_LOOP_PLAIN2 0     /* two-stage 64-deep K loop (128 x 128 default; 256 x 256 NN / TT) */
+#define KAI0_GEMM_LOOP_PLAIN4 1     /* four-stage 64-deep K loop (128 x 128 with at most one block per CU; the eight-wave 128 tile) */
+#define KAI0_GEMM_LOOP_QUADRANT 2   /* 256 x 256 x 64 quadrant schedule (NT) */
+#define KAI0_GEMM_LOOP_RING 3       /* 256 x 256 x 32 four-slot ring (TN) */
+#define KAI0_GEMM_LOOP_PERSISTENT 4 /* persistent NT kernel drawing 256 x 256 tiles from its queue */
+typedef struct kai0_gemm_plan_t {
+    int32_t tile;             /* 128 or 256 (square) */
+    int32_t waves;            /* 4 or 8 per block */
+    int32_t loop;             /* KAI0_GEMM_LOOP_* */
+    int32_t tiles_m, tiles_n; /* tiles of that size over M and over the logical width (2 N for act 6) */
+    int32_t k_chunk;          /* contraction length per split-K slice (K when split_k <= 1); slices past K are empty */
+    int32_t simple_epilogue;  /* 1: the 256 x 256 store-with-little-else epilogue applies (see general_epilogue) */
+    int32_t _pad;
+} kai0_gemm_plan_t;
+int kai0_gemm_plan(const kai0_gemm_desc* d, kai0_gemm_plan_t* out);
+int kai0_gemm_plan_size(void); /* sizeof the plan struct as compiled, as kai0_gemm_desc_size */
+
 /* ------------------------------------------------------------------------------------------------
  * Few-row weight-streaming GEMM for the denoise loop (B*action_horizon <= a few 64-row tiles):
  *   C[M, N] = A[M, K] @ W[N, K]^T, bf16 in, f32 accumulate, with the neighbouring element-wise ops fused.

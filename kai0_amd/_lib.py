@@ -51,6 +51,16 @@ class GemmDesc(C.Structure):
     ]  # fmt: skip
 
 
+class GemmPlan(C.Structure):
+    """Mirror of `kai0_gemm_plan_t` (include/kai0hip.h): the kernel kai0_gemm_bf16 selects for a descriptor."""
+
+    _fields_ = [("tile", C.c_int32), ("waves", C.c_int32), ("loop", C.c_int32), ("tiles_m", C.c_int32), ("tiles_n", C.c_int32),
+                ("k_chunk", C.c_int32), ("simple_epilogue", C.c_int32), ("_pad", C.c_int32)]  # fmt: skip
+
+
+GEMM_LOOPS = ("plain2", "plain4", "quadrant", "ring", "persistent")  # KAI0_GEMM_LOOP_* in order
+
+
 class AttnDesc(C.Structure):
     """Mirror of `kai0_attn_desc` (include/kai0hip.h)."""
 
@@ -123,6 +133,8 @@ _PROTOS: dict[str, list] = {
     "kai0_gemm_desc_size": [],
     "kai0_device_info": [c_i, C.POINTER(c_i), C.POINTER(c_i), C.c_char_p],
     "kai0_gemm_bf16": [C.POINTER(GemmDesc), c_p],
+    "kai0_gemm_plan": [C.POINTER(GemmDesc), C.POINTER(GemmPlan)],
+    "kai0_gemm_plan_size": [],
     "kai0_attn_fwd": [C.POINTER(AttnDesc), c_p],
     "kai0_attn_desc_size": [],
     "kai0_attn_combine": [c_p, c_p, c_p, c_i, c_i, c_i, c_i64, c_i64, c_i64, c_p],
@@ -238,7 +250,7 @@ def load() -> C.CDLL:
         raise Kai0HipError(
             f"kai0_gemm_desc layout mismatch: C {lib.kai0_gemm_desc_size()} B vs ctypes {C.sizeof(GemmDesc)} B"
         )
-    for fn, mirror in (("kai0_attn_desc_size", AttnDesc), ("kai0_attn_bwd_desc_size", AttnBwdDesc)):
+    for fn, mirror in (("kai0_attn_desc_size", AttnDesc), ("kai0_attn_bwd_desc_size", AttnBwdDesc), ("kai0_gemm_plan_size", GemmPlan)):
         if getattr(lib, fn)() != C.sizeof(mirror):
             raise Kai0HipError(f"{fn[:-5]} layout mismatch: C {getattr(lib, fn)()} B vs ctypes {C.sizeof(mirror)} B")
     lib.kai0_attn_decode_workspace_bytes.restype = c_i64

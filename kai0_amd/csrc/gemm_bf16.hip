@@ -255,6 +255,14 @@ __device__ __forceinline__ void epilogue8(const GemmArgs& p, float (&v)[8], int 
 
 #define N_ALIGNED8(n) (((n) & 7) == 0)
 
+// The ONE statement of when a 256 x 256 launch takes the store-with-little-else epilogue (act 0 / 1, optional bias / residual / column
+// routing / accumulation; no gate, f32 output, scale, output row map or split-K): the tile kernel, the persistent kernel and the
+// host's gemm_select (kai0_gemm_plan_t.simple_epilogue) all expand it.  `scale` is the normalised one (0 -> 1).  A macro, not a
+// function: its operands are evaluated lazily, left to right, exactly as the kernels' own expression was — a function (inlined or
+// not) makes hipcc allocate the 256 x 256 kernels' registers differently.
+#define SIMPLE_EPILOGUE_APPLIES(simple_epi, act, split_k, gate, out_f32, scale, c_rpb, n) \
+    ((simple_epi) && (act) <= 1 && (split_k) == 1 && (gate) == nullptr && !(out_f32) && (scale) == 1.0f && (c_rpb) == 0 && (N_ALIGNED8(n)))
+
 // block barrier that does NOT drain the LDS-DMA queue behind the compiler's back: the kernel places its own vmcnt.
 __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_sched_barrier(0);  // keep register-only MFMAs on their side of the barrier (they ignore "memory")
@@ -763,8 +771,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
     // optional accumulation into the bf16 destination; no gate / f32 output / scale / row map) without the general path's per-row checks of everything else — measured in
     // the persistent kernel: 9.7 -> 4.6 us per tile for a plain store (profiles/r05_gemm_persistent_phases.txt).  Same order and rounding
     // points as epilogue8; kai0_gemm_desc.general_epilogue = 1 sends these launches through the general path (tests).
-    const bool simple_fast = MT == 8 && p.simple_epi && p.act <= 1 && p.split_k == 1 && p.gate == nullptr && !p.out_f32 && p.scale == 1.0f &&
-                             p.cmap.rpb == 0 && (N_ALIGNED8(p.N));
+    const bool simple_fast = MT == 8 && SIMPLE_EPILOGUE_APPLIES(p.simple_epi, p.act, p.split_k, p.gate, p.out_f32, p.scale, p.cmap.rpb, p.N);
     auto epi_half = [&](auto hc) {
         constexpr int h = decltype(hc)::value;
         if constexpr (((MT == 4 && WM == 2) || (MT == 2 && WM == 4)) && WN == 2 && A_KC && B_KC) if (p.act == 7) {
@@ -1401,8 +1408,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
         const bool fused_fast = p.act >= 2 && p.act <= 5 && p.bias == nullptr && p.gate == nullptr && p.residual == nullptr && !p.accumulate &&
                                 !p.out_f32 && p.nseg == 0 && (p.act == 4 || p.scale == 1.0f) && (p.act != 3 || p.pre_out != nullptr);
         // (the same predicate as the tile kernel's; split_k == 1 is also what the host requires of a persistent launch)
-        const bool simple_fast = p.simple_epi && p.act <= 1 && p.split_k == 1 && p.gate == nullptr && !p.out_f32 && p.scale == 1.0f && p.cmap.rpb == 0 &&
-                                 (N_ALIGNED8(p.N));
+        const bool simple_fast = SIMPLE_EPILOGUE_APPLIES(p.simple_epi, p.act, p.split_k, p.gate, p.out_f32, p.scale, p.cmap.rpb, p.N);
         auto to_slab = [&](int ti) {  // MFMA row-tile ti of the wave's sub-tile (16 rows x 64 columns) -> slab
             __builtin_amdgcn_wave_barrier();
             // (static indexing of acc: callers pass compile-time ti through the unrolled loops below)
@@ -1837,7 +1843,8 @@ KAI0_API int kai0_debug_ps_trace(long long* host_out) {
 }
 #endif
 
-KAI0_API int kai0_gemm_bf16(const kai0_gemm_desc* d, kai0_stream_t stream) {
+// Everything kai0_gemm_bf16 refuses, checked on the descriptor alone (no device call): shared by the launch and by kai0_gemm_plan.
+static int gemm_validate(const kai0_gemm_desc* d) {
     KAI0_REQUIRE(d != nullptr, "kai0_gemm_bf16: null descriptor");
     KAI0_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "kai0_gemm_bf16: empty problem M=%d N=%d K=%d", d->M, d->N,
                  d->K);
@@ -1908,6 +1915,79 @@ KAI0_API int kai0_gemm_bf16(const kai0_gemm_desc* d, kai0_stream_t stream) {
                      "kai0_gemm_bf16: an operand spans more than 2 GiB per batch entry (A %lld rows, B %lld rows)",
                      (long long)a_rows, (long long)b_rows);
     }
+    if (d->split_k > 1) {
+        const int batch = d->batch > 0 ? d->batch : 1;
+        KAI0_REQUIRE(d->workspace != nullptr && d->workspace_bytes >= (int64_t)batch * d->split_k * d->M * d->N * 4,
+                     "kai0_gemm_bf16: split_k=%d needs a workspace of batch*split*M*N*4 bytes", d->split_k);
+        KAI0_REQUIRE((d->N % 8) == 0, "kai0_gemm_bf16: split_k needs N %% 8 == 0");
+    }
+    return 0;
+}
+
+// The ONE place that decides which kernel a (valid) descriptor gets: the launch below switches on its result and kai0_gemm_plan
+// reports it.  Pure host arithmetic on the descriptor.
+static kai0_gemm_plan_t gemm_select(const kai0_gemm_desc* d) {
+    kai0_gemm_plan_t pl{};
+    const int batch = d->batch > 0 ? d->batch : 1;
+    const int split = d->split_k > 1 ? d->split_k : 1;
+    const int N = d->act == 6 ? 2 * d->N : d->N;  // act 6: logical width = gate | up interleaved
+    const int k_chunk = split > 1 ? ((d->K + split - 1) / split + BK - 1) / BK * BK : d->K;
+    // tile configuration: 256x256 (1 block of 8 waves per CU, half the staged bytes per FLOP) when the problem gives
+    // (nearly) every CU a block; 128x128 (2 blocks per CU) for small problems.
+    const int64_t big_tiles = (int64_t)((d->M + 255) / 256) * ((N + 255) / 256) * batch * split;
+    const bool big = d->act != 7 && big_tiles >= 160 && d->K >= 256;  // (act 7: 128-column tiles)
+    // few 128x128 tiles (at most one block per CU): nothing else hides the load latency -> 4-stage pipeline
+    const int64_t small_blocks = (int64_t)((d->M + 127) / 128) * ((N + 127) / 128) * batch * split;
+    const bool deep = small_blocks <= 256 && k_chunk >= 256;
+    // 128 x 128 on EIGHT waves (4 x 2 wave tiles of 32 x 64; round 6): with at most one block per CU the four-wave loop has one wave per
+    // SIMD, so a K-tile is that wave's 8 LDS-DMA issues + 16 fragment reads + 32 MFMAs one after the other (~1470 clocks for 544 of MFMA);
+    // two waves per SIMD let one wave's MFMAs run under the other's DMA issue and read latency.  K-contiguous operands, act 0 / 1 / 7 (the
+    // epilogues the narrower wave tile implements); kai0_gemm_desc.small_w8: 0 = this rule, 1 = never, 2 = every eligible 128 x 128 launch.
+    const bool w8 = !big && d->a_kc && d->b_kc && (d->act <= 1 || d->act == 7) && (d->small_w8 == 2 || (d->small_w8 == 0 && deep));
+    // persistent NT kernel with the dynamic tile queue (kai0_gemm_desc.persist: 0 = the rule below, 1 = never, 2 = every eligible NT launch)
+    const int persist = d->persist == 1 ? 0 : (d->persist == 2 ? 2 : 1);
+    const bool ps_ok = persist && big && d->a_kc && d->b_kc && batch == 1 && split == 1 &&
+                       big_tiles >= (persist == 2 ? 512 : 2048) &&  // (B = 1 prefix MLP, 512 tiles = two per CU: 97 -> 136 us persistent)
+                       (d->K % 8) == 0 && !d->rowvec && d->a_rpb == 0 && d->b_rpb == 0;
+    // the rule (measured inside the training step with KAI0_GEMM_BREAKDOWN=1, round 4): the wide MLP shapes gain — 30976 x 16384 x 2048 with the GeGLU
+    // epilogues 993 -> 1046 TFLOP/s (1056 -> 1165 for the pair GEMM alone), x 2048 x 16384 1371 -> 1385 — while launches of < ~1000
+    // tiles (q|k|v, o_proj, SigLIP) lose 1-8 %: their tiles are too few for the queue to pay for its hand-over
+    const bool ps_rule = N >= 8192 || d->K >= 8192;
+    // 256 x 256 by layout (measured on the MLP shapes, random data): NT runs the quadrant schedule (+6..10 % over a two-buffer
+    // ping-pong, 1.37 PFLOP/s at 8192^3); TN (weight gradients: 512-B source rows, so a 32-deep sub-tile still moves whole cache
+    // lines) the 32-deep ring (+21 %; it loses up to 17 % for NT, whose 64-B source rows are half lines); the layouts with one
+    // transposed operand the plain two-stage loop (a ping-pong loses there: their load slot is longer than the MFMA slot).  Act 6 (NT
+    // only) selects its second weight per DMA piece of a 64-deep K-tile.  Removed after measurement: a 384x256 plain tile (equal to
+    // the ping-pong, spilled), the quadrant schedule with its DMA pieces between the MFMAs, the ring with two pieces per slot kind
+    // (-0.9 %), the two-buffer ping-pong, two blocks per CU (round 6: 128 x 128 on eight waves x 2 stages, 256 x 128 x 32 x 3 stages).
+    pl.tile = big ? 256 : 128;
+    pl.waves = big || w8 ? 8 : 4;
+    if (ps_ok && (persist == 2 || ps_rule)) pl.loop = KAI0_GEMM_LOOP_PERSISTENT;
+    else if (big && d->a_kc && d->b_kc) pl.loop = KAI0_GEMM_LOOP_QUADRANT;
+    else if (big && !d->a_kc && !d->b_kc) pl.loop = KAI0_GEMM_LOOP_RING;
+    else if (big) pl.loop = KAI0_GEMM_LOOP_PLAIN2;
+    else if (w8 || deep) pl.loop = KAI0_GEMM_LOOP_PLAIN4;
+    else pl.loop = KAI0_GEMM_LOOP_PLAIN2;
+    pl.tiles_m = (d->M + pl.tile - 1) / pl.tile;
+    pl.tiles_n = (N + pl.tile - 1) / pl.tile;
+    pl.k_chunk = k_chunk;
+    // the kernels' own condition, on the values the launch hands them (GemmArgs: simple_epi, the normalised scale, the logical width)
+    pl.simple_epilogue = big && SIMPLE_EPILOGUE_APPLIES(d->general_epilogue == 0, d->act, split, d->gate, d->out_f32,
+                                                        (d->scale == 0.0f ? 1.0f : d->scale), d->c_rpb, N);
+    return pl;
+}
+
+KAI0_API int kai0_gemm_plan_size(void) { return (int)sizeof(kai0_gemm_plan_t); }
+
+KAI0_API int kai0_gemm_plan(const kai0_gemm_desc* d, kai0_gemm_plan_t* out) {
+    KAI0_REQUIRE(out != nullptr, "kai0_gemm_plan: null result");
+    if (int rc = gemm_validate(d)) return rc;
+    *out = gemm_select(d);
+    return 0;
+}
+
+KAI0_API int kai0_gemm_bf16(const kai0_gemm_desc* d, kai0_stream_t stream) {
+    if (int rc = gemm_validate(d)) return rc;
     const int batch = d->batch > 0 ? d->batch : 1;
     GemmArgs p;
     p.A = (const bf16_t*)d->A;
@@ -1958,42 +2038,15 @@ KAI0_API int kai0_gemm_bf16(const kai0_gemm_desc* d, kai0_stream_t stream) {
         p.seg_ld[i] = i < d->nseg ? d->seg[i].ld : 0;
         p.seg_begin[i] = i < d->nseg ? d->seg[i].n_begin : 0;
     }
-    p.split_k = 1;
-    p.k_chunk = d->K;
+    const kai0_gemm_plan_t pl = gemm_select(d);
     const int split = d->split_k > 1 ? d->split_k : 1;
-    p.ws = nullptr;
-    if (split > 1) {
-        KAI0_REQUIRE(d->workspace != nullptr && d->workspace_bytes >= (int64_t)batch * split * d->M * d->N * 4,
-                     "kai0_gemm_bf16: split_k=%d needs a workspace of batch*split*M*N*4 bytes", split);
-        KAI0_REQUIRE((d->N % 8) == 0, "kai0_gemm_bf16: split_k needs N %% 8 == 0");
-        p.split_k = split;
-        p.k_chunk = ((d->K + split - 1) / split + BK - 1) / BK * BK;
-        p.ws = (float*)d->workspace;
-    }
-    // tile configuration: 256x256 (1 block of 8 waves per CU, half the staged bytes per FLOP) when the problem gives
-    // (nearly) every CU a block; 128x128 (2 blocks per CU) for small problems.
-    const int64_t big_tiles = (int64_t)((d->M + 255) / 256) * ((p.N + 255) / 256) * batch * (split > 1 ? split : 1);
-    const bool big = d->act != 7 && big_tiles >= 160 && d->K >= 256;  // (act 7: 128-column tiles)
+    p.split_k = split;
+    p.k_chunk = pl.k_chunk;
+    p.ws = split > 1 ? (float*)d->workspace : nullptr;
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    // few 128x128 tiles (at most one block per CU): nothing else hides the load latency -> 4-stage pipeline
-    const int64_t small_blocks = (int64_t)((d->M + 127) / 128) * ((p.N + 127) / 128) * batch * (split > 1 ? split : 1);
-    const bool deep = small_blocks <= 256 && p.k_chunk >= 256;
-    // 128 x 128 on EIGHT waves (4 x 2 wave tiles of 32 x 64; round 6): with at most one block per CU the four-wave loop has one wave per
-    // SIMD, so a K-tile is that wave's 8 LDS-DMA issues + 16 fragment reads + 32 MFMAs one after the other (~1470 clocks for 544 of MFMA);
-    // two waves per SIMD let one wave's MFMAs run under the other's DMA issue and read latency.  K-contiguous operands, act 0 / 1 / 7 (the
-    // epilogues the narrower wave tile implements); kai0_gemm_desc.small_w8: 0 = this rule, 1 = never, 2 = every eligible 128 x 128 launch.
-    const bool w8 = !big && d->a_kc && d->b_kc && (d->act <= 1 || d->act == 7) && (d->small_w8 == 2 || (d->small_w8 == 0 && deep));
-    // persistent NT kernel with the dynamic tile queue (kai0_gemm_desc.persist: 0 = the rule below, 1 = never, 2 = every eligible NT launch)
-    const int persist = d->persist == 1 ? 0 : (d->persist == 2 ? 2 : 1);
-    const bool ps_ok = persist && big && d->a_kc && d->b_kc && batch == 1 && split == 1 &&
-                       big_tiles >= (persist == 2 ? 512 : 2048) &&  // (B = 1 prefix MLP, 512 tiles = two per CU: 97 -> 136 us persistent)
-                       (p.K % 8) == 0 && !d->rowvec && d->a_rpb == 0 && d->b_rpb == 0;
-    // the rule (measured inside the training step with KAI0_GEMM_BREAKDOWN=1, round 4): the wide MLP shapes gain — 30976 x 16384 x 2048 with the GeGLU
-    // epilogues 993 -> 1046 TFLOP/s (1056 -> 1165 for the pair GEMM alone), x 2048 x 16384 1371 -> 1385 — while launches of < ~1000
-    // tiles (q|k|v, o_proj, SigLIP) lose 1-8 %: their tiles are too few for the queue to pay for its hand-over
-    const bool ps_rule = p.N >= 8192 || d->K >= 8192;
-    if (ps_ok && (persist == 2 || ps_rule)) {
+    if (pl.loop == KAI0_GEMM_LOOP_PERSISTENT) {
+        const int64_t big_tiles = (int64_t)pl.tiles_m * pl.tiles_n;  // (one batch entry, no split)
         constexpr int LDS = 2 * 2 * 256 * 64 * 2 + 8 * 4096;  // two stages + the epilogue slabs = 160 KiB
         // per device: the counters' address (a __device__ symbol has one instance per device), the kernel's LDS attribute, the CU count
         struct PsDev { unsigned int* ctr = nullptr; int cus = 0; };
@@ -2020,18 +2073,11 @@ KAI0_API int kai0_gemm_bf16(const kai0_gemm_desc* d, kai0_stream_t stream) {
         hipLaunchKernelGGL(gemm_nt_persistent_kernel, dim3(nblk), dim3(512), LDS, s, p, ctr);
         return kai0_check_launch("kai0_gemm_bf16 (persistent)");
     }
-    // 256 x 256 by layout (measured on the MLP shapes, random data): NT runs the quadrant schedule (+6..10 % over a two-buffer
-    // ping-pong, 1.37 PFLOP/s at 8192^3); TN (weight gradients: 512-B source rows, so a 32-deep sub-tile still moves whole cache
-    // lines) the 32-deep ring (+21 %; it loses up to 17 % for NT, whose 64-B source rows are half lines); the layouts with one
-    // transposed operand the plain two-stage loop (a ping-pong loses there: their load slot is longer than the MFMA slot).  Act 6 (NT
-    // only) selects its second weight per DMA piece of a 64-deep K-tile.  Removed after measurement: a 384x256 plain tile (equal to
-    // the ping-pong, spilled), the quadrant schedule with its DMA pieces between the MFMAs, the ring with two pieces per slot kind
-    // (-0.9 %), the two-buffer ping-pong, two blocks per CU (round 6: 128 x 128 on eight waves x 2 stages, 256 x 128 x 32 x 3 stages).
-    if (big && d->a_kc && d->b_kc) rc = launch_cfg<L_NT, 2, 4, 8, 4, true, 2, 64, 1>(d, p, batch, s);
-    else if (big && !d->a_kc && !d->b_kc) rc = launch_cfg<L_TN, 2, 4, 8, 4, true, 4, 32, 3>(d, p, batch, s);
-    else if (big) rc = launch_cfg<L_NN | L_TT, 2, 4, 8, 4, false>(d, p, batch, s);
-    else if (w8) rc = launch_cfg<L_NT, 4, 2, 2, 4, false, 4>(d, p, batch, s);
-    else if (deep) rc = launch_cfg<L_ALL, 2, 2, 4, 4, false, 4>(d, p, batch, s);
+    if (pl.tile == 256 && pl.loop == KAI0_GEMM_LOOP_QUADRANT) rc = launch_cfg<L_NT, 2, 4, 8, 4, true, 2, 64, 1>(d, p, batch, s);
+    else if (pl.tile == 256 && pl.loop == KAI0_GEMM_LOOP_RING) rc = launch_cfg<L_TN, 2, 4, 8, 4, true, 4, 32, 3>(d, p, batch, s);
+    else if (pl.tile == 256) rc = launch_cfg<L_NN | L_TT, 2, 4, 8, 4, false>(d, p, batch, s);
+    else if (pl.waves == 8) rc = launch_cfg<L_NT, 4, 2, 2, 4, false, 4>(d, p, batch, s);
+    else if (pl.loop == KAI0_GEMM_LOOP_PLAIN4) rc = launch_cfg<L_ALL, 2, 2, 4, 4, false, 4>(d, p, batch, s);
     else rc = launch_cfg<L_ALL, 2, 2, 4, 4, false>(d, p, batch, s);
     if (rc) return rc;
     rc = kai0_check_launch("kai0_gemm_bf16");

@@ -78,9 +78,12 @@ def gemm(
     accumulate: bool = False, a_off_elems: int = 0, b_off_elems: int = 0, c_off_elems: int = 0, split_k: int = 1,
     aux1: torch.Tensor | None = None, aux2: torch.Tensor | None = None, segs=None, rowvec=None, rv=(0, 0, 1),
     B2: torch.Tensor | None = None, pre_out2: torch.Tensor | None = None, norm=None, nt_out: bool = False, rope=None,
+    _plan: "_lib.GemmPlan | None" = None,
 ) -> torch.Tensor:  # fmt: skip
     """kai0_gemm_bf16. `*_map` = (rows_per_batch, batch_stride_rows, row_offset). `*_off_elems` shift the base
-    pointer (for column slices such as a head inside a fused projection)."""
+    pointer (for column slices such as a head inside a fused projection).  `_plan` (gemm_plan's): fill it with kai0_gemm_plan's
+    answer for this descriptor instead of launching — the ONE place that builds a kai0_gemm_desc, so the launch and the plan
+    cannot drift (and the launch path pays no extra call for it)."""
     for t in (A, B, out):
         if not t.is_cuda:
             raise _lib.Kai0HipError("gemm: expected CUDA (HIP) tensors; the product path has no CPU fallback")
@@ -141,7 +144,9 @@ def gemm(
         d.nseg = len(segs)
         for i, (dst, ld, nb) in enumerate(segs):
             d.seg[i].dst, d.seg[i].ld, d.seg[i].n_begin = dst.data_ptr(), ld, nb
-    if split_k > 1:
+    if split_k > 1 and _plan is not None:  # a plan follows no pointer: name the size the launch would allocate, allocate nothing
+        d.split_k, d.workspace, d.workspace_bytes = split_k, d.A, batch * split_k * M * N * 4
+    elif split_k > 1:
         ws = _workspace(batch * split_k * M * N * 4, A.device)
         d.split_k, d.workspace, d.workspace_bytes = split_k, ws.data_ptr(), ws.numel()
     if norm is not None:  # (kind, norm_out, weight, bias | None, eps): the consumer's norm, fused into the split-K reduction
@@ -153,8 +158,21 @@ def gemm(
             _chk(nb, BF16, "gemm: norm bias")
             d.norm_b = nb.data_ptr()
     d.persist, d.general_epilogue, d.small_w8 = GEMM_TUNING["persist"], GEMM_TUNING["general_epilogue"], GEMM_TUNING["small_w8"]
+    if _plan is not None:
+        _lib.call("kai0_gemm_plan", C.byref(d), C.byref(_plan))
+        return out
     _lib.call("kai0_gemm_bf16", C.byref(d), _stream())
     return out
+
+
+def gemm_plan(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, **kw) -> dict:
+    """kai0_gemm_plan for exactly the descriptor `gemm(A, B, out, **kw)` would launch (the GEMM_TUNING hooks included): which tile,
+    wave count and K loop the library selects, its tile counts, the split-K chunk and whether the simple epilogue applies.  Launches
+    nothing."""
+    pl = _lib.GemmPlan()
+    gemm(A, B, out, _plan=pl, **kw)
+    return {"tile": pl.tile, "waves": pl.waves, "loop": _lib.GEMM_LOOPS[pl.loop], "tiles_m": pl.tiles_m, "tiles_n": pl.tiles_n,
+            "k_chunk": pl.k_chunk, "simple_epilogue": bool(pl.simple_epilogue)}
 
 
 def skinny_split_k(N: int, K: int) -> int:

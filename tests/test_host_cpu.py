@@ -246,6 +246,33 @@ def test_cabi_v2_exports_every_declared_symbol():
     assert ctypes.sizeof(_lib.GemmDesc) == lib.kai0_gemm_desc_size()
 
 
+def test_gemm_plan_needs_no_device():
+    """kai0_gemm_plan validates and selects on the descriptor alone: it runs here, without a GPU, on pointers it never follows —
+    160 batch entries of a 200 x 136 x 264 problem get the 256 x 256 quadrant kernel, 159 the 128 x 128 tile, a bad descriptor the
+    launch's own error."""
+    import ctypes
+
+    from kai0_amd import _lib
+
+    lib = _lib.load()
+    assert lib.kai0_gemm_plan_size() == ctypes.sizeof(_lib.GemmPlan)
+    d = _lib.GemmDesc()
+    d.A = d.B = d.C = 0x10000
+    d.M, d.N, d.K, d.a_kc, d.b_kc = 200, 136, 264, 1, 1
+    d.lda = d.ldb = 264
+    d.ldc = 136
+    d.batch, d.batch_inner = 160, 8
+    d.persist = 1
+    pl = _lib.GemmPlan()
+    assert lib.kai0_gemm_plan(ctypes.byref(d), ctypes.byref(pl)) == 0
+    assert (pl.tile, pl.waves, _lib.GEMM_LOOPS[pl.loop], pl.tiles_m, pl.tiles_n, pl.k_chunk, pl.simple_epilogue) == (256, 8, "quadrant", 1, 1, 264, 1)
+    d.batch = 159
+    assert lib.kai0_gemm_plan(ctypes.byref(d), ctypes.byref(pl)) == 0
+    assert (pl.tile, pl.waves, _lib.GEMM_LOOPS[pl.loop], pl.tiles_m, pl.tiles_n, pl.simple_epilogue) == (128, 4, "plain2", 2, 2, 0)
+    d.lda = 260
+    assert lib.kai0_gemm_plan(ctypes.byref(d), ctypes.byref(pl)) != 0 and b"multiples of 8" in lib.kai0_last_error()
+
+
 def test_cabi_version_mismatch_is_rejected(monkeypatch):
     """_lib.load() refuses a library whose kai0_abi_version() differs from the version the binding's mirrors describe."""
     from kai0_amd import _lib

@@ -6,6 +6,8 @@ import math
 import pytest
 import torch
 
+import gemm_refs
+
 pytestmark = pytest.mark.gpu
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -42,6 +44,16 @@ def assert_close_bf16(out, ref, tol=6e-3, what=""):
     assert rel_err(out, ref) < 4e-3, f"{what}: rel-L2 {rel_err(out, ref):.3e}"
 
 
+def assert_gemm_within(out, a, b, what="", **epi):
+    """kai0_gemm_bf16 output against the float64 product of the LOGICAL operands a [.., M, K], b [.., K, N] and the linear epilogue
+    `epi` (tests/gemm_refs.py): every element inside the derived bound, none exempt.  Used NEXT TO assert_close_bf16, not instead of
+    it: the bound's accumulation term K * 2^-23 * |A||B| grows like K^2, so it is the stricter check up to K of a few thousand (no
+    outlier share, one bf16 rounding per element) and the looser one beyond (K = 24576 / 30976 split-K), where the rel-L2 and the
+    6e-3 tolerance of assert_close_bf16 bind."""
+    ref, bound = gemm_refs.reference(a, b, **epi)
+    return gemm_refs.assert_within(out.reshape(ref.shape), ref, bound, what)
+
+
 # --------------------------------------------------------------------------------------------------- GEMM
 GEMM_SHAPES = [
     (128, 128, 64),
@@ -59,8 +71,8 @@ GEMM_SHAPES = [
 def test_gemm_nt(ops, M, N, K):
     x, w = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=0.05)
     out = ops.linear_fwd(x, w)
-    ref = x.float() @ w.float().t()
-    assert_close_bf16(out, ref, what=f"NT {M}x{N}x{K}")
+    assert_close_bf16(out, x.float() @ w.float().t(), what=f"NT {M}x{N}x{K}")
+    assert_gemm_within(out, x, w.t(), what=f"NT {M}x{N}x{K}")
 
 
 def test_gemm_nt_is_not_transposed(ops):
@@ -79,6 +91,7 @@ def test_gemm_nn(ops, M, N, K):
     out = torch.empty((M, N), dtype=BF16, device=dev())
     ops.gemm(a, b, out, M=M, N=N, K=K, a_kc=True, b_kc=False, lda=K, ldb=N, ldc=N)
     assert_close_bf16(out, a.float() @ b.float(), what=f"NN {M}x{N}x{K}")
+    assert_gemm_within(out, a, b, what=f"NN {M}x{N}x{K}")
 
 
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (256, 384, 500), (136, 72, 1000), (2048, 256, 3872), (72, 256, 264)])
@@ -88,6 +101,7 @@ def test_gemm_tn(ops, M, N, K):
     out = torch.empty((M, N), dtype=BF16, device=dev())
     ops.gemm(a, b, out, M=M, N=N, K=K, a_kc=False, b_kc=False, lda=M, ldb=N, ldc=N)
     assert_close_bf16(out, a.float().t() @ b.float(), what=f"TN {M}x{N}x{K}")
+    assert_gemm_within(out, a.t(), b, what=f"TN {M}x{N}x{K}")
 
 
 @pytest.mark.parametrize("lay,M,N,K,S", [("TN", 256, 2048, 30976, 8), ("TN", 1152, 1152, 24576, 6), ("NT", 136, 264, 4104, 3),
@@ -101,6 +115,7 @@ def test_gemm_split_k(ops, lay, M, N, K, S):
     A = a.float() if a_kc else a.float().t()
     Bm = b.float().t() if b_kc else b.float()
     assert_close_bf16(out, A @ Bm, what=f"split-K {lay} {M}x{N}x{K}/{S}")
+    assert_gemm_within(out, a if a_kc else a.t(), b.t() if b_kc else b, what=f"split-K {lay} {M}x{N}x{K}/{S}")
     assert ops.pick_split_k(256, 2048, 30976) > 1 and ops.pick_split_k(16384, 2048, 30976) == 1
 
 
@@ -117,9 +132,11 @@ def test_gemm_split_k_full_epilogue(ops):
         ops.gemm(x, w, out, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, bias=bias, residual=res, ldr=N, gate=gate, gate_rpb=rpb,
                  gate_ld=N, split_k=S)
         assert_close_bf16(out, ref, what=f"split {S} epilogue")
+        assert_gemm_within(out, x, w.t(), what=f"split {S} epilogue", bias=bias, gate=gate.repeat_interleave(rpb, 0), residual=res)
     buf = torch.zeros((B, S_ld, N), dtype=BF16, device=dev())
     ops.gemm(x, w, buf, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, c_map=(rpb, S_ld, row0), split_k=5)
     assert_close_bf16(buf[:, row0 : row0 + rpb].reshape(M, N), x.float() @ w.float().t(), what="split + c_map")
+    assert_gemm_within(buf[:, row0 : row0 + rpb], x, w.t(), what="split + c_map")
 
 
 def test_gemm_tn_a_only(ops):
@@ -129,6 +146,7 @@ def test_gemm_tn_a_only(ops):
     out = torch.empty((M, N), dtype=BF16, device=dev())
     ops.gemm(a, b, out, M=M, N=N, K=K, a_kc=False, b_kc=True, lda=M, ldb=K, ldc=N)
     assert_close_bf16(out, a.float().t() @ b.float().t(), what="TN(a only)")
+    assert_gemm_within(out, a.t(), b.t(), what="TN(a only)")
 
 
 def test_gemm_epilogue_bias_gelu_residual(ops):
@@ -165,20 +183,20 @@ def test_gemm_row_remaps_and_batch(ops):
     x, w = rnd(B * rows, K, seed=1), rnd(N, K, seed=2, scale=0.1)
     buf = torch.zeros((B, S_ld, N), dtype=BF16, device=dev())
     ops.gemm(x, w, buf, M=B * rows, N=N, K=K, lda=K, ldb=K, ldc=N, c_map=(rows, S_ld, row0))
-    ref = (x.float() @ w.float().t()).view(B, rows, N)
-    assert_close_bf16(buf[:, row0 : row0 + rows], ref, what="c_map")
+    assert_close_bf16(buf[:, row0 : row0 + rows], (x.float() @ w.float().t()).view(B, rows, N), what="c_map")
+    assert_gemm_within(buf[:, row0 : row0 + rows], x, w.t(), what="c_map")
     assert float(buf[:, :row0].abs().max()) == 0.0 and float(buf[:, row0 + rows :].abs().max()) == 0.0
     w2 = rnd(K, N, seed=3, scale=0.1)  # [N2=K, K2=N]
     out = torch.empty((B * rows, K), dtype=BF16, device=dev())
     ops.gemm(buf, w2, out, M=B * rows, N=K, K=N, lda=N, ldb=N, ldc=K, a_map=(rows, S_ld, row0))
-    ref2 = buf[:, row0 : row0 + rows].reshape(B * rows, N).float() @ w2.float().t()
-    assert_close_bf16(out, ref2, what="a_map")
+    assert_close_bf16(out, buf[:, row0 : row0 + rows].reshape(B * rows, N).float() @ w2.float().t(), what="a_map")
+    assert_gemm_within(out, buf[:, row0 : row0 + rows].reshape(B * rows, N), w2.t(), what="a_map")
     # TN with a remapped contraction index
     g = rnd(B * rows, K, seed=4)
     dw = torch.empty((N, K), dtype=BF16, device=dev())
     ops.gemm(buf, g, dw, M=N, N=K, K=B * rows, a_kc=False, b_kc=False, lda=N, ldb=K, ldc=K, a_map=(rows, S_ld, row0))
-    ref3 = buf[:, row0 : row0 + rows].reshape(B * rows, N).float().t() @ g.float()
-    assert_close_bf16(dw, ref3, what="a_map on contraction rows")
+    assert_close_bf16(dw, buf[:, row0 : row0 + rows].reshape(B * rows, N).float().t() @ g.float(), what="a_map on contraction rows")
+    assert_gemm_within(dw, buf[:, row0 : row0 + rows].reshape(B * rows, N).t(), g, what="a_map on contraction rows")
     # batched heads: q [n, S, NH*HD] x k -> scores [n*NH, S, S]
     n, S, NH, HD = 2, 16, 4, 72
     E = NH * HD
@@ -186,9 +204,10 @@ def test_gemm_row_remaps_and_batch(ops):
     sc = torch.empty((n * NH, S, S), dtype=BF16, device=dev())
     ops.gemm(q, k, sc, M=S, N=S, K=HD, lda=E, ldb=E, ldc=S, batch=n * NH, batch_inner=NH, sA=(S * E, HD), sB=(S * E, HD),
              sC=(NH * S * S, S * S))
-    qh = q.view(n, S, NH, HD).permute(0, 2, 1, 3).float()
-    kh = k.view(n, S, NH, HD).permute(0, 2, 1, 3).float()
-    assert_close_bf16(sc.view(n, NH, S, S), qh @ kh.transpose(-1, -2), what="two-level batch")
+    qh = q.view(n, S, NH, HD).permute(0, 2, 1, 3)
+    kh = k.view(n, S, NH, HD).permute(0, 2, 1, 3)
+    assert_close_bf16(sc.view(n, NH, S, S), qh.float() @ kh.float().transpose(-1, -2), what="two-level batch")
+    assert_gemm_within(sc.view(n, NH, S, S), qh, kh.transpose(-1, -2), what="two-level batch")
 
 
 def test_gemm_batch_strides_may_be_negative_or_span_two_allocations(ops):
@@ -253,6 +272,7 @@ def test_gemm_n_not_multiple_of_8(ops):
     out = torch.full((M, ld), 7.0, dtype=BF16, device=dev())
     ops.gemm(a, b, out, M=M, N=N, K=K, lda=K, ldb=K, ldc=ld)
     assert_close_bf16(out[:, :N], a.float() @ b.float().t(), what="N=20")
+    assert_gemm_within(out[:, :N], a, b.t(), what="N=20")
     assert float(out[:, N:].abs().max()) == 0.0
 
 
@@ -1210,6 +1230,8 @@ def test_simple_epilogue_fast_path_equals_the_general_epilogue(ops, case, persis
                 dst = [torch.full((M, w), 3.0, dtype=BF16, device=dev()) for w in (N // 2, N // 4, N // 4)]
                 k2["segs"] = [(dst[0], N // 2, 0), (dst[1], N // 4, N // 2), (dst[2], N // 4, 3 * N // 4)]
                 outs = outs + dst
+            loop = ops.gemm_plan(A, W, outs[0], M=M, N=N, K=K, ldc=N, **lay, **k2)["loop"]
+            assert (loop == "persistent") == (persist == 2 and case not in ("batched", "tn")), f"{case}, persist={persist}: the library plans {loop}"
             ops.gemm(A, W, outs[0], M=M, N=N, K=K, ldc=N, **lay, **k2)
             torch.cuda.synchronize()
             res[simple] = outs
@@ -1217,6 +1239,9 @@ def test_simple_epilogue_fast_path_equals_the_general_epilogue(ops, case, persis
         assert torch.equal(a, b)
     if case == "plain":
         assert rel_err(res[1][0], A.float() @ W.float().t()) < 5e-3
+        assert_gemm_within(res[1][0], A, W.t(), what=f"plain, persist={persist}")  # (persist 2: the persistent kernel, on the f64 bound)
+    if case == "ragged_rows":
+        assert_gemm_within(res[1][0], A, W.t(), what=f"ragged rows, persist={persist}", bias=kw["bias"], residual=kw["residual"])
     if case == "routed":
         assert not torch.equal(res[1][1], torch.full_like(res[1][1], 3.0))  # the routed destinations were written
 
@@ -1301,14 +1326,17 @@ def test_persistent_gemm_is_bit_identical_to_one_block_per_tile(ops, case):
                 k2["pre_out"] = outs[1]
             if nout >= 3:
                 k2["pre_out2"] = outs[2]
+            plan = ops.gemm_plan(A, W, outs[0], M=M, N=N, K=K, lda=K, ldb=K, ldc=N, **k2)
+            assert (plan["tile"], plan["loop"]) == (256, "persistent" if mode == 2 else "quadrant"), f"{case}, persist={mode}: the library plans {plan}"
             ops.gemm(A, W, outs[0], M=M, N=N, K=K, lda=K, ldb=K, ldc=N, **k2)
             torch.cuda.synchronize()
             res[mode] = outs
     for a, b in zip(res[0], res[2]):
         assert torch.equal(a, b)
-    ref = A.float() @ W.float().t()  # and it is the right product (plain case: against fp32)
-    if case == "plain":
-        assert rel_err(res[2][0], ref) < 5e-3
+    if case == "plain":  # and it is the right product: against fp32, and element by element on the f64 bound
+        assert rel_err(res[2][0], A.float() @ W.float().t()) < 5e-3
+    if case in ("plain", "ragged"):
+        assert_gemm_within(res[2][0], A, W.t(), what=f"persistent {case}")
 
 
 @pytest.mark.parametrize("B", [1, 2])
