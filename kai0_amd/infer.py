@@ -18,7 +18,10 @@ MI355X-first choices:
     (torch.cuda.CUDAGraph on ROCm is hipGraph) and replayed per request: no per-op Python or launch cost;
   * pi0 (`pi05=False`): `state` is a request input (a static buffer of the graph), the suffix has Hs + 1 rows per
     sample (state token | action tokens, mask codes 0 / 1 / 2), the time half of `action_time_mlp_in` is hoisted per step like the
-    modulation table, and the expert's plain RMSNorms run through the same folded stack as the constant modulation [w | 0 | 1].
+    modulation table, and the expert's plain RMSNorms run through the same folded stack as the constant modulation [w | 0 | 1];
+  * real-time chunking: a request with a previous chunk runs the guided loop `_run_guided` — per Euler step one
+    forward of the generic per-layer step that keeps what its backward needs, an explicit reverse sweep over the training backward's
+    entry points (`_denoiser_vjp`) and two f32 seam kernels — captured into a hipGraph of its own; the unguided graph is not touched.
 """
 
 from __future__ import annotations
@@ -120,6 +123,10 @@ class InferenceEngine:
         self._graph_steps = None
         self._static_in = None
         self._static_out = None
+        # real-time chunking: the guided chunk's own graph and static buffers (sample_actions_guided)
+        self._guided_mods = {}
+        self._g_prev = self._g_w = None
+        self._g_graph = self._g_graph_key = self._g_static_in = self._g_static_out = None
         self._content_init()
 
     def compatible(self, batch, n_lang, n_cam):
@@ -347,17 +354,18 @@ class InferenceEngine:
         self.b_mod = torch.cat([m.bias for m in dens], 0).contiguous()
 
     # ---------------------------------------------------------------------------------------------- attention
-    def _attend(self, l: int, q0: int, Sq: int, Sk: int, qcode, kcode):
-        """masked MQA over the static buffers for query rows [q0, q0+Sq) against key rows [0, Sk)."""
+    def _attend(self, l: int, q0: int, Sq: int, Sk: int, qcode, kcode, want_probs: bool = False):
+        """masked MQA over the static buffers for query rows [q0, q0+Sq) against key rows [0, Sk).  want_probs (the guided step's forward,
+        whose reverse sweep reads them): the logits / softmax / P V form at every batch, returns the probabilities bf16 [B, Sq H, S_ld]."""
         B, S_ld, H, HD = self.B, self.S_ld, self.H, self.HD
         M = Sq * H
-        if ((M + 127) // 128) * B >= 192:  # enough 128-row blocks to fill the chip: one fused kernel
+        if not want_probs and ((M + 127) // 128) * B >= 192:  # enough 128-row blocks to fill the chip: one fused kernel
             ops.attn_fwd(self.q_buf, self.k_cache[l], self.v_cache[l], self.att_buf, None, rows=M, Sk=Sk, HD=HD, H=H, q0=q0,
                          batch=B, ldq=HD, ldk=HD, ldv=HD, ldo=HD, sQ=(S_ld * H * HD, 0), sK=(S_ld * HD, 0),
                          sV=(S_ld * HD, 0), sO=(S_ld * H * HD, 0), qcode=qcode, kcode=kcode, scale=HD**-0.5,
                          q_off=q0 * H * HD, o_off=q0 * H * HD)
             return
-        if B == 1 and self.key_split and Sq > 128 and HD == 256 and Sk % 4 == 0 and Sk >= 512 and q0 == 0:
+        if not want_probs and B == 1 and self.key_split and Sq > 128 and HD == 256 and Sk % 4 == 0 and Sk >= 512 and q0 == 0:
             # the B = 1 prefix pass (round 5): the one-pass kernel over four key ranges (244 blocks instead of 61) + the lse-weighted
             # merge — two launches and no logits / probabilities in memory instead of logits GEMM, softmax, split-K P V (+ reduce)
             ops.attn_fwd_keysplit(self.q_buf, self.k_cache[l], self.v_cache[l], self.att_buf, rows=M, Sk=Sk, HD=HD, H=H, q0=q0, ldk=HD, ldv=HD,
@@ -373,6 +381,7 @@ class InferenceEngine:
         gemm(scores, self.v_cache[l], self.att_buf, M=M, N=HD, K=S_ld, a_kc=True, b_kc=False, lda=S_ld, ldb=HD, ldc=HD,
              batch=B, sA=(M * S_ld, 0), sB=(S_ld * HD, 0), sC=(S_ld * H * HD, 0), c_off_elems=q0 * H * HD,
              split_k=pick_split_k(M, HD, S_ld, B))  # fmt: skip
+        return scores
 
     def _proj_into(self, x, lin, dst, rows_pb: int, row0: int, width: int):
         """dst[b, row0 + r, :width] = (x @ W^T)[b*rows_pb + r]  — GEMM epilogue row remap, no copy."""
@@ -607,12 +616,26 @@ class InferenceEngine:
         v = ops.linear_f32(ops.cast(act, F32), model.action_out_proj.weight, model.action_out_proj.bias)
         return v.view(B, Hs, self.A)
 
-    def _denoise_step(self, x_t, step: int, mods, mf):
+    def _adarms(self, xs, mod, eps: float):
+        """kai0_adarms_fwd -> (y, gate bf16 [B, De], rstd f32 [rows]); `rstd` is what the guided step's reverse sweep reads."""
+        rows, D = xs.shape
+        y = torch.empty_like(xs)
+        gate = torch.empty((self.B, D), dtype=BF16, device=self.dev)
+        rstd = torch.empty((rows,), dtype=F32, device=self.dev)
+        _lib.call("kai0_adarms_fwd", xs.data_ptr(), mod.data_ptr(), y.data_ptr(), gate.data_ptr(), rstd.data_ptr(), rows, rows // self.B, D,
+                  eps, ops._stream())  # fmt: skip
+        return y, gate, rstd
+
+    def _denoise_step(self, x_t, step: int, mods, mf, tape: list | None = None):
         """One Euler step on the generic path (shapes the production stack was not built for): per layer adaRMS, three projection
-        GEMMs into the static buffers, RoPE, attention, o_proj + gated residual, adaRMS, GeGLU MLP + gated residual."""
+        GEMMs into the static buffers, RoPE, attention, o_proj + gated residual, adaRMS, GeGLU MLP + gated residual.
+        `tape` (a guided step, `_denoiser_vjp`): the same launches, and what the reverse sweep needs is kept and appended per layer —
+        the inputs of both norms with their rstd, the gates, g / u, the attention's rotated query rows, output rows and probabilities;
+        the final norm's input and rstd come last."""
         model, pe = self.model, self.pe
         B, P, Hs, De = self.B, self.P, self.Hs, self.De
         H, HD, S_ld = self.H, self.HD, self.S_ld
+        NQ = H * HD
         ex = pe.gemma_expert.model
         inv_freq = self._inv_freq
         a = ops.linear_f32(x_t.view(B * Hs, self.A), model.action_in_proj.weight, model.action_in_proj.bias)
@@ -620,23 +643,121 @@ class InferenceEngine:
         rows = slice(step * B, (step + 1) * B)
         for l, layer in enumerate(ex.layers):
             m1, m2 = mods[l][0][rows], mods[l][1][rows]
-            hs, gate1 = ops.adarms(xs, m1, Hs, layer.input_layernorm.eps)
+            x_in = xs
+            hs, gate1, rstd1 = self._adarms(xs, m1, layer.input_layernorm.eps)
             at = layer.self_attn
-            self._proj_into(hs, at.q_proj, self.q_buf, Hs, P, H * HD)
+            self._proj_into(hs, at.q_proj, self.q_buf, Hs, P, NQ)
             self._proj_into(hs, at.k_proj, self.k_cache[l], Hs, P, HD)
             self._proj_into(hs, at.v_proj, self.v_cache[l], Hs, P, HD)
             ops.rope_(self.q_buf, self.pos_suffix, inv_freq, B, Hs, S_ld, P, H, HD)
             ops.rope_(self.k_cache[l], self.pos_suffix, inv_freq, B, Hs, S_ld, P, 1, HD)
-            self._attend(l, P, Hs, P + Hs, self.qcode, self.kcode)
+            probs = self._attend(l, P, Hs, P + Hs, self.qcode, self.kcode, want_probs=tape is not None)
+            if tape is not None:  # q_buf / att_buf are shared by the layers: this layer's suffix rows, compact [B Hs, H HD]
+                q_rows = torch.empty((B * Hs, NQ), dtype=BF16, device=self.dev)
+                att_rows = torch.empty((B * Hs, NQ), dtype=BF16, device=self.dev)
+                ops._copy_rows(self.q_buf, q_rows, B, Hs, NQ, S_ld * NQ, P, NQ, Hs * NQ, 0, NQ)
+                ops._copy_rows(self.att_buf, att_rows, B, Hs, NQ, S_ld * NQ, P, NQ, Hs * NQ, 0, NQ)
             xs = self._oproj(at.o_proj, Hs, P, residual=xs, gate=gate1)
-            hs, gate2 = ops.adarms(xs, m2, Hs, layer.post_attention_layernorm.eps)
+            x_mid = xs
+            hs, gate2, rstd2 = self._adarms(xs, m2, layer.post_attention_layernorm.eps)
             g = ops.linear_fwd(hs, layer.mlp.gate_proj.weight)
             u = ops.linear_fwd(hs, layer.mlp.up_proj.weight)
-            _lib.call("kai0_geglu_fwd", g.data_ptr(), u.data_ptr(), g.data_ptr(), g.numel(), ops._stream())
-            xs = ops.linear_fwd(g, layer.mlp.down_proj.weight, residual=xs, gate=gate2, gate_rpb=Hs)
-        out, _ = ops.adarms(xs, mf[rows], Hs, ex.norm.eps)
+            h = g if tape is None else torch.empty_like(g)  # (the sweep's kai0_geglu_bwd reads g)
+            _lib.call("kai0_geglu_fwd", g.data_ptr(), u.data_ptr(), h.data_ptr(), g.numel(), ops._stream())
+            xs = ops.linear_fwd(h, layer.mlp.down_proj.weight, residual=xs, gate=gate2, gate_rpb=Hs)
+            if tape is not None:
+                tape.append((x_in, rstd1, gate1, q_rows, att_rows, probs, x_mid, rstd2, gate2, g, u))
+        out, _, rstd_f = self._adarms(xs, mf[rows], ex.norm.eps)
+        if tape is not None:
+            tape.append((xs, rstd_f))
         v = ops.linear_f32(ops.cast(out, F32), model.action_out_proj.weight, model.action_out_proj.bias)
         return v.view(B, Hs, self.A)
+
+    # ------------------------------------------------------------------------------- real-time chunking (guided sampling)
+    def _dgrad(self, dy, w, *, a_map=None, into=None):
+        """dx [M, K] = dy [M, N] @ w [N, K] (ops.LinearFn.backward's dgrad form); `into`: dx is added to it (one bf16 rounding).
+        a_map: dy's rows addressed through kai0_gemm_desc's row remap."""
+        N, K = w.shape
+        M = self.B * self.Hs
+        if into is None:
+            dx = torch.empty((M, K), dtype=BF16, device=self.dev)
+            gemm(dy, w, dx, M=M, N=K, K=N, a_kc=True, b_kc=False, lda=N, ldb=K, ldc=K, a_map=a_map, split_k=pick_split_k(M, K, N))
+            return dx
+        gemm(dy, w, into, M=M, N=K, K=N, a_kc=True, b_kc=False, lda=N, ldb=K, ldc=K, a_map=a_map, accumulate=True, split_k=1)
+        return into
+
+    def _adarms_bwd(self, dy, x, mod, rstd, dres):
+        """dx of y = adaRMS(x, mod) (+ dres, the residual branch's gradient, added inside the kernel).  The modulation's gradient is
+        not needed: it lands in a scratch buffer."""
+        rows, D = x.shape
+        dx = torch.empty_like(x)
+        dmod = torch.empty((self.B, 3 * D), dtype=F32, device=self.dev)
+        _lib.call("kai0_adarms_bwd", dy.data_ptr(), None, x.data_ptr(), mod.data_ptr(), rstd.data_ptr(), dx.data_ptr(), dmod.data_ptr(),
+                  ops._p(dres), rows, rows // self.B, D, ops._stream())  # fmt: skip
+        return dx
+
+    def _gated_bwd(self, dout, gate):
+        """d(y) of out = x + y * gate[b]: bf16(dout * gate[b]).  kai0_gated_bwd's gate gradient (the only reader of y) is scratch: `dout`
+        stands in for y."""
+        rows, D = dout.shape
+        dy = torch.empty_like(dout)
+        dgate = torch.empty((self.B, D), dtype=BF16, device=self.dev)
+        _lib.call("kai0_gated_bwd", dout.data_ptr(), dout.data_ptr(), gate.data_ptr(), dy.data_ptr(), dgate.data_ptr(), rows, rows // self.B,
+                  D, ops._stream())  # fmt: skip
+        return dy
+
+    def _denoiser_vjp(self, cot, tape, step: int, mods, mf):
+        """(dv / dx_t)^T cot for the step `_denoise_step(..., tape)` just ran: cot f32 [B Hs, A] -> f32 [B Hs, A].  An explicit reverse sweep
+        over the C entry points of the training backward (the arithmetic and rounding points of autograd over the bf16 model), called
+        directly: not through the autograd shims, which would write weight gradients into a trainer's buffers (ops._grad_dst).  Only the
+        path x_t -> v is differentiated; weights, modulations and the prefix K / V are constants.  Attention: dS and dQ for the Hs H
+        folded suffix rows against all P + Hs keys in one launch (kai0_attn_bwd_dq over the stored probabilities), dK / dV for the
+        suffix key rows only, as two TN GEMMs over the key columns [P, P + Hs) of dS and P (widened to 16-byte boundaries)."""
+        model = self.model
+        B, P, Hs, De, A = self.B, self.P, self.Hs, self.De, self.A
+        H, HD, S_ld = self.H, self.HD, self.S_ld
+        NQ, M, R = H * HD, B * Hs, Hs * H
+        dev = self.dev
+        rows = slice(step * B, (step + 1) * B)
+        layers = self.pe.gemma_expert.model.layers
+        # action_out_proj^T: d(out32)[m, k] = sum_a cot[m, a] w_out[a, k]; the f32 <- bf16 cast hands its gradient on rounded to bf16
+        d32 = torch.empty((M, De), dtype=F32, device=dev)
+        ops.gemm_f32(cot, A, 1, model.action_out_proj.weight, De, 1, d32, M, De, A)
+        x_last, rstd_f = tape[-1]
+        dxs = self._adarms_bwd(ops.cast(d32, BF16), x_last, mf[rows], rstd_f, None)
+        c0 = P // 8 * 8  # the suffix key columns, from a 16-byte boundary of the probability rows
+        kw, koff = round_up(P + Hs - c0, 8), P - c0
+        for l in range(len(layers) - 1, -1, -1):
+            layer = layers[l]
+            x_in, rstd1, gate1, q_rows, att_rows, probs, x_mid, rstd2, gate2, g, u = tape[l]
+            at, mlp = layer.self_attn, layer.mlp
+            # xs = x_mid + down(geglu(gate(hs2), up(hs2))) * gate2,  hs2 = adaRMS(x_mid, m2)
+            dh = self._dgrad(self._gated_bwd(dxs, gate2), mlp.down_proj.weight)
+            dg, du = torch.empty_like(g), torch.empty_like(u)
+            _lib.call("kai0_geglu_bwd", dh.data_ptr(), g.data_ptr(), u.data_ptr(), dg.data_ptr(), du.data_ptr(), g.numel(), ops._stream())
+            dhs = self._dgrad(du, mlp.up_proj.weight, into=self._dgrad(dg, mlp.gate_proj.weight))
+            dxs = self._adarms_bwd(dhs, x_mid, mods[l][1][rows], rstd2, dxs)
+            # x_mid = x_in + o_proj(attention(q, k, v)) * gate1,  q | k | v = rope(proj(adaRMS(x_in, m1)))
+            datt = self._dgrad(self._gated_bwd(dxs, gate1), at.o_proj.weight)
+            dS = torch.empty_like(probs)
+            dq = torch.empty((M, NQ), dtype=BF16, device=dev)
+            _lib.call("kai0_attn_bwd_dq", datt.data_ptr(), att_rows.data_ptr(), probs.data_ptr(), self.k_cache[l].data_ptr(),
+                      self.v_cache[l].data_ptr(), dS.data_ptr(), dq.data_ptr(), B, R, P + Hs, HD, HD, HD, HD, S_ld, R * HD, S_ld * HD,
+                      S_ld * HD, R * S_ld, HD**-0.5, ops._stream())  # fmt: skip
+            dkv = torch.empty((2, B, kw, HD), dtype=BF16, device=dev)
+            for dst, a_t, b_t in ((dkv[0], dS, q_rows), (dkv[1], probs, datt)):  # dK = dS^T Q, dV = P^T dO over the suffix key columns
+                gemm(a_t, b_t, dst, M=kw, N=HD, K=R, a_kc=False, b_kc=False, lda=S_ld, ldb=HD, ldc=HD, batch=B, sA=(R * S_ld, 0),
+                     sB=(R * HD, 0), sC=(kw * HD, 0), a_off_elems=c0)
+            ops.rope_(dq, self.pos_suffix, self._inv_freq, B, Hs, Hs, 0, H, HD, inverse=True)
+            ops.rope_(dkv[0], self.pos_suffix, self._inv_freq, B, Hs, kw, koff, 1, HD, inverse=True)
+            dhs = self._dgrad(dq, at.q_proj.weight)
+            self._dgrad(dkv[0], at.k_proj.weight, a_map=(Hs, kw, koff), into=dhs)
+            self._dgrad(dkv[1], at.v_proj.weight, a_map=(Hs, kw, koff), into=dhs)
+            dxs = self._adarms_bwd(dhs, x_in, mods[l][0][rows], rstd1, dxs)
+        # xs = bf16(action_in_proj(x_t)): action_in_proj^T of the gradient as f32
+        jte = torch.empty((M, A), dtype=F32, device=dev)
+        ops.gemm_f32(ops.cast(dxs, F32), De, 1, model.action_in_proj.weight, A, 1, jte, M, A, De)
+        return jte
 
     def _run_pi0(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, state):
         """pi0 chunk: prefix pass, the request's state token once, then the Euler loop over Hs + 1 suffix rows."""
@@ -688,6 +809,19 @@ class InferenceEngine:
         self._content_stamp()
         return x_t
 
+    def _tables(self, times: list[float]):
+        """The modulation table (and, production stack: the folded per-step weights) of a schedule: a function of the weights and the
+        schedule only — computed on the first (warm-up) run, outside graph capture, and kept for the engine's lifetime."""
+        if tuple(times) not in self._times_dev:  # H2D copy: must happen outside graph capture (warm-up run)
+            self._times_dev[tuple(times)] = torch.tensor(times, dtype=F32).repeat_interleave(self.B).to(self.dev)
+        hit = self._mods_cache.get(tuple(times))
+        if hit is None:
+            mods, mf = self._modulations(times)
+            hit = self._mods_cache[tuple(times)] = (mods, mf, self._mod_ld if self.fast else None, self._gates if self.fast else None)
+            if self.fast:
+                self._fold_cache[tuple(times)] = self._fold_modulations(mods, len(times))
+        return hit
+
     def _run(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, state=None):
         if not self.pi05:
             if state is None and self._static_in is not None:
@@ -697,16 +831,7 @@ class InferenceEngine:
             return self._run_pi0(images, img_masks, lang_tokens, lang_masks, noise, num_steps, state)
         times = euler_times(num_steps)
         dt = float(np.float32(-1.0 / num_steps))
-        if tuple(times) not in self._times_dev:  # H2D copy: must happen outside graph capture (warm-up run)
-            self._times_dev[tuple(times)] = torch.tensor(times, dtype=F32).repeat_interleave(self.B).to(self.dev)
-        # the modulation table (and, production stack: the folded per-step weights) of this schedule: a function of the weights and the
-        # schedule only — computed on the first (warm-up) run, kept for the engine's lifetime
-        hit = self._mods_cache.get(tuple(times))
-        if hit is None:
-            mods, mf = self._modulations(times)
-            hit = self._mods_cache[tuple(times)] = (mods, mf, self._mod_ld if self.fast else None, self._gates if self.fast else None)
-            if self.fast:
-                self._fold_cache[tuple(times)] = self._fold_modulations(mods, len(times))
+        hit = self._tables(times)
         mods, mf = hit[0], hit[1]
         x_t = noise.clone().contiguous()
         if not self.fast:
@@ -751,6 +876,109 @@ class InferenceEngine:
             ops.euler_step_(x_t, v_t, dt)
         self._content_stamp()
         return x_t
+
+    def _guided_tables(self, times: list[float]):
+        """`_tables` for the guided loop, which runs the generic per-layer step on every engine: contiguous [steps B, 3 De] modulation
+        rows per norm (the production stack keeps them as column slices of one table)."""
+        mods, mf = self._tables(times)[:2]
+        if not self.fast:
+            return mods, mf
+        hit = self._guided_mods.get(tuple(times))
+        if hit is None:
+            hit = self._guided_mods[tuple(times)] = ([(a.contiguous(), b.contiguous()) for a, b in mods], mf.contiguous())
+        return hit
+
+    def _run_guided(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, max_guidance_weight: float, provided: int):
+        """A real-time-chunking chunk (pi0_rtc.py:293-349; kai0_amd/rtc.py): the prefix pass and the modulation tables of `_run`, then per
+        Euler step ONE forward of the generic per-layer step that keeps what its reverse sweep needs (the linearisation point),
+        kai0_rtc_error, the sweep `_denoiser_vjp`, kai0_rtc_update.  One stream; t, the guidance weight and dt are launch constants;
+        the previous chunk and the prefix weights are read from the engine's static buffers `_g_prev` / `_g_w`."""
+        from . import rtc
+
+        times = euler_times(num_steps)
+        dt = float(np.float32(-1.0 / num_steps))
+        mods, mf = self._guided_tables(times)
+        gws = rtc.guidance_weights(times, max_guidance_weight)
+        x_t = noise.clone().contiguous()
+        self._prefix_pass(images, img_masks, lang_tokens, lang_masks)
+        M = self.B * self.Hs
+        for step, (t, g) in enumerate(zip(times, gws, strict=True)):
+            tape = []
+            v_t = self._denoise_step(x_t, step, mods, mf, tape)
+            err = ops.rtc_error(x_t, v_t, self._g_prev, self._g_w, provided, t)
+            jte = self._denoiser_vjp(err.view(M, self.A), tape, step, mods, mf)
+            ops.rtc_update_(x_t, v_t, err, jte, t, g, dt)
+        self._content_stamp()
+        return x_t
+
+    @torch.no_grad()
+    def denoiser_vjp(self, images, img_masks, lang_tokens, lang_masks, x_t, cotangent, num_steps: int, step: int):
+        """The guided loop's primitive on its own (tests, tools): the prefix pass, then at `x_t` and the time of Euler step `step` the
+        velocity v and (dv / dx_t)^T cotangent, both f32 [B, Hs, A].  Eager launches."""
+        times = euler_times(num_steps)
+        mods, mf = self._guided_tables(times)
+        self._prefix_pass(images, img_masks, lang_tokens, lang_masks)
+        tape = []
+        x_t = x_t.to(F32).contiguous()
+        v_t = self._denoise_step(x_t, step, mods, mf, tape)
+        jte = self._denoiser_vjp(cotangent.to(F32).contiguous().view(self.B * self.Hs, self.A), tape, step, mods, mf)
+        return v_t, jte.view(self.B, self.Hs, self.A)
+
+    @torch.no_grad()
+    def sample_actions_guided(self, images, img_masks, lang_tokens, lang_masks, noise, guidance, num_steps: int = 10):
+        """`sample_actions` steered towards the previous chunk (`guidance`: kai0_amd.rtc.Guidance, resolved on the host).  Captured into
+        a hipGraph of its own, keyed on what is baked into its launches (num_steps, max_guidance_weight, provided); the unguided graph
+        and its static buffers are not touched.  KAI0_INFER_GRAPH=0 (or a refused capture) runs the same launches eagerly."""
+        if not self.pi05:
+            raise NotImplementedError("guided sampling (real-time chunking) is built for pi0.5 only: pi0's Jacobian also runs through the "
+                                      "time MLP and the state token")  # fmt: skip
+        B, Hs, A = self.B, self.Hs, self.A
+        if guidance.prev.shape != (B, Hs, A) or guidance.weights.shape != (Hs,):
+            raise ValueError(f"guidance for a [{B}, {Hs}, {A}] chunk expected, got prev {guidance.prev.shape}, weights {guidance.weights.shape}")
+        if self._g_prev is None:
+            self._g_prev = torch.zeros((B, Hs, A), dtype=F32, device=self.dev)
+            self._g_w = torch.zeros((Hs,), dtype=F32, device=self.dev)
+        self._g_prev.copy_(torch.from_numpy(guidance.prev))
+        self._g_w.copy_(torch.from_numpy(guidance.weights))
+        key = (num_steps, float(guidance.max_guidance_weight), int(guidance.provided))
+        args = (images, img_masks, lang_tokens, lang_masks, noise)
+        if self.use_graph and self._g_graph_key != key:
+            self._capture_guided(*args, key)
+        if not self.use_graph or self._g_graph is None:
+            return self._run_guided(*args, *key)
+        si = self._g_static_in
+        for dst, src in zip(si["images"], images, strict=True):
+            dst.copy_(src)
+        for dst, src in zip(si["img_masks"], img_masks, strict=True):
+            dst.copy_(src)
+        si["lang_tokens"].copy_(lang_tokens)
+        si["lang_masks"].copy_(lang_masks)
+        si["noise"].copy_(noise)
+        self._g_graph.replay()
+        return self._g_static_out.clone()
+
+    def _capture_guided(self, images, img_masks, lang_tokens, lang_masks, noise, key):
+        si = {
+            "images": [im.clone().contiguous() for im in images],
+            "img_masks": [m.clone() for m in img_masks],
+            "lang_tokens": lang_tokens.clone().contiguous(),
+            "lang_masks": lang_masks.clone().contiguous(),
+            "noise": noise.clone().contiguous(),
+        }
+        self._g_graph = self._g_graph_key = self._g_static_in = self._g_static_out = None
+        try:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture requires
+                self._run_guided(si["images"], si["img_masks"], si["lang_tokens"], si["lang_masks"], si["noise"], *key)
+            torch.cuda.current_stream().wait_stream(side)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                out = self._run_guided(si["images"], si["img_masks"], si["lang_tokens"], si["lang_masks"], si["noise"], *key)
+            self._g_graph, self._g_graph_key, self._g_static_in, self._g_static_out = graph, key, si, out
+        except Exception as e:  # noqa: BLE001 - capture problems must not take serving down
+            logger.warning("hipGraph capture of the guided chunk failed (%s); running eager HIP launches", e)
+            self._g_graph_key = key  # (not tried again for this key)
 
     # -------------------------------------------------------------------------------------------------- API
     @torch.no_grad()

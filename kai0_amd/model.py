@@ -737,10 +737,29 @@ class PI0Pytorch(nn.Module):
 
     # ---- inference ----------------------------------------------------------------------------------------
     @torch.no_grad()
-    def sample_actions(self, device, observation, noise=None, num_steps=10) -> torch.Tensor:
-        """pi0_pytorch.py:375-419: prefix pass into a static KV cache, then `num_steps` Euler steps."""
+    def sample_actions(self, device, observation, noise=None, num_steps=10, *, prev_action_chunk=None, inference_delay=None,
+                       execute_horizon=None, mask_prefix_delay=False, prefix_attention_schedule="exp", max_guidance_weight=0.5,
+                       enable_rtc=True) -> torch.Tensor:  # fmt: skip
+        """pi0_pytorch.py:375-419: prefix pass into a static KV cache, then `num_steps` Euler steps.
+        Real-time chunking (pi0_rtc.py:233-360, kai0_amd/rtc.py): with a `prev_action_chunk` ([H, A'] or [B, H, A'], in the model's
+        normalised action space) and `enable_rtc`, every step is steered towards the part of the previous chunk that will still be
+        executed — rows below `inference_delay` fully, rows up to `execute_horizon` by `prefix_attention_schedule` — through the
+        denoiser's vector-Jacobian product (infer.InferenceEngine.sample_actions_guided).  Without one the call is the unguided one in
+        every respect.  pi0.5 only; `mask_prefix_delay` is not built."""
         from .infer import InferenceEngine
 
+        guidance = None
+        if mask_prefix_delay:
+            raise NotImplementedError("sample_actions: mask_prefix_delay is not built (the reference's Policy never passes it)")
+        if enable_rtc and prev_action_chunk is not None:
+            from . import rtc
+
+            if not self.pi05:
+                raise NotImplementedError("sample_actions: real-time chunking is built for pi0.5 only (pi0's Jacobian also runs through "
+                                          "the time MLP and the state token)")  # fmt: skip
+            guidance = rtc.resolve(prev_action_chunk, batch=observation.state.shape[0], action_horizon=self.config.action_horizon,
+                                   action_dim=self.config.action_dim, inference_delay=inference_delay, execute_horizon=execute_horizon,
+                                   prefix_attention_schedule=prefix_attention_schedule, max_guidance_weight=max_guidance_weight)  # fmt: skip
         bsize = observation.state.shape[0]
         if noise is None:
             noise = self.sample_noise((bsize, self.config.action_horizon, self.config.action_dim), device)
@@ -757,7 +776,7 @@ class PI0Pytorch(nn.Module):
             # ... the other prompt-length buckets' engines too: their own stamps still equal their reference (they have not run since
             # the edit), so `compatible()` would accept them and the next request in their bucket would compute from old weights
             self.__dict__.pop("_engine_lru", None)
-        if eng is not None and eng.shape_matches(*key):
+        if guidance is None and eng is not None and eng.shape_matches(*key):
             # the common serving case: same request shape as the last call.  The captured chunk is queued BEFORE the weights are checked
             # (0.13 ms of host work that would otherwise stand in front of every chunk); a failed check falls through to the rebuild
             out = eng.replay_then_verify(images, img_masks, lang_tokens, lang_masks, noise.to(F32), num_steps, state=state)
@@ -772,6 +791,8 @@ class PI0Pytorch(nn.Module):
             while len(lru) > self._ENGINE_SLOTS:
                 lru.pop(next(iter(lru)))
             self.__dict__["_engine_cur"] = eng
+        if guidance is not None:
+            return eng.sample_actions_guided(images, img_masks, lang_tokens, lang_masks, noise.to(F32), guidance, num_steps)
         return eng.sample_actions(images, img_masks, lang_tokens, lang_masks, noise.to(F32), num_steps, state=state)
 
 

@@ -1767,6 +1767,38 @@ def euler_step_(x, v, dt: float):
     return x
 
 
+def _chk_f32_rows(name: str, rows: int, A: int, **ts) -> None:
+    for k, t in ts.items():
+        if not t.is_cuda:
+            raise _lib.Kai0HipError(f"{name}: expected a CUDA (HIP) tensor for `{k}`; the product path has no CPU fallback")
+        if t.dtype != F32 or not t.is_contiguous() or t.numel() != rows * A:
+            raise TypeError(f"{name}: `{k}` must be a contiguous f32 tensor of {rows} x {A} elements, got {t.dtype} {tuple(t.shape)}")
+
+
+def rtc_error(x, v, prev, w_row, provided: int, t: float, out=None):
+    """kai0_rtc_error: e = ((prev - (x - t v)) * w_row[row % Hs]) * (col < provided) for f32 [..., Hs, A] (contiguous, any element offset)."""
+    A, Hs = x.shape[-1], w_row.numel()
+    rows = x.numel() // A
+    if out is None:
+        out = torch.empty_like(x)
+    _chk_f32_rows("rtc_error", rows, A, x=x, v=v, prev=prev, out=out)
+    if not w_row.is_cuda or w_row.dtype != F32 or not w_row.is_contiguous() or rows % Hs != 0:
+        raise TypeError(f"rtc_error: w_row must be a contiguous f32 HIP vector whose length divides the {rows} rows")
+    _lib.call("kai0_rtc_error", x.data_ptr(), v.data_ptr(), prev.data_ptr(), w_row.data_ptr(), int(provided), float(t), out.data_ptr(),
+              rows, Hs, A, _stream())  # fmt: skip
+    return out
+
+
+def rtc_update_(x, v, err, jte, t: float, g: float, dt: float):
+    """kai0_rtc_update: x += dt * nan_to_num(v - g (err - t jte)) in place (non-finite -> 0)."""
+    A = x.shape[-1]
+    rows = x.numel() // A
+    _chk_f32_rows("rtc_update", rows, A, x=x, v=v, err=err, jte=jte)
+    _lib.call("kai0_rtc_update", x.data_ptr(), v.data_ptr(), err.data_ptr(), jte.data_ptr(), float(t), float(g), float(dt), rows, A,
+              _stream())  # fmt: skip
+    return x
+
+
 def sqrt_scale(dim: int) -> float:
     """`math.sqrt(dim)` as the f32 scalar torch multiplies a bf16 tensor by."""
     return float(torch.tensor(math.sqrt(dim), dtype=torch.float32))

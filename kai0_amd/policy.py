@@ -41,7 +41,8 @@ def _map_leaves(fn, tree):
 class Policy(BasePolicy):
     def __init__(self, model, *, transforms: Sequence = (), output_transforms: Sequence = (),
                  sample_kwargs: dict[str, Any] | None = None, metadata: dict[str, Any] | None = None,
-                 pytorch_device: str = "cuda:0", is_pytorch: bool = True, rng=None, device_resize: bool = True):  # fmt: skip
+                 pytorch_device: str = "cuda:0", is_pytorch: bool = True, rng=None, device_resize: bool = True,
+                 rtc_normalize_prev: bool = False):  # fmt: skip
         if not is_pytorch:
             raise ValueError("kai0_amd.policy.Policy serves the torch-protocol model only (JAX checkpoints: convert first)")
         self._model = model.to(pytorch_device)
@@ -65,10 +66,45 @@ class Policy(BasePolicy):
         self._metadata = metadata or {}
         self._pytorch_device = pytorch_device
         self._sample_actions = self._model.sample_actions
+        # Real-time chunking: the reference hands the client's previous chunk to the model as it arrives (policy.py:84-90) — in ROBOT
+        # space, while the model compares it with its own NORMALISED chunk.  That stays the default, for drop-in
+        # parity; rtc_normalize_prev maps the chunk through the action statistics of the output stack's Unnormalize first.
+        self._rtc_norm = None
+        if rtc_normalize_prev:
+            if any(isinstance(t, _transforms.AbsoluteActions) for t in output_transforms):
+                raise ValueError("rtc_normalize_prev: the output stack holds AbsoluteActions (the served actions are state + delta); "
+                                 "normalising the previous chunk alone does not bring it back to the model's space")  # fmt: skip
+            un = [t for t in output_transforms if isinstance(t, _transforms.Unnormalize)]
+            if len(un) != 1 or un[0].norm_stats is None or "actions" not in un[0].norm_stats:
+                raise ValueError("rtc_normalize_prev needs exactly one Unnormalize with `actions` statistics in the output stack")
+            self._rtc_norm = (un[0].norm_stats["actions"], bool(un[0].use_quantiles))
+
+    _RTC_KEYS = ("prev_action_chunk", "inference_delay", "execute_horizon")
+
+    def _rtc_kwargs(self, inputs: dict) -> dict:
+        """The real-time-chunking keys of a request (policy.py:84-90), taken OUT of it: lists / scalars as the clients send them ->
+        sample kwargs.  The transform stack never sees them."""
+        kw = {k: inputs.pop(k) for k in self._RTC_KEYS if k in inputs}
+        prev = kw.get("prev_action_chunk")
+        if prev is not None:
+            prev = np.asarray(prev, dtype=np.float32)
+            if self._rtc_norm is not None:
+                from . import normalize as _normalize
+
+                stats, quant = self._rtc_norm
+                n = min(prev.shape[-1], np.asarray(stats.mean).shape[-1])  # the statistics cover the robot's dims; the rest is padding
+                prev = prev.copy()
+                prev[..., :n] = _normalize.normalize(prev[..., :n], stats, use_quantiles=quant)
+            kw["prev_action_chunk"] = prev
+        for k in ("inference_delay", "execute_horizon"):
+            if kw.get(k) is not None:
+                kw[k] = int(np.asarray(kw[k]).reshape(-1)[0])
+        return kw
 
     def infer(self, obs: dict, *, noise: np.ndarray | None = None) -> dict:
         dev = self._pytorch_device
         inputs = _map_leaves(lambda x: x, obs)  # shallow structural copy: transforms may rebind entries
+        rtc_kwargs = self._rtc_kwargs(inputs)
         inputs = self._input_transform(inputs)
         rs = self._device_resize
         if rs is not None and not all(isinstance(v, np.ndarray) and v.dtype == np.uint8 for v in inputs["image"].values()):
@@ -83,7 +119,7 @@ class Policy(BasePolicy):
                 inputs["image"] = {k: out[i : i + 1] for i, k in enumerate(inputs["image"])}
             else:
                 inputs["image"] = {k: resize_with_pad_u8(v, rs.height, rs.width) for k, v in inputs["image"].items()}
-        kwargs = dict(self._sample_kwargs)
+        kwargs = {**self._sample_kwargs, **rtc_kwargs}
         if noise is not None:
             n = torch.from_numpy(noise).to(dev)
             kwargs["noise"] = n[None, ...] if n.ndim == 2 else n

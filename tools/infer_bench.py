@@ -1,6 +1,9 @@
 """p50 of one B = 1 action chunk + stage split, without the training bench (quick iteration on the inference path).
 usage: python tools/infer_bench.py [--pi0]      (--pi0: Pi0Config(pi05=False) — 48 prompt slots, a state token; adds the time of the
-ten steps' suffix-embedding launches, ops.pi0_suffix_embed, replayed from a graph of their own)"""
+ten steps' suffix-embedding launches, ops.pi0_suffix_embed, replayed from a graph of their own)
+       python tools/infer_bench.py --rtc        (pi0.5: adds the p50 of a GUIDED B = 1 chunk — real-time chunking, d = 3, exec_h = 8, "exp",
+the previous chunk as 14-dim rows — measured the same way as the unguided p50 beside it, and of the same chunk on eager launches)"""
+import time
 import json
 import os
 import sys
@@ -38,4 +41,30 @@ if pi0:
                                  model.action_time_mlp_out.weight, model.action_time_mlp_out.bias, xs, sq, Hs, Ss)
 
     res["suffix_embed_10_steps_ms"] = bench._graph_time_ms(ten)
+if "--rtc" in sys.argv[1:] and not pi0:
+    model.trim_prompt_padding_infer = False
+    obs, _ = bench.synthetic_batch(cfg, 1, seed=123, device=dev)
+    noise = torch.randn(1, cfg.action_horizon, cfg.action_dim, device=dev)
+    prev = torch.randn(cfg.action_horizon, 14).tolist()
+    kw = dict(prev_action_chunk=prev, inference_delay=3, execute_horizon=8)
+
+    def p50(iters=20):
+        for _ in range(2):
+            model.sample_actions(dev, obs, noise=noise, num_steps=10, **kw)
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(iters):
+            t0 = time.perf_counter()
+            model.sample_actions(dev, obs, noise=noise, num_steps=10, **kw).cpu()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        ts.sort()
+        return {"p50_ms": ts[len(ts) // 2], "min_ms": ts[0], "p90_ms": ts[int(len(ts) * 0.9)]}
+
+    rtc = {"captured": p50()}
+    eng = model._engine
+    rtc["graph"] = eng._g_graph is not None
+    eng.use_graph = False
+    rtc["eager"] = p50(5)
+    eng.use_graph = True
+    res["rtc_guided"] = {k: ({a: round(b, 3) for a, b in v.items()} if isinstance(v, dict) else v) for k, v in rtc.items()}
 print(json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in res.items()}))
