@@ -705,6 +705,28 @@ int kai0_multi_dot(const void* g, int g_f32, const void* const* srcs, int src_f3
  * (torch.nn.utils.clip_grad_norm_) */
 int kai0_clip_coef(const float* sumsq, float max_norm, float* coef, float* norm_out, kai0_stream_t stream);
 
+/* LoRA adapters (src/openpi/models/lora.py:54-65 `Einsum`: result + einsum(einsum(x, lora_a), lora_b) * scaling_value, every einsum in
+ * the activation dtype; :144-148 `FeedForward._dot`: the same without the scale).  The two products with an activation-sized operand
+ * and a rank-sized dimension; the rank-r up-projection and dx += dT A are kai0_gemm_bf16 launches.
+ * kai0_lora_down (:61 `jnp.einsum(eqn_a, x, w_a)`; in the backward dT = dY B with B transposed first):
+ *   T[m][r] = bf16( sum_k X[m][k] A[r][k] ),   X bf16 [M][ldx], A bf16 [R][lda], T bf16 [M][ldt]; f32 accumulation, one rounding.
+ *   R in {16, 32, 48, 64} (stacked adapters: A rows of several adapters over one X); K a multiple of 8; any M >= 0.  Leading
+ *   dimensions are multiples of 8 and may exceed the extents, so T may be a column slice of a wider buffer (only columns < R of
+ *   rows < M are written).  X and A 16-byte aligned.  X is read once. */
+int kai0_lora_down(const void* X, int64_t ldx, const void* A, int64_t lda, void* T, int64_t ldt, int M, int R, int K,
+                   kai0_stream_t stream);
+/* kai0_lora_wgrad (the adapter gradients of :61-63 through autograd): G = scale * P^T Q over the M rows of both,
+ *   P bf16 [M][ldp] with R columns (R a multiple of 8, at most 64), Q bf16 [M][ldq] with C columns (C a multiple of 8),
+ *   transposed == 0:  G[r][c] at r * ldg + c   (lora_a.weight [R, in]  = dT^T X)
+ *   transposed != 0:  G[c][r] at c * ldg + r   (lora_b.weight [out, R] = s dY^T T with P = T, Q = dY)
+ *   G bf16, or f32 with out_f32:  f32 accumulation over M; the f32 sum times scale (one f32 multiply) is rounded once to G's dtype.
+ * M is cut into slices over the grid; each block writes an f32 partial into `workspace` (kai0_lora_wgrad_workspace_bytes(M, R, C)
+ * bytes, 4-byte aligned) and a second launch adds the slices in slice order: no atomics, the same call gives the same bits.
+ * P and Q 16-byte aligned, ldp / ldq multiples of 8.  Both operands are read once. */
+int kai0_lora_wgrad(const void* P, int64_t ldp, const void* Q, int64_t ldq, void* G, int64_t ldg, int M, int R, int C, float scale,
+                    int transposed, int out_f32, void* workspace, int64_t workspace_bytes, kai0_stream_t stream);
+int64_t kai0_lora_wgrad_workspace_bytes(int M, int R, int C);
+
 #ifdef __cplusplus
 }
 #endif

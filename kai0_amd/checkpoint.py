@@ -37,6 +37,8 @@ def load_model_safetensors(model: torch.nn.Module, path: str, strict: bool = Tru
     # a missing name is forgiven only if it is tied to a tensor the file DID contain (what safetensors.torch.load_model
     # forgives: the aliases save_model dropped); a file with no member of a tied group leaves that weight unloaded -> error
     forgiven = {n for names in _tied_groups(model) if any(m in sd for m in names) for n in names}
-    missing = [k for k in missing if k not in forgiven]
+    # a base (non-LoRA) checkpoint into a LoRA model: the adapters keep their initialisation (weight_loaders.py:53-54,
+    # `missing_regex=".*lora.*"`); nothing else may be missing
+    missing = [k for k in missing if k not in forgiven and ".lora_" not in k]
     if strict and (missing or unexpected):
         raise RuntimeError(f"Error(s) in loading state_dict: missing {missing}, unexpected {list(unexpected)}")

@@ -12,6 +12,12 @@ trees themselves — each rule cites the JAX definition whose einsum / matmul fi
     layers/attn/attn_vec_einsum/w [L, N, H, D]  "BTNH,NHD->BTD" -> o_proj.weight [D, N*H]                          :238-245
     layers/mlp/gating_einsum [L, 2, D, F]  dot(x, w[0]) = gate, dot(x, w[1]) = up -> gate_proj / up_proj.weight [F, D]  :262-270
     layers/mlp/linear [L, F, D]  dot(a, w)              -> down_proj.weight [D, F]                                 :273-278
+    LoRA variants (models/lora.py:43-52, 109-121; r = rank), ten more arrays per tower, into the grouped layout of kai0_amd.lora:
+      attn/q_einsum/lora_a [L, N, D, r], lora_b [L, N, r, H]        -> q_proj.lora_a.weight [N*r, D], q_proj.lora_b.weight [N*H, r]
+      attn/kv_einsum/lora_a [L, 2, K, D, r], lora_b [L, 2, K, r, H] -> k_proj / v_proj .lora_a.weight [K*r, D], .lora_b.weight [K*H, r]
+      attn/attn_vec_einsum/lora_a [L, N, H, r], lora_b [L, N, r, D] -> o_proj.lora_a.weight [N*r, H], o_proj.lora_b.weight [D, N*r]
+      mlp/gating_einsum_lora_a [L, 2, D, r], _lora_b [L, 2, r, F]   -> gate_proj / up_proj .lora_a.weight [r, D], .lora_b.weight [F, r]
+      mlp/linear_lora_a [L, F, r], linear_lora_b [L, r, D]          -> down_proj.lora_a.weight [r, F], .lora_b.weight [D, r]
     layers/pre_attention_norm/scale [L, D], pre_ffw_norm/scale, final_norm/scale   -> *.weight ((1 + w) on both sides) :121-125
     layers/pre_attention_norm_1/Dense_0/{kernel [L, D, 3D], bias [L, 3D]} (adaRMS) -> *.dense.{weight [3D, D], bias}   :128
     pi0 (pi05=False): the expert's RMSNorm is called with cond = None (embed_suffix returns `adarms_cond = None`, pi0.py:139-177), so it creates
@@ -116,6 +122,26 @@ def jax_to_torch(params: Mapping, *, fill_missing: bool = False, vocab_size: int
             sd[pre + "mlp.gate_proj.weight"] = _t(gating[i, 0].T)
             sd[pre + "mlp.up_proj.weight"] = _t(gating[i, 1].T)
             sd[pre + "mlp.down_proj.weight"] = _t(linear[i].T)
+            if f"{llm}layers/attn/q_einsum{sfx}/lora_a" in p:
+                at, ml = f"{llm}layers/attn/", f"{llm}layers/mlp{sfx}/"
+                qa, qb = p[f"{at}q_einsum{sfx}/lora_a"][i], p[f"{at}q_einsum{sfx}/lora_b"][i]              # [N, D, r], [N, r, H]
+                kva, kvb = p[f"{at}kv_einsum{sfx}/lora_a"][i], p[f"{at}kv_einsum{sfx}/lora_b"][i]          # [2, K, D, r], [2, K, r, H]
+                oa, ob = p[f"{at}attn_vec_einsum{sfx}/lora_a"][i], p[f"{at}attn_vec_einsum{sfx}/lora_b"][i]  # [N, H, r], [N, r, D]
+                ga, gb = p[ml + "gating_einsum_lora_a"][i], p[ml + "gating_einsum_lora_b"][i]              # [2, D, r], [2, r, F]
+                la, lb = p[ml + "linear_lora_a"][i], p[ml + "linear_lora_b"][i]                            # [F, r], [r, D]
+                r = qa.shape[-1]
+                sd[pre + "self_attn.q_proj.lora_a.weight"] = _t(qa.transpose(0, 2, 1).reshape(N * r, D))
+                sd[pre + "self_attn.q_proj.lora_b.weight"] = _t(qb.transpose(0, 2, 1).reshape(N * H, r))
+                for j, tn in ((0, "k_proj"), (1, "v_proj")):
+                    sd[f"{pre}self_attn.{tn}.lora_a.weight"] = _t(kva[j].transpose(0, 2, 1).reshape(K * r, D))
+                    sd[f"{pre}self_attn.{tn}.lora_b.weight"] = _t(kvb[j].transpose(0, 2, 1).reshape(K * H, r))
+                sd[pre + "self_attn.o_proj.lora_a.weight"] = _t(oa.transpose(0, 2, 1).reshape(N * r, H))
+                sd[pre + "self_attn.o_proj.lora_b.weight"] = _t(ob.reshape(N * r, D).T)
+                for j, tn in ((0, "gate_proj"), (1, "up_proj")):
+                    sd[f"{pre}mlp.{tn}.lora_a.weight"] = _t(ga[j].T)
+                    sd[f"{pre}mlp.{tn}.lora_b.weight"] = _t(gb[j].T)
+                sd[pre + "mlp.down_proj.lora_a.weight"] = _t(la.T)
+                sd[pre + "mlp.down_proj.lora_b.weight"] = _t(lb.T)
             for jn, tn in (("pre_attention_norm", "input_layernorm"), ("pre_ffw_norm", "post_attention_layernorm")):
                 if ada:
                     sd[f"{pre}{tn}.dense.weight"] = _t(p[f"{llm}layers/{jn}{sfx}/Dense_0/kernel"][i].T)
@@ -188,6 +214,22 @@ def torch_to_jax(sd: Mapping[str, torch.Tensor], *, num_heads: int = 8, num_kv_h
         out[f"{llm}layers/attn/attn_vec_einsum{sfx}/w"] = np.stack([g(i, "self_attn.o_proj.weight").T.reshape(N, H, D) for i in range(L)])
         out[f"{llm}layers/mlp{sfx}/gating_einsum"] = np.stack([np.stack([g(i, "mlp.gate_proj.weight").T, g(i, "mlp.up_proj.weight").T]) for i in range(L)])
         out[f"{llm}layers/mlp{sfx}/linear"] = np.stack([g(i, "mlp.down_proj.weight").T for i in range(L)])
+        if f"{src}layers.0.self_attn.q_proj.lora_a.weight" in sd:
+            at, ml = f"{llm}layers/attn/", f"{llm}layers/mlp{sfx}/"
+            r = g(0, "self_attn.q_proj.lora_b.weight").shape[1]
+            F = g(0, "mlp.gate_proj.weight").shape[0]
+            st = lambda f: np.stack([f(i) for i in range(L)])  # noqa: E731
+            out[f"{at}q_einsum{sfx}/lora_a"] = st(lambda i: g(i, "self_attn.q_proj.lora_a.weight").reshape(N, r, D).transpose(0, 2, 1))
+            out[f"{at}q_einsum{sfx}/lora_b"] = st(lambda i: g(i, "self_attn.q_proj.lora_b.weight").reshape(N, H, r).transpose(0, 2, 1))
+            out[f"{at}kv_einsum{sfx}/lora_a"] = st(lambda i: np.stack([g(i, f"self_attn.{n}_proj.lora_a.weight").reshape(K, r, D).transpose(0, 2, 1) for n in ("k", "v")]))
+            out[f"{at}kv_einsum{sfx}/lora_b"] = st(lambda i: np.stack([g(i, f"self_attn.{n}_proj.lora_b.weight").reshape(K, H, r).transpose(0, 2, 1) for n in ("k", "v")]))
+            out[f"{at}attn_vec_einsum{sfx}/lora_a"] = st(lambda i: g(i, "self_attn.o_proj.lora_a.weight").reshape(N, r, H).transpose(0, 2, 1))
+            out[f"{at}attn_vec_einsum{sfx}/lora_b"] = st(lambda i: g(i, "self_attn.o_proj.lora_b.weight").T.reshape(N, r, D))
+            out[ml + "gating_einsum_lora_a"] = st(lambda i: np.stack([g(i, f"mlp.{n}_proj.lora_a.weight").T for n in ("gate", "up")]))
+            out[ml + "gating_einsum_lora_b"] = st(lambda i: np.stack([g(i, f"mlp.{n}_proj.lora_b.weight").T for n in ("gate", "up")]))
+            out[ml + "linear_lora_a"] = st(lambda i: g(i, "mlp.down_proj.lora_a.weight").T)
+            out[ml + "linear_lora_b"] = st(lambda i: g(i, "mlp.down_proj.lora_b.weight").T)
+            assert out[ml + "linear_lora_a"].shape == (L, F, r)
         for jn, tn in (("pre_attention_norm", "input_layernorm"), ("pre_ffw_norm", "post_attention_layernorm")):
             if ada:
                 out[f"{llm}layers/{jn}{sfx}/Dense_0/kernel"] = np.stack([g(i, tn + ".dense.weight").T for i in range(L)])

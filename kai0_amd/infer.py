@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from . import lora as lora_ops
 from .ops import BF16, F32, gemm, pick_split_k, round_up
 
 logger = logging.getLogger("kai0_amd")
@@ -76,7 +77,10 @@ class InferenceEngine:
     def __init__(self, model, batch: int, n_lang: int, n_cam: int):
         self.model = model
         pe = model.paligemma_with_expert
-        self.pe = pe
+        self._pe_src = pe  # the parameters themselves: what `_fingerprint` and the content stamp watch
+        # a LoRA model serves on merged weights W + s B A (kai0_amd.lora.merged_view): derived copies of this engine like the stacked
+        # ones below, rebuilt with it when a base weight or an adapter changes
+        self.pe = lora_ops.merged_view(pe) if lora_ops.has_adapters(pe) else pe
         self.B, self.T, self.ncam = batch, n_lang, n_cam
         self.n_img = pe.paligemma.model.vision_tower.vision_model.embeddings.num_patches
         self.P = n_cam * self.n_img + n_lang
@@ -190,9 +194,9 @@ class InferenceEngine:
         cached = getattr(self, "_fp_srcs", None)
         if cached is not None:  # per request: one pass over the tensor list, no module-tree walk (~0.1 ms instead of ~0.5 ms of host time)
             return (optim.WEIGHT_UPDATES[0], *((p.data_ptr(), p._version) for p in cached))
-        ex = self.pe.gemma_expert.model
-        vt = self.pe.paligemma.model.vision_tower.vision_model
-        lm = self.pe.paligemma.model.language_model
+        ex = self._pe_src.gemma_expert.model
+        vt = self._pe_src.paligemma.model.vision_tower.vision_model
+        lm = self._pe_src.paligemma.model.language_model
         srcs = [w for l in ex.layers for w in (l.self_attn.q_proj.weight, l.self_attn.k_proj.weight, l.self_attn.v_proj.weight,
                                                 l.mlp.gate_proj.weight, l.mlp.up_proj.weight, l.self_attn.o_proj.weight,
                                                 l.mlp.down_proj.weight)]  # fmt: skip
@@ -209,6 +213,9 @@ class InferenceEngine:
         else:  # pi0: the cached per-step time vectors are cut from action_time_mlp_in; the other heads are listed for the content stamp
             srcs += [w for l in ex.layers for w in (l.input_layernorm.weight, l.post_attention_layernorm.weight)] + [ex.norm.weight]
             srcs += [p for h in (m.state_proj, m.action_time_mlp_in, m.action_time_mlp_out) for p in (h.weight, h.bias)]
+        if self.pe is not self._pe_src:  # merged weights: cut from every adapted Linear's base weight (the prefix tower's others too) and adapters
+            srcs += [w for l in lm.layers for w in (l.self_attn.o_proj.weight, l.mlp.gate_proj.weight, l.mlp.up_proj.weight, l.mlp.down_proj.weight)]
+            srcs += [p for n, p in self._pe_src.named_parameters() if ".lora_" in n]
         self._fp_srcs = srcs  # (the parameter OBJECTS are stable: load_state_dict / optimizer steps / .to() change data_ptr or _version)
         return (optim.WEIGHT_UPDATES[0], *((p.data_ptr(), p._version) for p in srcs))
 

@@ -34,6 +34,7 @@ import torch
 from torch import nn
 
 from . import _lib, ops
+from . import lora as lora_ops
 from .config import Pi0Config, SiglipConfig, get_config
 from .preprocessing import IMAGE_KEYS, preprocess_observation
 
@@ -43,10 +44,21 @@ logger = logging.getLogger("kai0_amd")
 
 
 # ------------------------------------------------------------------------------------- parameter containers
-class Linear(nn.Module):
-    """nn.Linear-shaped parameter holder (weight [out, in], optional bias)."""
+class LoraWeight(nn.Module):
+    """One adapter matrix in nn.Linear layout: `weight` [out, in], normal(0, std) (lora.py:20 — lora_b is not zero either)."""
 
-    def __init__(self, in_features: int, out_features: int, bias: bool = True):
+    def __init__(self, in_features: int, out_features: int, std: float):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(out_features, in_features))
+        nn.init.normal_(self.weight, std=std)
+
+
+class Linear(nn.Module):
+    """nn.Linear-shaped parameter holder (weight [out, in], optional bias).  With `lora` = (LoRAConfig, scale, heads_up, heads_down)
+    it also holds the adapter pair `lora_a.weight` [N r, in / heads_down], `lora_b.weight` [out, r or N r] in the grouped layout of
+    kai0_amd.lora (N = the grouped side's head count); without it the module is exactly what it was."""
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = True, lora=None):
         super().__init__()
         self.in_features, self.out_features = in_features, out_features
         self.weight = nn.Parameter(torch.empty(out_features, in_features))
@@ -54,6 +66,18 @@ class Linear(nn.Module):
         nn.init.normal_(self.weight, std=0.02)
         if bias:
             nn.init.zeros_(self.bias)
+        self.lora = None
+        if lora is not None:
+            lc, scale, heads_up, heads_down = lora
+            if bias:
+                raise NotImplementedError("LoRA on a Linear with a bias")
+            n = max(heads_up, heads_down)
+            self.lora = (float(scale), heads_up, heads_down)
+            self.lora_a = LoraWeight(in_features // heads_down, n * lc.rank, lc.init_std)
+            self.lora_b = LoraWeight(n * lc.rank if heads_down > 1 else lc.rank, out_features, lc.init_std)
+
+    def adapter(self):
+        return lora_ops.Adapter(self.lora_a.weight, self.lora_b.weight, *self.lora)
 
 
 class Embedding(nn.Module):
@@ -94,11 +118,13 @@ class GemmaRMSNorm(nn.Module):
 
 
 class GemmaMLP(nn.Module):
-    def __init__(self, width: int, mlp_dim: int):
+    def __init__(self, width: int, mlp_dim: int, lora=None):
         super().__init__()
-        self.gate_proj = Linear(width, mlp_dim, bias=False)
-        self.up_proj = Linear(width, mlp_dim, bias=False)
-        self.down_proj = Linear(mlp_dim, width, bias=False)
+        # gating_einsum_lora_a / _b and linear_lora_a / _b (lora.py:109-121): dense, and no scale (`_dot`, :144-148, ignores alpha)
+        spec = None if lora is None else (lora, 1.0, 1, 1)
+        self.gate_proj = Linear(width, mlp_dim, bias=False, lora=spec)
+        self.up_proj = Linear(width, mlp_dim, bias=False, lora=spec)
+        self.down_proj = Linear(mlp_dim, width, bias=False, lora=spec)
 
 
 class GemmaAttention(nn.Module):
@@ -108,17 +134,22 @@ class GemmaAttention(nn.Module):
         self.num_heads = cfg.num_heads
         self.num_key_value_groups = cfg.num_heads // cfg.num_kv_heads
         self.scaling = cfg.head_dim**-0.5
-        self.q_proj = Linear(cfg.width, cfg.num_heads * cfg.head_dim, bias=False)
-        self.k_proj = Linear(cfg.width, cfg.num_kv_heads * cfg.head_dim, bias=False)
-        self.v_proj = Linear(cfg.width, cfg.num_kv_heads * cfg.head_dim, bias=False)
-        self.o_proj = Linear(cfg.num_heads * cfg.head_dim, cfg.width, bias=False)
+        # q_einsum / kv_einsum / attn_vec_einsum adapters (gemma.py:185-199): per head on q's output and o's input, scaled
+        lc = getattr(cfg, "lora_configs", {}).get("attn")
+        if lc is not None and cfg.num_kv_heads != 1:
+            raise NotImplementedError("LoRA with more than one KV head")
+        s, N = (lc.scaling_value if lc is not None else None), cfg.num_heads
+        self.q_proj = Linear(cfg.width, cfg.num_heads * cfg.head_dim, bias=False, lora=lc and (lc, s, N, 1))
+        self.k_proj = Linear(cfg.width, cfg.num_kv_heads * cfg.head_dim, bias=False, lora=lc and (lc, s, 1, 1))
+        self.v_proj = Linear(cfg.width, cfg.num_kv_heads * cfg.head_dim, bias=False, lora=lc and (lc, s, 1, 1))
+        self.o_proj = Linear(cfg.num_heads * cfg.head_dim, cfg.width, bias=False, lora=lc and (lc, s, 1, N))
 
 
 class GemmaDecoderLayer(nn.Module):
     def __init__(self, cfg, cond_dim):
         super().__init__()
         self.self_attn = GemmaAttention(cfg)
-        self.mlp = GemmaMLP(cfg.width, cfg.mlp_dim)
+        self.mlp = GemmaMLP(cfg.width, cfg.mlp_dim, getattr(cfg, "lora_configs", {}).get("ffn"))
         self.input_layernorm = GemmaRMSNorm(cfg.width, cond_dim=cond_dim)
         self.post_attention_layernorm = GemmaRMSNorm(cfg.width, cond_dim=cond_dim)
 
@@ -252,7 +283,23 @@ KEEP_F32_SELECTORS = (  # gemma_pytorch.py:72-79 (substring match; also catches 
 
 # ---------------------------------------------------------------------------------------- compute helpers
 def _lin(x, mod: Linear, residual=None, act=0):
+    if mod.lora is not None:
+        return lora_ops.lora_linear(x, mod.weight, mod.adapter(), residual)
     return ops.linear(x, mod.weight, mod.bias, residual, act)
+
+
+def _qkv(h, at):
+    ws = [at.q_proj.weight, at.k_proj.weight, at.v_proj.weight]
+    if at.q_proj.lora is not None:
+        return lora_ops.lora_linear_multi(h, ws, [at.q_proj.adapter(), at.k_proj.adapter(), at.v_proj.adapter()])
+    return ops.linear_multi(h, ws)
+
+
+def _mlp(h, mlp, residual=None):
+    ws = (mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight)
+    if mlp.gate_proj.lora is not None:
+        return lora_ops.lora_geglu_mlp(h, *ws, mlp.gate_proj.adapter(), mlp.up_proj.adapter(), mlp.down_proj.adapter(), residual=residual)
+    return ops.geglu_mlp(h, *ws, residual=residual)
 
 
 def build_mask_codes(pad_masks: torch.Tensor, att_masks: torch.Tensor):
@@ -421,9 +468,9 @@ class PaliGemmaWithExpertModel(nn.Module):
                 else:
                     mod1 = ops.linear_f32(cond, le.input_layernorm.dense.weight, le.input_layernorm.dense.bias)
                     xs, hs, gate1 = ops.adarms_res(xs, mod1, Hs, le.input_layernorm.eps)
-                qkv_s = ops.linear_multi(hs, [ae.q_proj.weight, ae.k_proj.weight, ae.v_proj.weight])
+                qkv_s = _qkv(hs, ae)
             xp, hp = ops.rmsnorm_res(xp, lp.input_layernorm.weight, lp.input_layernorm.eps)
-            qkv_p = ops.linear_multi(hp, [ap.q_proj.weight, ap.k_proj.weight, ap.v_proj.weight])
+            qkv_p = _qkv(hp, ap)
             if dual:
                 main.wait_stream(side)
                 hand(qkv_s, main)
@@ -436,12 +483,12 @@ class PaliGemmaWithExpertModel(nn.Module):
                 if cond is None:  # plain residuals, as on the prefix side
                     xs = _lin(att_s, ae.o_proj, residual=xs)
                     xs, hs = ops.rmsnorm_res(xs, le.post_attention_layernorm.weight, le.post_attention_layernorm.eps)
-                    xs = ops.geglu_mlp(hs, le.mlp.gate_proj.weight, le.mlp.up_proj.weight, le.mlp.down_proj.weight, residual=xs)
+                    xs = _mlp(hs, le.mlp, residual=xs)
                 else:
                     xs = ops.gated_residual(xs, _lin(att_s, ae.o_proj), gate1, Hs)
                     mod2 = ops.linear_f32(cond, le.post_attention_layernorm.dense.weight, le.post_attention_layernorm.dense.bias)
                     xs, hs, gate2 = ops.adarms_res(xs, mod2, Hs, le.post_attention_layernorm.eps)
-                    ys = ops.geglu_mlp(hs, le.mlp.gate_proj.weight, le.mlp.up_proj.weight, le.mlp.down_proj.weight)
+                    ys = _mlp(hs, le.mlp)
                     xs = ops.gated_residual(xs, ys, gate2, Hs)
             if last and _SKIP_DEAD_PREFIX:
                 # nothing reads the prefix stream after the last joint attention (the model's output is the suffix; the prefix's
@@ -452,7 +499,7 @@ class PaliGemmaWithExpertModel(nn.Module):
             # prefix: o_proj + residual fused in the GEMM epilogue, then RMSNorm -> GeGLU MLP -> residual
             xp = _lin(att_p, ap.o_proj, residual=xp)
             xp, hp = ops.rmsnorm_res(xp, lp.post_attention_layernorm.weight, lp.post_attention_layernorm.eps)
-            xp = ops.geglu_mlp(hp, lp.mlp.gate_proj.weight, lp.mlp.up_proj.weight, lp.mlp.down_proj.weight, residual=xp)
+            xp = _mlp(hp, lp.mlp, residual=xp)
             return xp, xs
 
         xp, xs = prefix, suffix

@@ -315,6 +315,20 @@ def build_model(config, device):
     return model
 
 
+def apply_freeze_filter(model, freeze_filter) -> int:
+    """`requires_grad_(False)` on every parameter whose state-dict name the filter freezes (TrainConfig.freeze_filter: LoRA fine-tuning
+    freezes the Gemma towers, Pi0Config.get_freeze_filter).  The Trainer, the AdamW engine and both shard modes only ever see
+    trainable parameters; frozen ones stay whole and resident on every rank.  Returns the number of frozen elements."""
+    if freeze_filter is None:
+        return 0
+    frozen = 0
+    for name, p in model.named_parameters(remove_duplicate=False):
+        if freeze_filter(name) and p.requires_grad:
+            p.requires_grad_(False)
+            frozen += p.numel()
+    return frozen
+
+
 def train_loop(config, *, device=None, shard_ops=None, model=None, log=None):
     """scripts/train_pytorch.py:309-633 over this framework's pieces.
 
@@ -354,6 +368,10 @@ def train_loop(config, *, device=None, shard_ops=None, model=None, log=None):
     if model is None:
         model = build_model(config, device)
     model.train()
+    frozen = apply_freeze_filter(model, config.freeze_filter)
+    if frozen:
+        trainable = sum(p.numel() for p in model.parameters() if p.requires_grad)
+        say(f"freeze_filter: {frozen / 1e6:.1f} M parameters frozen, {trainable / 1e6:.1f} M trained")
     sch, opt = config.lr_schedule, config.optimizer
     # `config.ema_decay` (0.99 in every kai0 entry) is what the reference's JAX trainer averages with; its torch trainer ignores it
     # (train_pytorch.py:510) and so does this loop unless KAI0_EMA=1, so that existing runs do not change

@@ -210,6 +210,16 @@ class LerobotARXDataConfig(LerobotAgilexDataConfig):
     _outputs_cls = agilex_policy.ARXOutputs
 
 
+class TrainableFilter:
+    """The complement of a freeze filter (None freezes nothing); picklable like the filter itself."""
+
+    def __init__(self, freeze):
+        self.freeze = freeze
+
+    def __call__(self, name: str) -> bool:
+        return self.freeze is None or not self.freeze(name)
+
+
 # ------------------------------------------------------------------------------------ config.py:656-757
 @dataclasses.dataclass(frozen=True)
 class TrainConfig:
@@ -246,6 +256,11 @@ class TrainConfig:
     fsdp_devices: int = 1
 
     @property
+    def trainable_filter(self):
+        """config.py:753 (`nnx.All(nnx.Param, nnx.Not(self.freeze_filter))`) over torch state-dict names: True = trained."""
+        return TrainableFilter(self.freeze_filter)
+
+    @property
     def assets_dirs(self) -> pathlib.Path:
         return (pathlib.Path(self.assets_base_dir) / self.name).resolve()
 
@@ -273,10 +288,16 @@ def _advantage_repack() -> _transforms.Group:
         "progress": "progress"})])  # fmt: skip
 
 
-def _kai0_task(name: str, factory, task_dir: str, prompt: str, *, awbc: bool) -> TrainConfig:
+def _lora_model(pi05: bool, paligemma: str, expert: str) -> dict:
+    """model / freeze_filter / ema_decay of a LoRA entry (config.py:879-899: the filter comes from the model config, EMA is off)."""
+    model = Pi0Config(pi05=pi05, paligemma_variant=paligemma, action_expert_variant=expert)
+    return dict(model=model, freeze_filter=model.get_freeze_filter(), ema_decay=None)
+
+
+def _kai0_task(name: str, factory, task_dir: str, prompt: str, *, awbc: bool, lora: bool = False) -> TrainConfig:
     sub = "advantage" if awbc else "base"
     return TrainConfig(
-        name=name, model=Pi0Config(pi05=True),
+        name=name, **(_lora_model(True, "gemma_2b_lora", "gemma_300m_lora") if lora else dict(model=Pi0Config(pi05=True))),
         data=factory(repo_id=f"<path_to_repo_root>/data/{task_dir}/{sub}", default_prompt=prompt, use_delta_joint_actions=False,
                      base_config=DataConfig(prompt_from_task=True) if awbc else None),
         weight_loader=CheckpointWeightLoader("<path/to/pi05_base/checkpoint>"),
@@ -290,8 +311,15 @@ _CONFIGS = [
     TrainConfig(name="debug_pi05", model=Pi0Config(pi05=True, paligemma_variant="dummy", action_expert_variant="dummy"),
                 data=FakeDataConfig(), batch_size=2, num_train_steps=10, overwrite=True, exp_name="debug_pi05",
                 wandb_enabled=False),  # fmt: skip
+    # LoRA (project-only tiny variant "dummy_lora" on both towers: adapters trained, the Gemma towers frozen)
+    TrainConfig(name="debug_lora", data=FakeDataConfig(), batch_size=2, **_lora_model(False, "dummy_lora", "dummy_lora"), save_interval=100,
+                overwrite=True, exp_name="debug_lora", num_train_steps=10, wandb_enabled=False),  # fmt: skip
+    TrainConfig(name="debug_pi05_lora", data=FakeDataConfig(), batch_size=2, **_lora_model(True, "dummy_lora", "dummy_lora"),
+                num_train_steps=10, overwrite=True, exp_name="debug_pi05_lora", wandb_enabled=False),  # fmt: skip
     # normal pi0.5 full fine-tuning (config.py:1176-1218)
     _kai0_task("pi05_flatten_fold_normal", LerobotAgilexDataConfig, "FlattenFold", "Flatten and fold the cloth.", awbc=False),
+    # its low-memory twin: gemma_2b_lora / gemma_300m_lora with the towers frozen (the recipe of config.py:879-899 on this task)
+    _kai0_task("pi05_flatten_fold_lora", LerobotAgilexDataConfig, "FlattenFold", "Flatten and fold the cloth.", awbc=False, lora=True),
     _kai0_task("pi05_tee_shirt_sort_normal", LerobotAgilexDataConfig, "TeeShirtSort",
                "Fetch the clothes, fold the tee shirts and hand-over the collared shirts.", awbc=False),
     _kai0_task("pi05_hang_cloth_normal", LerobotARXDataConfig, "HangCloth", "Fetch and hang the cloth.", awbc=False),
