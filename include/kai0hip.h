@@ -727,6 +727,32 @@ int kai0_lora_wgrad(const void* P, int64_t ldp, const void* Q, int64_t ldq, void
                     int transposed, int out_f32, void* workspace, int64_t workspace_bytes, kai0_stream_t stream);
 int64_t kai0_lora_wgrad_workspace_bytes(int M, int R, int C);
 
+/* Stage-Advantage annotation (stage_advantage/annotation/evaluator.py): the device-side image preparation and prefix assembly of
+ * kai0_amd.stage_advantage.ValueAnnotator.
+ * kai0_frames_to_chw replaces the evaluator's `_process_single_image` (evaluator.py:151-165: `float() / 255.0`, `* 2.0 - 1.0`,
+ * image_tools.resize_with_pad_torch(..., 224, 224), HWC -> CHW) for N frames at once:
+ *   frames uint8 [N][H0][W0][3] -> out f32 [N][3][H][W].  The caller computes resize_with_pad_torch's geometry in double precision
+ *   (ratio = max(W0 / W, H0 / H); rh = (int)(H0 / ratio), rw = (int)(W0 / ratio); ph0 = (H - rh) / 2, pw0 = (W - rw) / 2) and passes
+ *   it in.  Outside rows [ph0, ph0 + rh) x columns [pw0, pw0 + rw) the value is -1.0f.  Inside, with v(u) = u / 255.0f * 2.0f - 1.0f,
+ *     src = max(fmaf(scale, dst + 0.5f, -0.5f), 0), scale = (float)H0 / (float)rh;  i0 = min((int)src, H0 - 1), i1 = min(i0 + 1, H0 - 1),
+ *     l = src - i0  (F.interpolate(mode="bilinear", align_corners=False) taps, likewise along x);
+ *     w00 = (1 - ly) * (1 - lx), w01 = (1 - ly) * lx, w10 = ly * (1 - lx), w11 = ly * lx;
+ *     out = clamp(fmaf(w11, v11, fmaf(w10, v10, fmaf(w00, v00, w01 * v01))), -1, 1),
+ *   the fused multiply-adds being the ones torch's CPU kernel contracts when it does not split the image over threads (bit-identical
+ *   to it then; <= 2e-7 from its multi-threaded form), every other operation rounded to f32 on its own.
+ *   Any H0, W0 >= 1; rh or rw = 0 gives an all -1 image. */
+int kai0_frames_to_chw(const uint8_t* frames, float* out, int N, int H0, int W0, int H, int W, int rh, int rw, int ph0, int pw0,
+                       kai0_stream_t stream);
+/* kai0_prefix_gather replaces the per-(timestep, camera) kai0_copy_rows_bf16 calls and the torch.cat of image batches with which
+ * embed_prefix (pi0_pytorch.py:186-235, `torch.cat(embs, dim=1)`) assembles [images | prompt]: the image blocks come out of a
+ * resident bank of per-frame features by a slot table.
+ *   bank bf16 [cap][n_img][D], slots int32 [B][nslot] (device), lang bf16 rows of D, out bf16 [B][nslot * n_img + T][D]:
+ *     out[b][s * n_img + r] = bank[slots[b][s]][r];   out[b][nslot * n_img + t] = lang[b * lang_bs + t]
+ *   lang_bs counts rows (0: one prompt for the whole batch).  D a multiple of 8; bank, lang and out 16-byte aligned; T = 0 and
+ *   nslot = 0 are allowed.  The slots are NOT checked on the device: the caller guarantees 0 <= slot < cap. */
+int kai0_prefix_gather(const void* bank, const int32_t* slots, const void* lang, void* out, int B, int nslot, int n_img, int T, int D,
+                       int64_t lang_bs, kai0_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

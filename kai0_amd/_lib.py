@@ -213,6 +213,8 @@ _PROTOS: dict[str, list] = {
     "kai0_multi_dot": [c_p, c_i, C.POINTER(c_p), c_i, c_i, c_i64, c_p, c_p, c_p],
     "kai0_lora_down": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_p],
     "kai0_lora_wgrad": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_f, c_i, c_i, c_p, c_i64, c_p],
+    "kai0_frames_to_chw": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "kai0_prefix_gather": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i64, c_p],
 }  # fmt: skip
 
 EXPORTED_SYMBOLS = ("kai0_last_error", "kai0_skinny_workspace_bytes", "kai0_attn_decode_workspace_bytes", "kai0_gemm_f32_workspace_bytes",

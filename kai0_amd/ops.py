@@ -1799,6 +1799,73 @@ def rtc_update_(x, v, err, jte, t: float, g: float, dt: float):
     return x
 
 
+def resize_geometry(h0: int, w0: int, height: int, width: int) -> tuple[int, int, int, int]:
+    """(rh, rw, ph0, pw0) of `resize_with_pad_torch` (shared/image_tools.py:55-126), in Python floats exactly as it computes them."""
+    ratio = max(w0 / width, h0 / height)
+    rh, rw = int(h0 / ratio), int(w0 / ratio)
+    return rh, rw, (height - rh) // 2, (width - rw) // 2
+
+
+def frames_to_chw(frames: torch.Tensor, height: int, width: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """kai0_frames_to_chw: uint8 [N, H0, W0, 3] camera frames -> f32 [N, 3, height, width] in [-1, 1]: the evaluator's
+    `_process_single_image` (u8 / 255 * 2 - 1, resize_with_pad_torch with bilinear align_corners=False taps, -1 padding, HWC -> CHW)."""
+    if not frames.is_cuda:
+        raise _lib.Kai0HipError("frames_to_chw: expected a CUDA (HIP) tensor; the product path has no CPU fallback")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise TypeError(f"frames_to_chw: frames must be a contiguous uint8 [N, H0, W0, 3] tensor, got {frames.dtype} {tuple(frames.shape)}")
+    n, h0, w0, _ = frames.shape
+    if h0 < 1 or w0 < 1 or height < 1 or width < 1:
+        raise ValueError(f"frames_to_chw: empty image ({h0} x {w0} -> {height} x {width})")
+    rh, rw, ph0, pw0 = resize_geometry(h0, w0, height, width)
+    if rh < 1 or rw < 1:  # F.interpolate refuses an output size of 0 as well
+        raise ValueError(f"frames_to_chw: a {h0} x {w0} frame resized into {height} x {width} keeps no pixel ({rh} x {rw})")
+    if out is None:
+        out = torch.empty((n, 3, height, width), dtype=F32, device=frames.device)
+    elif out.dtype != F32 or not out.is_contiguous() or tuple(out.shape) != (n, 3, height, width) or out.device != frames.device:
+        raise TypeError(f"frames_to_chw: out must be a contiguous f32 [{n}, 3, {height}, {width}] tensor on {frames.device}")
+    _lib.call("kai0_frames_to_chw", frames.data_ptr(), out.data_ptr(), n, h0, w0, height, width, rh, rw, ph0, pw0, _stream())
+    return out
+
+
+def prefix_gather(bank: torch.Tensor, slots, lang: torch.Tensor | None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """kai0_prefix_gather: out[b][s * n_img + r] = bank[slots[b][s]][r], out[b][nslot * n_img + t] = lang[b][t] (lang [T, D]: one prompt
+    for the whole batch; [B, T, D]: per sample; None: no prompt rows) -> bf16 [B, nslot * n_img + T, D].
+    `slots` is a HOST table (nested list / numpy / CPU tensor) [B, nslot]: it is validated against the bank here (the kernel trusts it) and
+    uploaded; nothing is launched for an invalid table."""
+    _chk(bank, BF16, "prefix_gather.bank")
+    if bank.dim() != 3:
+        raise ValueError(f"prefix_gather: bank must be [cap, n_img, D], got {tuple(bank.shape)}")
+    cap, n_img, D = bank.shape
+    if isinstance(slots, torch.Tensor) and slots.is_cuda:
+        raise TypeError("prefix_gather: the slot table must live on the host (it is validated before the upload)")
+    table = torch.as_tensor(slots, dtype=torch.int64)
+    if table.dim() != 2:
+        raise ValueError(f"prefix_gather: slots must be [B, nslot], got {tuple(table.shape)}")
+    B, nslot = table.shape
+    if table.numel() and (int(table.min()) < 0 or int(table.max()) >= cap):
+        raise IndexError(f"prefix_gather: slot {int(table.min()) if int(table.min()) < 0 else int(table.max())} outside the bank's {cap} frames")
+    if D % 8 != 0:
+        raise ValueError(f"prefix_gather: D = {D} must be a multiple of 8")
+    T, lang_bs = 0, 0
+    if lang is not None:
+        _chk(lang, BF16, "prefix_gather.lang")
+        if lang.dim() not in (2, 3) or lang.shape[-1] != D or (lang.dim() == 3 and lang.shape[0] != B):
+            raise ValueError(f"prefix_gather: lang {tuple(lang.shape)} is neither [T, {D}] nor [{B}, T, {D}]")
+        T = lang.shape[-2]
+        lang_bs = T if lang.dim() == 3 else 0
+    P = nslot * n_img + T
+    if out is None:
+        out = torch.empty((B, P, D), dtype=BF16, device=bank.device)
+    else:
+        _chk(out, BF16, "prefix_gather.out")
+        if tuple(out.shape) != (B, P, D):
+            raise ValueError(f"prefix_gather: out must be [{B}, {P}, {D}], got {tuple(out.shape)}")
+    dev_slots = table.to(torch.int32).contiguous().to(bank.device)
+    _lib.call("kai0_prefix_gather", bank.data_ptr(), dev_slots.data_ptr(), _p(lang) if T else None, out.data_ptr(), B, nslot, n_img, T, D,
+              lang_bs, _stream())  # fmt: skip
+    return out
+
+
 def sqrt_scale(dim: int) -> float:
     """`math.sqrt(dim)` as the f32 scalar torch multiplies a bf16 tensor by."""
     return float(torch.tensor(math.sqrt(dim), dtype=torch.float32))
