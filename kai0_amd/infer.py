@@ -11,14 +11,18 @@ MI355X-first choices:
     37 adaRMS modulations for ALL steps are computed as M = steps*B row GEMMs (0.46 GB of f32 `dense` weights are
     read once instead of once per step) — and, being a function of the weights and the schedule only (no request input
     enters: sincos(t) -> time MLP -> `dense`), ONCE PER ENGINE, not per request: the engine is dropped whenever a weight
-    changes (`_fingerprint`), so the table is constant for its lifetime, like the RoPE inverse frequencies
-    (round 5: the switch that recomputed it inside every call is gone — one way to do it);
+    changes (`_fingerprint`), so the table is constant for its lifetime, like the RoPE inverse frequencies.  Everything of this
+    kind lives in ONE record per schedule (`_schedule`), built on the schedule's first run, outside graph capture;
   * the last prefix layer stops after its K/V projection — nothing reads its attention/MLP output;
   * the whole call (SigLIP -> prefix -> all denoise steps) is recorded once into a hipGraph
-    (torch.cuda.CUDAGraph on ROCm is hipGraph) and replayed per request: no per-op Python or launch cost;
+    (torch.cuda.CUDAGraph on ROCm is hipGraph) and replayed per request: no per-op Python or launch cost (`_Capture`);
+  * one Euler driver, `_run`: schedule record, prefix pass, then either the production stack (`fast`: folded weights, in-block
+    kernels, one-launch step seams — `_seams_pi05` / `_seams_pi0`) or the generic per-layer step `_denoise_step` over the plain GEMM;
   * pi0 (`pi05=False`): `state` is a request input (a static buffer of the graph), the suffix has Hs + 1 rows per
     sample (state token | action tokens, mask codes 0 / 1 / 2), the time half of `action_time_mlp_in` is hoisted per step like the
-    modulation table, and the expert's plain RMSNorms run through the same folded stack as the constant modulation [w | 0 | 1];
+    modulation table, and the expert's plain RMSNorms run through the same folded stack as the constant modulation [w | 0 | 1].
+    The generic step is the same function for both variants: what differs (rows per sample, the suffix embedding, the norm, the
+    gate) is data;
   * real-time chunking: a request with a previous chunk runs the guided loop `_run_guided` — per Euler step one
     forward of the generic per-layer step that keeps what its backward needs, an explicit reverse sweep over the training backward's
     entry points (`_denoiser_vjp`) and two f32 seam kernels — captured into a hipGraph of its own; the unguided graph is not touched.
@@ -28,6 +32,7 @@ from __future__ import annotations
 
 import logging
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -38,16 +43,14 @@ from .ops import BF16, F32, gemm, pick_split_k, round_up
 
 logger = logging.getLogger("kai0_amd")
 # split-K of the prefix pass's q|k|v, o_proj and down_proj GEMMs ("q,o,d"; 0 = ops.pick_split_k).  Swept on MI355X at B = 1
-# (a round-2 sweep script, in the git history): 1,1,6 -> prefix pass 6.52 ms; the automatic rule 6.80; everything else within 0.1-0.25 ms.  Round 3: with
-# the post-attention RMSNorm inside o_proj's reduction launch (kai0hip.h norm_kind) a split o_proj costs no extra launch: 1,2,6 ->
-# 5.56 against 5.68 ms for 1,1,6 (3 and 4: 5.58 / 5.59)
+# (profiles/HISTORY.md): with the post-attention RMSNorm inside o_proj's reduction launch (kai0hip.h norm_kind) a split o_proj costs
+# no extra launch: 1,2,6 -> prefix pass 5.56 ms against 5.68 for 1,1,6 (o = 3 and 4: 5.58 / 5.59); the automatic rule is 0.3 ms slower
 _PREFIX_SPLITS = [int(x) for x in os.environ.get("KAI0_PREFIX_SPLITS", "1,2,6").split(",")]
-# split-K of the SigLIP tower's two narrow-output Linears at B = 1 (M = 3 x 256 rows; (M, N, K) -> split), swept on MI355X in round 5
-# (one gpurun call, p50 of the tower): out_proj 54 tiles x 18 K-tiles unsplit + a LayerNorm launch -> three chunks with the norm inside the
-# reduction launch; fc2 (K = 4304) five chunks on the two-stage configuration (270 blocks) -> four (216 blocks, <= one per CU: the
-# four-stage loop): tower 2.97 -> 2.77 ms.  Round 6 (eight-wave 128 x 128 tile, tower 2.54 ms): re-swept — (1 | 2, 4), (3, 2 | 3 | 6) all within
-# +0.01 ... +0.27 ms of (3, 4); prefix "1,1,6" / "1,2,8" / "1,2,4" +0.05 ... +0.1 ms against "1,2,6"; the persistent kernel for the 512-tile
-# pair GEMM +0.16 ms (one gpurun call, tools/infer_ab.sh)
+# split-K of the SigLIP tower's two narrow-output Linears at B = 1 (M = 3 x 256 rows; (M, N, K) -> split), swept on MI355X (p50 of
+# the tower, profiles/HISTORY.md): out_proj 54 tiles x 18 K-tiles unsplit + a LayerNorm launch -> three chunks with the norm inside the
+# reduction launch; fc2 (K = 4304) four chunks (216 blocks, <= one per CU: the four-stage loop).  On the eight-wave 128 x 128 tile every
+# other choice — (1 | 2, 4), (3, 2 | 3 | 6) — is +0.01 ... +0.27 ms against (3, 4), and prefix "1,1,6" / "1,2,8" / "1,2,4" +0.05 ... +0.1 ms
+# against "1,2,6"
 _B1_SPLITS = {(768, 1152, 1152): 3, (768, 1152, 4304): 4}
 
 
@@ -107,8 +110,7 @@ class InferenceEngine:
         # The production denoise stack (`fast`): weight-streaming in-block kernels with fused RoPE / GeGLU / gated-residual epilogues,
         # adaRMS folded into per-step weights, one-launch step seams, the two-launch decode attention — for the shapes it was built for
         # (few denoise rows, the pi0.5 widths, <= 1024 keys).  Anything else (the tiny test models, other widths) runs the generic
-        # per-layer path `_denoise_step` over the plain GEMM.  Round 5: the two superseded stacks (split-K partials + combine launches;
-        # adaRMS as a projection prologue) and their switches are gone.
+        # per-layer path `_denoise_step` over the plain GEMM.
         ecfg = pe.exp_cfg
         self.F = ecfg.mlp_dim
         # pi0 takes the same stack: a plain GemmaRMSNorm is the adaRMS arithmetic with the constant modulation [w | 0 | 1] (`_build_fast`)
@@ -118,20 +120,20 @@ class InferenceEngine:
         if self.fast:
             self._build_fast()
         self._build_stacked()
-        self._times_dev = {}
         # the norm behind a split-K Linear of the SigLIP / prefix passes runs inside that Linear's reduction launch
         self.fuse_norm = bool(self.fuse_split_norm)
-        self._mods_cache = {}
-        self._fold_cache = {}
-        self._graph = None
-        self._graph_steps = None
-        self._static_in = None
-        self._static_out = None
-        # real-time chunking: the guided chunk's own graph and static buffers (sample_actions_guided)
-        self._guided_mods = {}
+        self._schedules = {}  # tuple(times) -> the schedule's record (`_schedule`)
+        self._cap = self._graph_steps = None  # the captured chunk (`_Capture`) and the step count baked into it
+        # real-time chunking: the guided chunk's own capture, its key, and the previous chunk / prefix weights it reads
+        self._g_cap = self._g_graph_key = None
         self._g_prev = self._g_w = None
-        self._g_graph = self._g_graph_key = self._g_static_in = self._g_static_out = None
         self._content_init()
+
+    # what tests, tools and the benchmark read of the captures
+    _graph = property(lambda self: self._cap.graph if self._cap else None)
+    _static_in = property(lambda self: self._cap.inputs if self._cap else None)
+    _static_out = property(lambda self: self._cap.out if self._cap else None)
+    _g_graph = property(lambda self: self._g_cap.graph if self._g_cap else None)
 
     def compatible(self, batch, n_lang, n_cam):
         return self.shape_matches(batch, n_lang, n_cam) and self.weights_unchanged()
@@ -142,7 +144,7 @@ class InferenceEngine:
     def weights_unchanged(self) -> bool:
         """The tensors the derived copies were cut from are the ones they were cut from (storage, autograd version, optimizer updates) and
         no completed chunk has stamped different contents.  ~0.13 ms of host time over ~470 tensors: `model.sample_actions` runs it AFTER
-        it has queued the graph replay (round 6), so the check overlaps the chunk instead of standing in front of it; a mismatch discards
+        it has queued the graph replay, so the check overlaps the chunk instead of standing in front of it; a mismatch discards
         that replay's result."""
         return self._weights_tag == self._fingerprint() and self._content_ok()
 
@@ -230,7 +232,7 @@ class InferenceEngine:
         lm = self.pe.paligemma.model.language_model
         self.lm_wqkv = [torch.cat([l.self_attn.q_proj.weight, l.self_attn.k_proj.weight, l.self_attn.v_proj.weight], 0).contiguous()
                         for l in lm.layers]  # fmt: skip
-        # round 5: RoPE in the epilogue of the prefix pass's q|k|v GEMM (kai0hip.h act 7) where that GEMM runs on 128-column tiles (the
+        # RoPE in the epilogue of the prefix pass's q|k|v GEMM (kai0hip.h act 7) where that GEMM runs on 128-column tiles (the
         # B = 1 pass: 18 launches of ~10 us fewer per chunk).  The rotation's partners (columns j, j + 128 of a head) must meet in one
         # tile, so the stacked copy of every layer but the last (which only projects K / V) is kept with its rows permuted instead.
         NQ = self.H * self.HD
@@ -240,11 +242,26 @@ class InferenceEngine:
             for l in range(self.L - 1):
                 self.lm_wqkv[l] = self.lm_wqkv[l][perm].contiguous()
 
+    def _gemm_norm(self, a, w, out, norm, plain: bool, **kw):
+        """gemm(a, w, out [M, N], **kw), then the norm that reads `out`, norm = (kind, weight, bias | None, eps) or None: inside the
+        split-K reduction launch (kai0hip.h norm_kind) when the contraction is split and the epilogue is `plain` (the caller's own
+        term), otherwise as a launch of its own.  Returns out, or (out, norm(out))."""
+        M, N = out.shape
+        fused = None
+        if norm is not None and self.fuse_norm and kw["split_k"] > 1 and N <= 2048 and N % 8 == 0 and plain:
+            kind, nw, nb, neps = norm
+            fused = (kind, torch.empty((M, N), dtype=BF16, device=self.dev), nw, nb, neps)
+        gemm(a, w, out, norm=fused, **kw)
+        if norm is None:
+            return out
+        if fused is not None:
+            return out, fused[1]
+        kind, nw, nb, neps = norm
+        return out, (ops.rmsnorm(out, nw, neps) if kind == 1 else ops.layernorm(out, nw, nb, neps))
+
     def _lin(self, x, w, *, bias=None, residual=None, act=0, split=None, aux1=None, norm=None, out=None):
         """flat Linear for the prefix / SigLIP passes: launches matter more than occupancy here, so the contraction is
-        only split when there are fewer than ~100 output tiles.
-        norm = (kind, weight, bias | None, eps): the norm that reads this Linear's output — returns (out, norm(out)); when the
-        contraction is split, the norm runs inside the split-K reduction launch (kai0hip.h norm_kind), otherwise as its own launch."""
+        only split when there are fewer than ~100 output tiles.  norm: the norm that reads this Linear's output (`_gemm_norm`)."""
         M, K = x.shape
         N = w.shape[0]
         if split is None:
@@ -252,18 +269,8 @@ class InferenceEngine:
             split = _B1_SPLITS.get((M, N, K)) or (1 if tiles >= 100 else pick_split_k(M, N, K))
         if out is None:
             out = torch.empty((M, N), dtype=BF16, device=self.dev)
-        fused = None
-        if norm is not None and self.fuse_norm and split > 1 and N <= 2048 and N % 8 == 0 and act == 0:
-            kind, nw, nb, neps = norm
-            fused = (kind, torch.empty((M, N), dtype=BF16, device=self.dev), nw, nb, neps)
-        gemm(x, w, out, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, bias=bias, residual=residual, ldr=N, act=act, aux1=aux1,
-             split_k=split, norm=fused)
-        if norm is None:
-            return out
-        if fused is not None:
-            return out, fused[1]
-        kind, nw, nb, neps = norm
-        return out, (ops.rmsnorm(out, nw, neps) if kind == 1 else ops.layernorm(out, nw, nb, neps))
+        return self._gemm_norm(x, w, out, norm, act == 0, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, bias=bias, residual=residual, ldr=N,
+                               act=act, aux1=aux1, split_k=split)  # fmt: skip
 
     def _siglip(self, image, out=None):
         """SigLIP tower for inference (modeling_siglip.py:271-281,325-460,756-778): stacked q|k|v projection, attention
@@ -303,7 +310,7 @@ class InferenceEngine:
         return self._lin(x, proj.weight, bias=proj.bias, out=out).view(n, S, -1)  # (`out`: the prefix buffer's image rows, B = 1)
 
     def _embed_prefix(self, images, img_masks, lang_tokens, lang_masks):
-        """PI0Pytorch.embed_prefix (pi0_pytorch.py:186-235) over the inference SigLIP tower -> the flat prefix [B * P, D].  Round 6: no
+        """PI0Pytorch.embed_prefix (pi0_pytorch.py:186-235) over the inference SigLIP tower -> the flat prefix [B * P, D].  No
         assembly copies — the prompt embedding is gathered straight into its rows of the prefix buffer (kai0_embed_gather's row offset /
         strides) and, at B = 1 (where camera-major == sequence order), the projector GEMM writes the image rows there too; the pad / att
         masks are not materialised (kai0_prefix_codes, `_prefix_pass`)."""
@@ -373,7 +380,7 @@ class InferenceEngine:
                          q_off=q0 * H * HD, o_off=q0 * H * HD)
             return
         if not want_probs and B == 1 and self.key_split and Sq > 128 and HD == 256 and Sk % 4 == 0 and Sk >= 512 and q0 == 0:
-            # the B = 1 prefix pass (round 5): the one-pass kernel over four key ranges (244 blocks instead of 61) + the lse-weighted
+            # the B = 1 prefix pass: the one-pass kernel over four key ranges (244 blocks instead of 61) + the lse-weighted
             # merge — two launches and no logits / probabilities in memory instead of logits GEMM, softmax, split-K P V (+ reduce)
             ops.attn_fwd_keysplit(self.q_buf, self.k_cache[l], self.v_cache[l], self.att_buf, rows=M, Sk=Sk, HD=HD, H=H, q0=q0, ldk=HD, ldv=HD,
                                   qcode=qcode[0], kcode=kcode[0], scale=HD**-0.5, q_off=q0 * H * HD, o_off=q0 * H * HD, parts=4)
@@ -398,27 +405,20 @@ class InferenceEngine:
 
     def _oproj(self, lin, rows_pb: int, row0: int, residual, gate=None, norm=None):
         """y = att_buf[b, row0 + r] @ Wo^T (+gate) + residual, reading the padded buffer through the A row remap.
-        norm = (kind, weight, bias | None, eps): returns (y, norm(y)), the norm inside the split-K reduction when there is one."""
+        norm: the norm that reads y (`_gemm_norm`)."""
         B, H, HD = self.B, self.H, self.HD
         M = B * rows_pb
         N = lin.weight.shape[0]
         out = torch.empty((M, N), dtype=BF16, device=self.dev)
         split = (_PREFIX_SPLITS[1] if M > 128 else 0) or pick_split_k(M, N, H * HD)
-        fused = None
-        if norm is not None and self.fuse_norm and split > 1 and N <= 2048 and N % 8 == 0 and gate is None:
-            fused = (norm[0], torch.empty((M, N), dtype=BF16, device=self.dev), norm[1], norm[2], norm[3])
-        gemm(self.att_buf, lin.weight, out, M=M, N=N, K=H * HD, lda=H * HD, ldb=H * HD, ldc=N,
-             a_map=(rows_pb, self.S_ld, row0), residual=residual, ldr=N, gate=gate, gate_rpb=rows_pb, gate_ld=N,
-             split_k=split, norm=fused)  # fmt: skip
-        if norm is None:
-            return out
-        if fused is not None:
-            return out, fused[1]
-        return out, (ops.rmsnorm(out, norm[1], norm[3]) if norm[0] == 1 else ops.layernorm(out, norm[1], norm[2], norm[3]))
+        return self._gemm_norm(self.att_buf, lin.weight, out, norm, gate is None, M=M, N=N, K=H * HD, lda=H * HD, ldb=H * HD, ldc=N,
+                               a_map=(rows_pb, self.S_ld, row0), residual=residual, ldr=N, gate=gate, gate_rpb=rows_pb, gate_ld=N,
+                               split_k=split)  # fmt: skip
 
     # ------------------------------------------------------------------------------------------------ passes
     def _prefix_pass(self, images, img_masks, lang_tokens, lang_masks):
-        model, pe = self.model, self.pe
+        """Prefix rows through the PaliGemma tower into the static K / V caches; leaves the request's mask codes, position ids and the
+        RoPE inverse frequencies on the engine for the denoise steps."""
         B, P, Hs = self.B, self.P, self.Hs
         prefix = self._embed_prefix(images, img_masks, lang_tokens, lang_masks)
         # mask codes and position ids of the whole request (prefix + action tokens) in one launch: what build_mask_codes makes of
@@ -428,9 +428,8 @@ class InferenceEngine:
         self.qcode, self.kcode, self.pos = qcode, kcode, pos
         self.pos_prefix = pos[:, :P].contiguous()
         self.pos_suffix = pos[:, P:].contiguous()
-        lm = pe.paligemma.model.language_model
-        self._inv_freq = lm.rope_inv_freq()
-        inv_freq = lm.rope_inv_freq()
+        lm = self.pe.paligemma.model.language_model
+        self._inv_freq = inv_freq = lm.rope_inv_freq()
         H, HD, S_ld = self.H, self.HD, self.S_ld
         xp = prefix.reshape(B * P, self.Dp)
         NQ = H * HD
@@ -472,12 +471,42 @@ class InferenceEngine:
             xp, hp = self._lin(hmid, layer.mlp.down_proj.weight, residual=xp, norm=(1, nxt.weight, None, nxt.eps),
                                split=_PREFIX_SPLITS[2] or pick_split_k(M, self.Dp, hmid.shape[1]))
 
-    def _modulations(self, times: list[float]):
-        """time embedding -> time MLP -> adaRMS `dense` for every layer and step at once (rows = step*B + b): one f32 GEMM over
-        the 37 stacked `dense` weights.  Returns per-layer views (row stride 37 * 3 De) and the final norm's."""
+    def _schedule(self, times: list[float]):
+        """The record of one Euler schedule: everything that is a function of the weights and the time values only — the engine is
+        dropped when a weight changes, so it is kept for the engine's lifetime.  Built on the schedule's first (warm-up) run, OUTSIDE
+        graph capture (the time values reach the device by a host-to-device copy).  Fields: pi0.5 — `times_dev` f32 [steps B], the
+        modulation table `mods` / `mf` (`_modulations`); production stack: its row stride `mod_ld`, the bf16 `gates`, the `folded`
+        per-step weights, and `guided` (contiguous `mods` / `mf` for the guided loop, made when first asked for); pi0 — `tvec`,
+        `w_act` (`_time_vectors`)."""
+        sch = self._schedules.get(tuple(times))
+        if sch is None:
+            sch = self._schedules[tuple(times)] = SimpleNamespace(times_dev=None, mods=None, mf=None, mod_ld=None, gates=None, folded=None,
+                                                                  guided=None, tvec=None, w_act=None)  # fmt: skip
+            if self.pi05:
+                sch.times_dev = torch.tensor(times, dtype=F32).repeat_interleave(self.B).to(self.dev)
+                sch.mods, sch.mf, sch.mod_ld, sch.gates = self._modulations(sch.times_dev, len(times))
+                if self.fast:
+                    sch.folded = self._fold_modulations(sch.mods, len(times))
+            else:
+                sch.tvec, sch.w_act = self._time_vectors(times)
+        return sch
+
+    def _guided_schedule(self, times: list[float]):
+        """`mods` / `mf` of a schedule for the guided loop, which runs the generic per-layer step on every engine: contiguous
+        [steps B, 3 De] modulation rows per norm (the production stack keeps them as column slices of one table)."""
+        sch = self._schedule(times)
+        if not self.fast:
+            return sch
+        if sch.guided is None:
+            sch.guided = SimpleNamespace(mods=[(a.contiguous(), b.contiguous()) for a, b in sch.mods], mf=sch.mf.contiguous())
+        return sch.guided
+
+    def _modulations(self, tt, n: int):
+        """time embedding -> time MLP -> adaRMS `dense` for every layer and step at once (rows = step*B + b; tt: the n steps' time
+        values, each B times).  -> (mods, mf, mod_ld, gates): per-layer (input norm, post-attention norm) modulations and the final
+        norm's.  Production stack: one f32 GEMM over the 37 stacked `dense` weights, mods / mf its column views of row stride mod_ld,
+        gates its bf16 cast (`_gate`); generic path: one GEMM per norm, no mod_ld / gates."""
         model, B, De = self.model, self.B, self.De
-        n = len(times)
-        tt = self._times_dev[tuple(times)]
         te = torch.empty((n * B, De), dtype=F32, device=self.dev)
         _lib.call("kai0_time_sincos", tt.data_ptr(), te.data_ptr(), n * B, De, 4e-3, 4.0, ops._stream())
         x = ops.silu_f32(ops.linear_f32(te, model.time_mlp_in.weight, model.time_mlp_in.bias))
@@ -487,13 +516,12 @@ class InferenceEngine:
             mods = [(ops.linear_f32(cond, l.input_layernorm.dense.weight, l.input_layernorm.dense.bias),
                      ops.linear_f32(cond, l.post_attention_layernorm.dense.weight, l.post_attention_layernorm.dense.bias))
                     for l in ex.layers]  # fmt: skip
-            return mods, ops.linear_f32(cond, ex.norm.dense.weight, ex.norm.dense.bias)
+            return mods, ops.linear_f32(cond, ex.norm.dense.weight, ex.norm.dense.bias), None, None
         allm = ops.linear_f32(cond, self.w_mod, self.b_mod)  # [n*B, 37 * 3 De]
-        self._mod_ld = allm.shape[1]
-        self._gates = ops.cast(allm, BF16)  # gate = bf16(third chunk): taken as views, row stride _mod_ld
+        gates = ops.cast(allm, BF16)  # gate = bf16(third chunk): taken as views, row stride mod_ld
         W3 = 3 * De
         mods = [(allm[:, (2 * l) * W3 : (2 * l + 1) * W3], allm[:, (2 * l + 1) * W3 : (2 * l + 2) * W3]) for l in range(self.L)]
-        return mods, allm[:, 2 * self.L * W3 :]
+        return mods, allm[:, 2 * self.L * W3 :], allm.shape[1], gates
 
     def _fold_modulations(self, mods, n_steps: int):
         """The adaRMS norms in front of the expert's q|k|v and gate|up projections, folded into the weights (kai0hip.h rowsq_in): the
@@ -519,26 +547,27 @@ class InferenceEngine:
             out.append(per_layer)
         return out
 
-    def _gate(self, idx: int, rows):
-        """bf16 gate vector(s) of stacked modulation `idx` (2 l: input norm, 2 l + 1: post-attention norm) for `rows`."""
-        De = self.De
+    def _gate(self, sch, idx: int, step: int):
+        """bf16 gate vectors of stacked modulation `idx` (2 l: input norm, 2 l + 1: post-attention norm) for the rows of `step`."""
+        B, De = self.B, self.De
         c0 = idx * 3 * De + 2 * De
-        return self._gates[rows, c0 : c0 + De]
+        return sch.gates[step * B : (step + 1) * B, c0 : c0 + De]
 
-    def _expert_layer_folded(self, l: int, xs, sq, parts: int, step: int, rows, folded):
+    def _expert_layer_folded(self, l: int, xs, sq, parts: int, step: int, sch, rope):
         """Expert layer `l` of one denoise step, 6 launches and no partial products: [q|k|v + RoPE], logits, softmax + P V, [o_proj +
         gated residual], [gate|up + GeGLU], [down_proj + gated residual], with the adaRMS norms folded into the weights: the projections
         read the raw residual stream, the producers (denoise glue, o_proj, down_proj) hand the rows' partial sums of squares along (`sq`:
-        [parts, M] f32); the gates are precomputed for all steps (`_gate`).  Returns (xs, sq, parts) for the next layer."""
+        [parts, M] f32); the gates are precomputed for all steps (`_gate`).  sch: the schedule's record; rope: the request's suffix
+        (cos, sin) tables.  Returns (xs, sq, parts) for the next layer."""
         B, P, De, H, HD, S_ld, F = self.B, self.P, self.De, self.H, self.HD, self.S_ld, self.F
         Hs = self.Ss  # suffix rows per sample (pi0: the state token + the action tokens)
         M, dev = B * Hs, self.dev
-        cos, sin = self._rope_cs
+        cos, sin = rope
         layer = self.pe.gemma_expert.model.layers[l]
         NQ = H * HD
-        ada = self.pi05  # pi0: plain residuals (no gate operand), one folded weight set for all steps
-        ld = self._mod_ld if ada else 0
-        (wq, cq), (wg, cg) = folded[step][l] if ada else folded[l]
+        ada = self.pi05  # pi0: plain residuals (no gate operand), one folded weight set for all steps (`_plain_fold`)
+        ld = sch.mod_ld if ada else 0
+        (wq, cq), (wg, cg) = sch.folded[step][l] if ada else self._plain_fold[l]
         ops.skinny_gemm(xs, wq, M=M, N=NQ + 2 * HD, K=De, lda=De, ldw=De, mode=1, pair_stride=HD // 2, split_k=-1,
                         segs=[(self.q_buf, NQ, 0, NQ, 1), (self.k_cache[l], HD, NQ, NQ + HD, 1),
                               (self.vt_all[l], S_ld, NQ + HD, NQ + 2 * HD, 2)],
@@ -550,7 +579,7 @@ class InferenceEngine:
         x1 = torch.empty((M, De), dtype=BF16, device=dev)
         sq1 = torch.empty((De // 16, M), dtype=F32, device=dev)
         ops.skinny_gemm(self.att_buf, self.w_o[l], M=M, N=De, K=NQ, lda=NQ, ldw=NQ, split_k=-1,
-                        a_map=(Hs, S_ld, P), segs=[(x1, De, 0, De, 0)], gate=self._gate(2 * l, rows) if ada else None, gate_rpb=Hs,
+                        a_map=(Hs, S_ld, P), segs=[(x1, De, 0, De, 0)], gate=self._gate(sch, 2 * l, step) if ada else None, gate_rpb=Hs,
                         gate_ld=ld, residual=xs, ldr=De, w_packed=True, rowsq_out=sq1)  # fmt: skip
         h = torch.empty((M, F), dtype=BF16, device=dev)
         ops.skinny_gemm(x1, wg, M=M, N=2 * F, K=De, lda=De, ldw=De, mode=2, pair_stride=F, split_k=-1,
@@ -559,15 +588,15 @@ class InferenceEngine:
         xs = torch.empty((M, De), dtype=BF16, device=dev)
         sq = torch.empty((De // 16, M), dtype=F32, device=dev)
         ops.skinny_gemm(h, self.w_d[l], M=M, N=De, K=F, lda=F, ldw=F, split_k=-1, segs=[(xs, De, 0, De, 0)],
-                        gate=self._gate(2 * l + 1, rows) if ada else None, gate_rpb=Hs, gate_ld=ld, residual=x1, ldr=De, w_packed=True,
+                        gate=self._gate(sch, 2 * l + 1, step) if ada else None, gate_rpb=Hs, gate_ld=ld, residual=x1, ldr=De, w_packed=True,
                         rowsq_out=sq)  # fmt: skip
         return xs, sq, De // 16
 
-    def _expert_stack_folded(self, xs, sq, step: int, rows, folded):
+    def _expert_stack_folded(self, xs, sq, step: int, sch, rope):
         """All expert layers of one denoise step (the step seam, kai0_denoise_glue, applies the final norm)."""
         parts = sq.shape[0]  # the step's first rows come from the glue kernel (one partial per row) / pi0's suffix embedding (De / 16)
         for l in range(self.L):
-            xs, sq, parts = self._expert_layer_folded(l, xs, sq, parts, step, rows, folded)
+            xs, sq, parts = self._expert_layer_folded(l, xs, sq, parts, step, sch, rope)
         return xs
 
     def _time_vectors(self, times: list[float]):
@@ -582,46 +611,15 @@ class InferenceEngine:
         tvec = ops.linear_f32(te, w[:, De:].contiguous(), model.action_time_mlp_in.bias)
         return tvec, w[:, :De].contiguous()
 
-    def _pi0_suffix_embed(self, x_t, step: int, tv, xs):
+    def _pi0_suffix_embed(self, x_t, step: int, sch, xs):
         """pi0 embed_suffix of one denoise step (pi0_pytorch.py:263-285) into the action rows 1 .. Hs of every sample's Hs + 1 suffix rows
         `xs` (row 0, the state token, is constant for a request: `_run` writes it once): action_in_proj, the action half of
         action_time_mlp_in + the step's hoisted time vector, SiLU, action_time_mlp_out — f32, one bf16 rounding at the store."""
         model, B, Hs, De = self.model, self.B, self.Hs, self.De
-        tvec, w_act = tv
         a = ops.linear_f32(x_t.view(B * Hs, self.A), model.action_in_proj.weight, model.action_in_proj.bias)
-        h = ops.silu_f32(ops.linear_f32(a, w_act, tvec[step].contiguous()))
+        h = ops.silu_f32(ops.linear_f32(a, sch.w_act, sch.tvec[step].contiguous()))
         y = ops.linear_f32(h, model.action_time_mlp_out.weight, model.action_time_mlp_out.bias)
         ops._copy_rows(ops.cast(y, BF16), xs, B, Hs, De, Hs * De, 0, De, self.Ss * De, 1, De)
-
-    def _denoise_step_plain(self, x_t, step: int, tv, xs):
-        """One Euler step of pi0 on the generic path: `_denoise_step` with plain RMSNorms and ungated residuals over Hs + 1 suffix rows
-        (the state token's layers are recomputed every step, as the reference does); action_out_proj reads the last Hs rows."""
-        model, pe = self.model, self.pe
-        B, P, Hs, Ss, De = self.B, self.P, self.Hs, self.Ss, self.De
-        H, HD, S_ld = self.H, self.HD, self.S_ld
-        ex = pe.gemma_expert.model
-        inv_freq = self._inv_freq
-        self._pi0_suffix_embed(x_t, step, tv, xs)
-        for l, layer in enumerate(ex.layers):
-            hs = ops.rmsnorm(xs, layer.input_layernorm.weight, layer.input_layernorm.eps)
-            at = layer.self_attn
-            self._proj_into(hs, at.q_proj, self.q_buf, Ss, P, H * HD)
-            self._proj_into(hs, at.k_proj, self.k_cache[l], Ss, P, HD)
-            self._proj_into(hs, at.v_proj, self.v_cache[l], Ss, P, HD)
-            ops.rope_(self.q_buf, self.pos_suffix, inv_freq, B, Ss, S_ld, P, H, HD)
-            ops.rope_(self.k_cache[l], self.pos_suffix, inv_freq, B, Ss, S_ld, P, 1, HD)
-            self._attend(l, P, Ss, P + Ss, self.qcode, self.kcode)
-            xs = self._oproj(at.o_proj, Ss, P, residual=xs)
-            hs = ops.rmsnorm(xs, layer.post_attention_layernorm.weight, layer.post_attention_layernorm.eps)
-            g = ops.linear_fwd(hs, layer.mlp.gate_proj.weight)
-            u = ops.linear_fwd(hs, layer.mlp.up_proj.weight)
-            _lib.call("kai0_geglu_fwd", g.data_ptr(), u.data_ptr(), g.data_ptr(), g.numel(), ops._stream())
-            xs = ops.linear_fwd(g, layer.mlp.down_proj.weight, residual=xs)
-        out = ops.rmsnorm(xs, ex.norm.weight, ex.norm.eps)
-        act = torch.empty((B * Hs, De), dtype=BF16, device=self.dev)
-        ops._copy_rows(out, act, B, Hs, De, Ss * De, Ss - Hs, De, Hs * De, 0, De)
-        v = ops.linear_f32(ops.cast(act, F32), model.action_out_proj.weight, model.action_out_proj.bias)
-        return v.view(B, Hs, self.A)
 
     def _adarms(self, xs, mod, eps: float):
         """kai0_adarms_fwd -> (y, gate bf16 [B, De], rstd f32 [rows]); `rstd` is what the guided step's reverse sweep reads."""
@@ -633,50 +631,68 @@ class InferenceEngine:
                   eps, ops._stream())  # fmt: skip
         return y, gate, rstd
 
-    def _denoise_step(self, x_t, step: int, mods, mf, tape: list | None = None):
-        """One Euler step on the generic path (shapes the production stack was not built for): per layer adaRMS, three projection
-        GEMMs into the static buffers, RoPE, attention, o_proj + gated residual, adaRMS, GeGLU MLP + gated residual.
-        `tape` (a guided step, `_denoiser_vjp`): the same launches, and what the reverse sweep needs is kept and appended per layer —
-        the inputs of both norms with their rstd, the gates, g / u, the attention's rotated query rows, output rows and probabilities;
-        the final norm's input and rstd come last."""
-        model, pe = self.model, self.pe
-        B, P, Hs, De = self.B, self.P, self.Hs, self.De
+    def _denoise_step(self, x_t, step: int, sch, xs=None, tape: list | None = None):
+        """One Euler step on the generic path (shapes the production stack was not built for) -> the velocity f32 [B, Hs, A].  Per layer:
+        norm, three projection GEMMs into the static buffers, RoPE, attention, o_proj + residual, norm, GeGLU MLP + residual; then the
+        final norm and action_out_proj.  The two model variants differ in data only:
+          pi0.5: Hs rows per sample, embedded by action_in_proj; adaRMS norms with the step's rows of `sch.mods` / `sch.mf`; gated residuals;
+          pi0:   Hs + 1 rows per sample in the request's `xs` (row 0, the state token, written once by `_run` and recomputed through the
+                 layers every step, as the reference does; rows 1 .. Hs by `_pi0_suffix_embed`); plain RMSNorms, no gates;
+                 action_out_proj reads the last Hs rows.
+        `tape` (a guided step, `_denoiser_vjp`; pi0.5 only): the same launches, and what the reverse sweep needs is kept and appended per
+        layer — the inputs of both norms with their rstd, the gates, g / u, the attention's rotated query rows, output rows and
+        probabilities; the final norm's input and rstd come last."""
+        model, ex = self.model, self.pe.gemma_expert.model
+        B, P, Hs, Ss, De = self.B, self.P, self.Hs, self.Ss, self.De
         H, HD, S_ld = self.H, self.HD, self.S_ld
         NQ = H * HD
-        ex = pe.gemma_expert.model
+        ada = self.pi05
         inv_freq = self._inv_freq
-        a = ops.linear_f32(x_t.view(B * Hs, self.A), model.action_in_proj.weight, model.action_in_proj.bias)
-        xs = ops.cast(a, BF16)
         rows = slice(step * B, (step + 1) * B)
+        if ada:
+            a = ops.linear_f32(x_t.view(B * Hs, self.A), model.action_in_proj.weight, model.action_in_proj.bias)
+            xs = ops.cast(a, BF16)
+        else:
+            self._pi0_suffix_embed(x_t, step, sch, xs)
+
+        def norm(x, ln, mod):  # -> (y, gate | None, rstd | None)
+            if ada:
+                return self._adarms(x, mod[rows], ln.eps)
+            return ops.rmsnorm(x, ln.weight, ln.eps), None, None
+
         for l, layer in enumerate(ex.layers):
-            m1, m2 = mods[l][0][rows], mods[l][1][rows]
+            m1, m2 = sch.mods[l] if ada else (None, None)
             x_in = xs
-            hs, gate1, rstd1 = self._adarms(xs, m1, layer.input_layernorm.eps)
+            hs, gate1, rstd1 = norm(xs, layer.input_layernorm, m1)
             at = layer.self_attn
-            self._proj_into(hs, at.q_proj, self.q_buf, Hs, P, NQ)
-            self._proj_into(hs, at.k_proj, self.k_cache[l], Hs, P, HD)
-            self._proj_into(hs, at.v_proj, self.v_cache[l], Hs, P, HD)
-            ops.rope_(self.q_buf, self.pos_suffix, inv_freq, B, Hs, S_ld, P, H, HD)
-            ops.rope_(self.k_cache[l], self.pos_suffix, inv_freq, B, Hs, S_ld, P, 1, HD)
-            probs = self._attend(l, P, Hs, P + Hs, self.qcode, self.kcode, want_probs=tape is not None)
+            self._proj_into(hs, at.q_proj, self.q_buf, Ss, P, NQ)
+            self._proj_into(hs, at.k_proj, self.k_cache[l], Ss, P, HD)
+            self._proj_into(hs, at.v_proj, self.v_cache[l], Ss, P, HD)
+            ops.rope_(self.q_buf, self.pos_suffix, inv_freq, B, Ss, S_ld, P, H, HD)
+            ops.rope_(self.k_cache[l], self.pos_suffix, inv_freq, B, Ss, S_ld, P, 1, HD)
+            probs = self._attend(l, P, Ss, P + Ss, self.qcode, self.kcode, want_probs=tape is not None)
             if tape is not None:  # q_buf / att_buf are shared by the layers: this layer's suffix rows, compact [B Hs, H HD]
                 q_rows = torch.empty((B * Hs, NQ), dtype=BF16, device=self.dev)
                 att_rows = torch.empty((B * Hs, NQ), dtype=BF16, device=self.dev)
                 ops._copy_rows(self.q_buf, q_rows, B, Hs, NQ, S_ld * NQ, P, NQ, Hs * NQ, 0, NQ)
                 ops._copy_rows(self.att_buf, att_rows, B, Hs, NQ, S_ld * NQ, P, NQ, Hs * NQ, 0, NQ)
-            xs = self._oproj(at.o_proj, Hs, P, residual=xs, gate=gate1)
+            xs = self._oproj(at.o_proj, Ss, P, residual=xs, gate=gate1)
             x_mid = xs
-            hs, gate2, rstd2 = self._adarms(xs, m2, layer.post_attention_layernorm.eps)
+            hs, gate2, rstd2 = norm(xs, layer.post_attention_layernorm, m2)
             g = ops.linear_fwd(hs, layer.mlp.gate_proj.weight)
             u = ops.linear_fwd(hs, layer.mlp.up_proj.weight)
-            h = g if tape is None else torch.empty_like(g)  # (the sweep's kai0_geglu_bwd reads g)
+            h = g if tape is None else torch.empty_like(g)  # in place, unless the sweep's kai0_geglu_bwd reads g
             _lib.call("kai0_geglu_fwd", g.data_ptr(), u.data_ptr(), h.data_ptr(), g.numel(), ops._stream())
-            xs = ops.linear_fwd(h, layer.mlp.down_proj.weight, residual=xs, gate=gate2, gate_rpb=Hs)
+            xs = ops.linear_fwd(h, layer.mlp.down_proj.weight, residual=xs, gate=gate2, gate_rpb=Hs if ada else 0)
             if tape is not None:
                 tape.append((x_in, rstd1, gate1, q_rows, att_rows, probs, x_mid, rstd2, gate2, g, u))
-        out, _, rstd_f = self._adarms(xs, mf[rows], ex.norm.eps)
+        out, _, rstd_f = norm(xs, ex.norm, sch.mf)
         if tape is not None:
             tape.append((xs, rstd_f))
+        if Ss != Hs:  # pi0: the action rows of every sample, compact
+            act = torch.empty((B * Hs, De), dtype=BF16, device=self.dev)
+            ops._copy_rows(out, act, B, Hs, De, Ss * De, Ss - Hs, De, Hs * De, 0, De)
+            out = act
         v = ops.linear_f32(ops.cast(out, F32), model.action_out_proj.weight, model.action_out_proj.bias)
         return v.view(B, Hs, self.A)
 
@@ -766,41 +782,36 @@ class InferenceEngine:
         ops.gemm_f32(ops.cast(dxs, F32), De, 1, model.action_in_proj.weight, A, 1, jte, M, A, De)
         return jte
 
-    def _run_pi0(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, state):
-        """pi0 chunk: prefix pass, the request's state token once, then the Euler loop over Hs + 1 suffix rows."""
-        times = euler_times(num_steps)
-        dt = float(np.float32(-1.0 / num_steps))
-        tv = self._mods_cache.get(tuple(times))
-        if tv is None:  # first (warm-up) run of this schedule: outside graph capture
-            tv = self._mods_cache[tuple(times)] = self._time_vectors(times)
-        model, B, De = self.model, self.B, self.De
-        x_t = noise.clone().contiguous()
-        self._prefix_pass(images, img_masks, lang_tokens, lang_masks)
-        if self.fast:
-            return self._denoise_pi0_folded(x_t, state, tv, len(times), dt)
-        xs0 = torch.empty((B * self.Ss, De), dtype=BF16, device=self.dev)
-        s = ops.linear_f32(state.to(F32).contiguous(), model.state_proj.weight, model.state_proj.bias)
-        ops._copy_rows(ops.cast(s, BF16), xs0, B, 1, De, De, 0, De, self.Ss * De, 0, De)  # row 0 of every sample: constant over the steps
-        for step in range(len(times)):
-            v_t = self._denoise_step_plain(x_t, step, tv, xs0)
-            ops.euler_step_(x_t, v_t, dt)
-        self._content_stamp()
-        return x_t
+    def _seams_pi05(self, x2, sch, rope, n: int, dt: float):
+        """pi0.5's Euler loop on the production stack.  Step seams in one launch each (kai0_denoise_glue): [final adaRMS ->
+        action_out_proj -> Euler update] of step s and [action_in_proj -> bf16 + the rows' sums of squares] of step s + 1."""
+        model, B, Hs, De = self.model, self.B, self.Hs, self.De
+        M = B * Hs
+        win, bin_ = model.action_in_proj.weight, model.action_in_proj.bias
+        wout, bout = model.action_out_proj.weight, model.action_out_proj.bias
+        eps = self.pe.gemma_expert.model.norm.eps
+        xs = torch.empty((M, De), dtype=BF16, device=self.dev)
+        sq = torch.empty((1, M), dtype=F32, device=self.dev)
+        ops.denoise_glue(x2, w_in=win, b_in=bin_, xs_next=xs, rowsq_next=sq)
+        last = None
+        for step in range(n + 1):
+            if step > 0:  # the seam behind step - 1 (and in front of `step`, if there is one)
+                more = step < n
+                xs = torch.empty((M, De), dtype=BF16, device=self.dev) if more else None
+                sq = torch.empty((1, M), dtype=F32, device=self.dev) if more else None
+                r_prev = slice((step - 1) * B, step * B)
+                ops.denoise_glue(x2, xs=last, mod=sch.mf[r_prev], mod_ld=sch.mod_ld, rows_per_batch=Hs, eps=eps, w_out=wout, b_out=bout,
+                                 dt=dt, w_in=win if more else None, b_in=bin_ if more else None, xs_next=xs, rowsq_next=sq)
+            if step < n:
+                last = self._expert_stack_folded(xs, sq, step, sch, rope)
 
-    def _denoise_pi0_folded(self, x_t, state, tv, n: int, dt: float):
+    def _seams_pi0(self, x2, sch, rope, n: int, dt: float, state):
         """pi0's Euler loop on the production stack.  One suffix buffer xs [B (Hs + 1), De] + its sums of squares [De / 16, B (Hs + 1)]
         for all steps: row 0 of every sample = bf16(state_proj(state)), written once per request (kai0_denoise_glue_rows' opening half
         with w_in = state_proj); rows 1 .. Hs by `ops.pi0_suffix_embed` at the start of every step.  The seam behind a step is
         kai0_denoise_glue_rows' closing half on the action rows: the final plain RMSNorm as the constant modulation row `_mod_final`,
         action_out_proj, the Euler update of x_t.  The state token's layers are recomputed every step, as the reference does."""
-        model, B, Hs, Ss, De, P, HD, S_ld = self.model, self.B, self.Hs, self.Ss, self.De, self.P, self.HD, self.S_ld
-        M = B * Hs
-        x2 = x_t.view(M, self.A)
-        tvec, _ = tv
-        self._rope_cs = ops.rope_table(self.pos_suffix, self._inv_freq)
-        # prefix value rows of every layer -> transposed cache, one launch
-        ops.transpose_strided(self.v_all, self.vt_all, R=P, C=HD, src_ld=HD, dst_ld=S_ld, batch=self.L * B, src_bs=S_ld * HD,
-                              dst_bs=HD * S_ld)
+        model, B, Hs, Ss, De = self.model, self.B, self.Hs, self.Ss, self.De
         xs = torch.empty((B * Ss, De), dtype=BF16, device=self.dev)
         sq = torch.zeros((De // 16, B * Ss), dtype=F32, device=self.dev)  # the state rows keep ONE partial (row 0 of sq), the rest 0
         ops.denoise_glue(state.to(F32).contiguous(), w_in=model.state_proj.weight, b_in=model.state_proj.bias, xs_next=xs, rowsq_next=sq,
@@ -809,91 +820,46 @@ class InferenceEngine:
         w_a, b_a = model.action_in_proj.weight, model.action_in_proj.bias
         w_in, w_out, b_out = model.action_time_mlp_in.weight, model.action_time_mlp_out.weight, model.action_time_mlp_out.bias
         for step in range(n):
-            ops.pi0_suffix_embed(x2, w_a, b_a, w_in, tvec[step], w_out, b_out, xs, sq, Hs, Ss)
-            last = self._expert_stack_folded(xs, sq, step, None, self._plain_fold)
-            ops.denoise_glue(x2, xs=last, mod=self._mod_final, mod_ld=3 * De, rows_per_batch=M, eps=ex_norm.eps,
+            ops.pi0_suffix_embed(x2, w_a, b_a, w_in, sch.tvec[step], w_out, b_out, xs, sq, Hs, Ss)
+            last = self._expert_stack_folded(xs, sq, step, sch, rope)
+            ops.denoise_glue(x2, xs=last, mod=self._mod_final, mod_ld=3 * De, rows_per_batch=B * Hs, eps=ex_norm.eps,
                              w_out=model.action_out_proj.weight, b_out=model.action_out_proj.bias, dt=dt, row_map=(Hs, Ss, Ss - Hs))
-        self._content_stamp()
-        return x_t
-
-    def _tables(self, times: list[float]):
-        """The modulation table (and, production stack: the folded per-step weights) of a schedule: a function of the weights and the
-        schedule only — computed on the first (warm-up) run, outside graph capture, and kept for the engine's lifetime."""
-        if tuple(times) not in self._times_dev:  # H2D copy: must happen outside graph capture (warm-up run)
-            self._times_dev[tuple(times)] = torch.tensor(times, dtype=F32).repeat_interleave(self.B).to(self.dev)
-        hit = self._mods_cache.get(tuple(times))
-        if hit is None:
-            mods, mf = self._modulations(times)
-            hit = self._mods_cache[tuple(times)] = (mods, mf, self._mod_ld if self.fast else None, self._gates if self.fast else None)
-            if self.fast:
-                self._fold_cache[tuple(times)] = self._fold_modulations(mods, len(times))
-        return hit
 
     def _run(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, state=None):
+        """One action chunk: the schedule's record, the prefix pass, the Euler loop (production stack or generic step), the content
+        stamp.  Every launch goes to the current stream: this is what `sample_actions` captures."""
         if not self.pi05:
             if state is None and self._static_in is not None:
                 state = self._static_in["state"]  # the captured request's (a stage timed on the static inputs)
             if state is None:
                 raise ValueError("a pi0 engine needs the request's `state`")
-            return self._run_pi0(images, img_masks, lang_tokens, lang_masks, noise, num_steps, state)
         times = euler_times(num_steps)
         dt = float(np.float32(-1.0 / num_steps))
-        hit = self._tables(times)
-        mods, mf = hit[0], hit[1]
+        sch = self._schedule(times)
         x_t = noise.clone().contiguous()
-        if not self.fast:
-            self._prefix_pass(images, img_masks, lang_tokens, lang_masks)
-        else:
-            self._mod_ld, self._gates = hit[2], hit[3]
-            # step seams in one launch each (kai0_denoise_glue): [final adaRMS -> action_out_proj -> Euler update] of step s and
-            # [action_in_proj -> bf16 + the rows' sums of squares] of step s + 1
-            model, B, Hs, De, P, HD, S_ld = self.model, self.B, self.Hs, self.De, self.P, self.HD, self.S_ld
-            M, n = B * Hs, len(times)
-            x2 = x_t.view(M, self.A)
-            win, bin_ = model.action_in_proj.weight, model.action_in_proj.bias
-            wout, bout = model.action_out_proj.weight, model.action_out_proj.bias
-            eps = self.pe.gemma_expert.model.norm.eps
-            folded = self._fold_cache[tuple(times)]
-            # (Round 5, measured and removed: the first Euler step's chain on a second stream behind the prefix pass — layer l of step 0
-            # needs only layer l's K / V rows — is bit-identical and 0.6 ms SLOWER, 16.6 against 15.95 ms p50: a forked hipGraph replays
-            # slower than a linear one, as round 2 found for a much smaller branch.)
-            self._prefix_pass(images, img_masks, lang_tokens, lang_masks)
-            self._rope_cs = ops.rope_table(self.pos_suffix, self._inv_freq)
+        self._prefix_pass(images, img_masks, lang_tokens, lang_masks)
+        model, B, P, HD, S_ld, De = self.model, self.B, self.P, self.HD, self.S_ld, self.De
+        if self.fast:
+            rope = ops.rope_table(self.pos_suffix, self._inv_freq)
             # prefix value rows of every layer -> transposed cache, one launch
             ops.transpose_strided(self.v_all, self.vt_all, R=P, C=HD, src_ld=HD, dst_ld=S_ld, batch=self.L * B, src_bs=S_ld * HD,
                                   dst_bs=HD * S_ld)
-            xs = torch.empty((M, De), dtype=BF16, device=self.dev)
-            sq = torch.empty((1, M), dtype=F32, device=self.dev)
-            ops.denoise_glue(x2, w_in=win, b_in=bin_, xs_next=xs, rowsq_next=sq)
-            last = None
-            for step in range(n + 1):
-                if step > 0:  # the seam behind step - 1 (and in front of `step`, if there is one)
-                    more = step < n
-                    xs = torch.empty((M, De), dtype=BF16, device=self.dev) if more else None
-                    sq = torch.empty((1, M), dtype=F32, device=self.dev) if more else None
-                    r_prev = slice((step - 1) * B, step * B)
-                    ops.denoise_glue(x2, xs=last, mod=mf[r_prev], mod_ld=self._mod_ld, rows_per_batch=Hs, eps=eps, w_out=wout, b_out=bout,
-                                     dt=dt, w_in=win if more else None, b_in=bin_ if more else None, xs_next=xs, rowsq_next=sq)
-                if step < n:
-                    last = self._expert_stack_folded(xs, sq, step, slice(step * B, (step + 1) * B), folded)
-            self._content_stamp()
-            return x_t
-        for step in range(len(times)):
-            v_t = self._denoise_step(x_t, step, mods, mf)
-            ops.euler_step_(x_t, v_t, dt)
+            x2 = x_t.view(B * self.Hs, self.A)
+            if self.pi05:
+                self._seams_pi05(x2, sch, rope, len(times), dt)
+            else:
+                self._seams_pi0(x2, sch, rope, len(times), dt, state)
+        else:
+            xs = None
+            if not self.pi05:  # the state token, row 0 of every sample's suffix rows: constant over the steps
+                xs = torch.empty((B * self.Ss, De), dtype=BF16, device=self.dev)
+                s = ops.linear_f32(state.to(F32).contiguous(), model.state_proj.weight, model.state_proj.bias)
+                ops._copy_rows(ops.cast(s, BF16), xs, B, 1, De, De, 0, De, self.Ss * De, 0, De)
+            for step in range(len(times)):
+                v_t = self._denoise_step(x_t, step, sch, xs)
+                ops.euler_step_(x_t, v_t, dt)
         self._content_stamp()
         return x_t
-
-    def _guided_tables(self, times: list[float]):
-        """`_tables` for the guided loop, which runs the generic per-layer step on every engine: contiguous [steps B, 3 De] modulation
-        rows per norm (the production stack keeps them as column slices of one table)."""
-        mods, mf = self._tables(times)[:2]
-        if not self.fast:
-            return mods, mf
-        hit = self._guided_mods.get(tuple(times))
-        if hit is None:
-            hit = self._guided_mods[tuple(times)] = ([(a.contiguous(), b.contiguous()) for a, b in mods], mf.contiguous())
-        return hit
 
     def _run_guided(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, max_guidance_weight: float, provided: int):
         """A real-time-chunking chunk (pi0_rtc.py:293-349; kai0_amd/rtc.py): the prefix pass and the modulation tables of `_run`, then per
@@ -904,16 +870,16 @@ class InferenceEngine:
 
         times = euler_times(num_steps)
         dt = float(np.float32(-1.0 / num_steps))
-        mods, mf = self._guided_tables(times)
+        sch = self._guided_schedule(times)
         gws = rtc.guidance_weights(times, max_guidance_weight)
         x_t = noise.clone().contiguous()
         self._prefix_pass(images, img_masks, lang_tokens, lang_masks)
         M = self.B * self.Hs
         for step, (t, g) in enumerate(zip(times, gws, strict=True)):
             tape = []
-            v_t = self._denoise_step(x_t, step, mods, mf, tape)
+            v_t = self._denoise_step(x_t, step, sch, tape=tape)
             err = ops.rtc_error(x_t, v_t, self._g_prev, self._g_w, provided, t)
-            jte = self._denoiser_vjp(err.view(M, self.A), tape, step, mods, mf)
+            jte = self._denoiser_vjp(err.view(M, self.A), tape, step, sch.mods, sch.mf)
             ops.rtc_update_(x_t, v_t, err, jte, t, g, dt)
         self._content_stamp()
         return x_t
@@ -922,13 +888,12 @@ class InferenceEngine:
     def denoiser_vjp(self, images, img_masks, lang_tokens, lang_masks, x_t, cotangent, num_steps: int, step: int):
         """The guided loop's primitive on its own (tests, tools): the prefix pass, then at `x_t` and the time of Euler step `step` the
         velocity v and (dv / dx_t)^T cotangent, both f32 [B, Hs, A].  Eager launches."""
-        times = euler_times(num_steps)
-        mods, mf = self._guided_tables(times)
+        sch = self._guided_schedule(euler_times(num_steps))
         self._prefix_pass(images, img_masks, lang_tokens, lang_masks)
         tape = []
         x_t = x_t.to(F32).contiguous()
-        v_t = self._denoise_step(x_t, step, mods, mf, tape)
-        jte = self._denoiser_vjp(cotangent.to(F32).contiguous().view(self.B * self.Hs, self.A), tape, step, mods, mf)
+        v_t = self._denoise_step(x_t, step, sch, tape=tape)
+        jte = self._denoiser_vjp(cotangent.to(F32).contiguous().view(self.B * self.Hs, self.A), tape, step, sch.mods, sch.mf)
         return v_t, jte.view(self.B, self.Hs, self.A)
 
     @torch.no_grad()
@@ -950,42 +915,17 @@ class InferenceEngine:
         key = (num_steps, float(guidance.max_guidance_weight), int(guidance.provided))
         args = (images, img_masks, lang_tokens, lang_masks, noise)
         if self.use_graph and self._g_graph_key != key:
-            self._capture_guided(*args, key)
-        if not self.use_graph or self._g_graph is None:
+            cap = _Capture(*args)
+            self._g_cap, self._g_graph_key = None, key  # (a refused capture is not tried again for this key)
+            try:
+                cap.capture(lambda im, mk, tok, lm, nz, st: self._run_guided(im, mk, tok, lm, nz, *key))
+                self._g_cap = cap
+            except Exception as e:  # noqa: BLE001 - capture problems must not take serving down
+                logger.warning("hipGraph capture of the guided chunk failed (%s); running eager HIP launches", e)
+        if not self.use_graph or self._g_cap is None:
             return self._run_guided(*args, *key)
-        si = self._g_static_in
-        for dst, src in zip(si["images"], images, strict=True):
-            dst.copy_(src)
-        for dst, src in zip(si["img_masks"], img_masks, strict=True):
-            dst.copy_(src)
-        si["lang_tokens"].copy_(lang_tokens)
-        si["lang_masks"].copy_(lang_masks)
-        si["noise"].copy_(noise)
-        self._g_graph.replay()
-        return self._g_static_out.clone()
-
-    def _capture_guided(self, images, img_masks, lang_tokens, lang_masks, noise, key):
-        si = {
-            "images": [im.clone().contiguous() for im in images],
-            "img_masks": [m.clone() for m in img_masks],
-            "lang_tokens": lang_tokens.clone().contiguous(),
-            "lang_masks": lang_masks.clone().contiguous(),
-            "noise": noise.clone().contiguous(),
-        }
-        self._g_graph = self._g_graph_key = self._g_static_in = self._g_static_out = None
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture requires
-                self._run_guided(si["images"], si["img_masks"], si["lang_tokens"], si["lang_masks"], si["noise"], *key)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                out = self._run_guided(si["images"], si["img_masks"], si["lang_tokens"], si["lang_masks"], si["noise"], *key)
-            self._g_graph, self._g_graph_key, self._g_static_in, self._g_static_out = graph, key, si, out
-        except Exception as e:  # noqa: BLE001 - capture problems must not take serving down
-            logger.warning("hipGraph capture of the guided chunk failed (%s); running eager HIP launches", e)
-            self._g_graph_key = key  # (not tried again for this key)
+        self._g_cap.replay(*args)
+        return self._g_cap.out.clone()
 
     # -------------------------------------------------------------------------------------------------- API
     @torch.no_grad()
@@ -993,17 +933,65 @@ class InferenceEngine:
         """`state`: the request's robot state f32 [B, action_dim] — a model input of pi0 (ignored by pi0.5, whose state is in the prompt)."""
         if self.pi05:
             state = None
-        if not self.use_graph:
-            return self._run(images, img_masks, lang_tokens, lang_masks, noise, num_steps, state)
-        if self._graph is None or self._graph_steps != num_steps:
-            self._capture(images, img_masks, lang_tokens, lang_masks, noise, num_steps, state)
-        if self._graph is None:  # capture refused: stay on eager HIP launches
-            return self._run(images, img_masks, lang_tokens, lang_masks, noise, num_steps, state)
-        self._replay(images, img_masks, lang_tokens, lang_masks, noise, state)
-        return self._static_out.clone()
+        args = (images, img_masks, lang_tokens, lang_masks, noise)
+        if self.use_graph and (self._cap is None or self._graph_steps != num_steps):
+            cap = _Capture(*args, state)
+            try:
+                cap.capture(lambda im, mk, tok, lm, nz, st: self._run(im, mk, tok, lm, nz, num_steps, st))
+                self._cap, self._graph_steps = cap, num_steps
+            except Exception as e:  # noqa: BLE001 - capture problems must not take serving down
+                logger.warning("hipGraph capture failed (%s); running eager HIP launches", e)
+                self._cap = None
+                self.use_graph = False
+        if not self.use_graph:  # switched off, or capture refused: eager HIP launches
+            return self._run(*args, num_steps, state)
+        self._cap.replay(*args, state)
+        return self._cap.out.clone()
 
-    def _replay(self, images, img_masks, lang_tokens, lang_masks, noise, state=None):
-        si = self._static_in
+    @torch.no_grad()
+    def replay_then_verify(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, state=None):
+        """The serving fast path: queue the captured chunk first, THEN check that the weights are still the ones the engine was built
+        from (the check is host work; the chunk only writes engine-owned buffers).  Returns the chunk, or None when there is no graph for
+        this schedule yet or the weights changed (the queued result is then dropped: the caller rebuilds the engine and runs again)."""
+        if not self.use_graph or self._cap is None or self._graph_steps != num_steps:
+            return None
+        self._cap.replay(images, img_masks, lang_tokens, lang_masks, noise, None if self.pi05 else state)
+        if not self.weights_unchanged():
+            return None
+        return self._cap.out.clone()
+
+
+class _Capture:
+    """Static copies of one request's inputs, a hipGraph recorded over them, and the tensor that graph writes its chunk to."""
+
+    def __init__(self, images, img_masks, lang_tokens, lang_masks, noise, state=None):
+        self.inputs = {
+            "images": [im.clone().contiguous() for im in images],
+            "img_masks": [m.clone() for m in img_masks],
+            "lang_tokens": lang_tokens.clone().contiguous(),
+            "lang_masks": lang_masks.clone().contiguous(),
+            "noise": noise.clone().contiguous(),
+            "state": state.to(F32).clone().contiguous() if state is not None else None,  # pi0: a static buffer inside the graph
+        }
+        self.graph = self.out = None
+
+    def capture(self, run):
+        """Record run(images, img_masks, lang_tokens, lang_masks, noise, state) -> chunk over the static copies.  Raises what the
+        warm-up or the capture raises: what a refused capture means is the caller's business."""
+        args = tuple(self.inputs.values())
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture requires
+            run(*args)
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = run(*args)
+        self.graph, self.out = graph, out
+
+    def replay(self, images, img_masks, lang_tokens, lang_masks, noise, state=None):
+        """Copy a request into the static buffers and queue the graph: the chunk lands in `out`."""
+        si = self.inputs
         if si["state"] is not None:
             si["state"].copy_(state)
         for dst, src in zip(si["images"], images, strict=True):
@@ -1013,40 +1001,4 @@ class InferenceEngine:
         si["lang_tokens"].copy_(lang_tokens)
         si["lang_masks"].copy_(lang_masks)
         si["noise"].copy_(noise)
-        self._graph.replay()
-
-    @torch.no_grad()
-    def replay_then_verify(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, state=None):
-        """The serving fast path: queue the captured chunk first, THEN check that the weights are still the ones the engine was built
-        from (the check is host work; the chunk only writes engine-owned buffers).  Returns the chunk, or None when there is no graph for
-        this schedule yet or the weights changed (the queued result is then dropped: the caller rebuilds the engine and runs again)."""
-        if not self.use_graph or self._graph is None or self._graph_steps != num_steps:
-            return None
-        self._replay(images, img_masks, lang_tokens, lang_masks, noise, None if self.pi05 else state)
-        if not self.weights_unchanged():
-            return None
-        return self._static_out.clone()
-
-    def _capture(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, state=None):
-        si = {
-            "images": [im.clone().contiguous() for im in images],
-            "img_masks": [m.clone() for m in img_masks],
-            "lang_tokens": lang_tokens.clone().contiguous(),
-            "lang_masks": lang_masks.clone().contiguous(),
-            "noise": noise.clone().contiguous(),
-            "state": state.to(F32).clone().contiguous() if state is not None else None,  # pi0: a static buffer inside the graph
-        }
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture requires
-                self._run(si["images"], si["img_masks"], si["lang_tokens"], si["lang_masks"], si["noise"], num_steps, si["state"])
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                out = self._run(si["images"], si["img_masks"], si["lang_tokens"], si["lang_masks"], si["noise"], num_steps, si["state"])
-            self._graph, self._graph_steps, self._static_in, self._static_out = graph, num_steps, si, out
-        except Exception as e:  # noqa: BLE001 - capture problems must not take serving down
-            logger.warning("hipGraph capture failed (%s); running eager HIP launches", e)
-            self._graph = None
-            self.use_graph = False
+        self.graph.replay()

@@ -271,7 +271,7 @@ def test_fullwidth_production_denoise_stack_agrees_with_the_generic_path(fw):
         m.invalidate_inference_engine()
         ref = m.sample_actions(d, gobs, noise=noise, num_steps=10)
         eng = m._engine
-        assert eng.fast and eng.fuse_norm and eng._fold_cache
+        assert eng.fast and eng.fuse_norm and eng._schedules and all(s.folded for s in eng._schedules.values())
         InferenceEngine.force_generic = True
         try:
             m.invalidate_inference_engine()

@@ -29,7 +29,7 @@ if pi0:
     model.sample_actions(dev, obs, noise=torch.randn(1, cfg.action_horizon, cfg.action_dim, device=dev), num_steps=10)
     eng = model._engine
     res["engine_fast"] = bool(eng.fast)
-    tvec, _ = eng._time_vectors(euler_times(10))
+    tvec = eng._schedule(euler_times(10)).tvec
     Hs, Ss, De = eng.Hs, eng.Ss, eng.De
     x2 = torch.randn(Hs, cfg.action_dim, device=dev)
     xs = torch.empty((Ss, De), dtype=torch.bfloat16, device=dev)
