@@ -753,6 +753,39 @@ int kai0_frames_to_chw(const uint8_t* frames, float* out, int N, int H0, int W0,
 int kai0_prefix_gather(const void* bank, const int32_t* slots, const void* lang, void* out, int B, int nslot, int n_img, int T, int D,
                        int64_t lang_bs, kai0_stream_t stream);
 
+/* Normalisation statistics over action chunks (scripts/compute_norm_stats.py:102-109: the loop that feeds every transformed sample's
+ * "state" and "actions" to normalize.RunningStats; kai0_amd.norm_stats.compute_norm_stats).  Both entry points read the same virtual
+ * rows and materialise none of them.  For every frame m < M (i = frame_idx ? frame_idx[m] : m; any order, duplicates allowed), chunk
+ * row h < horizon and column c < width:
+ *     a = c < da ? action[min(i + h, ep_end[i] - 1) * ld_action + c] : 0         (lerobot's window clamp; ep_end[i] = one past the last
+ *     if (clip_action && fabsf(a) > f32(pi)) a = 0                                row of frame i's episode)
+ *     if (delta_mask bit c) { s = (mask_state || c >= ds) ? 0 : state[i * ld_state + c];
+ *                             if (clip_state && fabsf(s) > f32(pi)) s = 0;   a = a - s; }                      (one f32 subtract)
+ * i.e. agilex_policy.py:28 `_clip_glitches` and transforms.py:213-233 `DeltaActions` on the zero-padded tables.  The "state" statistics
+ * are the horizon = 1, delta_mask = 0 case with the state table passed as `action` (and clip_state as clip_action).
+ * state f32 [N][ld_state], action f32 [N][ld_action], ep_end int32 [N], frame_idx int32 [M] or NULL (then M <= N); width 1..32,
+ * ds, da <= width; delta_mask / col_mask select no column >= width.  Rows the tables do not hold are never read: a frame_idx outside
+ * [0, N) is skipped and ep_end is clamped to [i + 1, N] on the device, but the CALLER guarantees valid values (a skipped frame is
+ * missing from the counts).  Caller-owned buffers, explicit stream, no allocation, no host synchronisation.
+ * kai0_chunk_stats_moments (pass 1): out f64 [4][width] = per column min, max (exact f32 values; a NaN anywhere in a column makes both
+ *   NaN), sum and sum of squares accumulated in f64 (x * x is exact).  Per-block partials go to `workspace`
+ *   (kai0_chunk_stats_workspace_bytes(M, width) bytes, 8-byte aligned) and a second launch adds them in block order: no float atomics,
+ *   the same call gives the same bits; any summation order is within (n - 1) 2^-53 sum|x| of the exact sum.
+ * kai0_chunk_stats_hist (pass 2): hist u64 [width][bins] += np.histogram's counts of the columns in col_mask over edges f64
+ *   [width][bins + 1] (ascending, edges[c][0] <= every value <= edges[c][bins]; rows of unselected columns are not read): the bin is
+ *   floor((x - e[0]) * bins / (e[bins] - e[0])) corrected against the table until e[k] <= x < e[k + 1], the last bin closed on the
+ *   right, with x the f32 value widened to f64 — numpy's searchsorted answer as an integer.  u32 counters in LDS (bins <= 40960; a block
+ *   owns up to 8 columns x a slab of frames), flushed with integer atomic adds: order-independent, the caller zeroes hist. */
+int64_t kai0_chunk_stats_workspace_bytes(int M, int width);
+int kai0_chunk_stats_moments(const float* state, int64_t ld_state, int ds, const float* action, int64_t ld_action, int da,
+                             const int32_t* ep_end, int N, const int32_t* frame_idx, int M, int horizon, int width, int clip_state,
+                             int clip_action, int mask_state, uint32_t delta_mask, double* out, void* workspace, int64_t workspace_bytes,
+                             kai0_stream_t stream);
+int kai0_chunk_stats_hist(const float* state, int64_t ld_state, int ds, const float* action, int64_t ld_action, int da,
+                          const int32_t* ep_end, int N, const int32_t* frame_idx, int M, int horizon, int width, int clip_state,
+                          int clip_action, int mask_state, uint32_t delta_mask, const double* edges, int bins, uint32_t col_mask,
+                          unsigned long long* hist, kai0_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

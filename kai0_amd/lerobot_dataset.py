@@ -386,6 +386,39 @@ def create_advantage_torch_dataset(data_config, action_horizon: int, model_confi
     return dataset
 
 
+def read_state_action_columns(repo_id, state_col: str, action_col: str, episodes: list[int] | None = None):
+    """The two vector columns of a dataset and its episode boundaries, for `kai0_amd.norm_stats`: f32 [N, ds], f32 [N, da] and
+    int32 ep_end [N] (ep_end[i] = one past the last row of frame i's episode), episodes in `LeRobotDataset`'s order.  Only these two
+    columns are read from each parquet file: image columns and videos are never touched."""
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+
+    meta = LeRobotDatasetMetadata(repo_id)
+    eps = list(episodes) if episodes is not None else sorted(meta.episodes)
+    parts: dict[str, list[np.ndarray]] = {state_col: [], action_col: []}
+    lengths = []
+    for ep in eps:
+        t = pq.read_table(meta.data_file(ep), columns=[state_col, action_col])
+        lengths.append(t.num_rows)
+        for name in (state_col, action_col):
+            col = t.column(name).combine_chunks()
+            if pa.types.is_list(col.type) or pa.types.is_large_list(col.type) or pa.types.is_fixed_size_list(col.type):
+                flat = col.flatten().to_numpy(zero_copy_only=False)
+                if t.num_rows and (flat.size % t.num_rows or col.null_count):
+                    raise ValueError(f"{meta.data_file(ep)}: column {name!r} is not a table of equally long vectors")
+                arr = flat.reshape(t.num_rows, -1) if t.num_rows else flat.reshape(0, 0)
+            else:
+                arr = col.to_numpy(zero_copy_only=False).reshape(t.num_rows, 1)
+            parts[name].append(arr.astype(np.float32, copy=False))
+    widths = {name: {a.shape[1] for a in arrs if len(a)} for name, arrs in parts.items()}
+    if any(len(w) > 1 for w in widths.values()):
+        raise ValueError(f"{meta.root}: the width of {state_col!r} / {action_col!r} changes between episodes: {widths}")
+    state, action = (np.concatenate([a for a in parts[name] if len(a)]) if any(len(a) for a in parts[name]) else np.zeros((0, 0), np.float32)
+                     for name in (state_col, action_col))  # fmt: skip
+    ep_end = np.repeat(np.cumsum(lengths), lengths).astype(np.int32)
+    return state, action, ep_end
+
+
 def transform_dataset(dataset, data_config, *, skip_norm_stats: bool = False):
     """data_loader.py:230-251: repack -> robot transforms -> Normalize -> model transforms."""
     from .data_loader import TransformedDataset
@@ -393,7 +426,7 @@ def transform_dataset(dataset, data_config, *, skip_norm_stats: bool = False):
     norm_stats = {}
     if data_config.repo_id != "fake" and not skip_norm_stats:
         if data_config.norm_stats is None:
-            raise ValueError("Normalization stats not found. Make sure to run `scripts/compute_norm_stats.py --config-name=<your-config>`.")
+            raise ValueError("Normalization stats not found. Make sure to run `python -m kai0_amd.compute_norm_stats <your-config>`.")
         norm_stats = data_config.norm_stats
     return TransformedDataset(dataset, [*data_config.repack_transforms.inputs, *data_config.data_transforms.inputs,
                                         _transforms.Normalize(norm_stats, use_quantiles=data_config.use_quantile_norm),
