@@ -155,6 +155,23 @@ typedef struct kai0_gemm_desc {
     const void* rope_cos;
     const void* rope_sin;
     int32_t rope_half, rope_n_end;
+    /* Transposed second store, null = off.  (Four fields in front of the hooks: kai0_gemm_desc_size() grew by 32 bytes and the hooks
+     * moved, so a binding must rebuild its mirror — kai0_gemm_desc_size() tells it; kai0_abi_version() stays 2.)  The epilogue ALSO
+     * writes the bf16 values it stores row-major, bit for bit, as [N][M] matrices, 16 bytes (8 consecutive m) per store:
+     *   act 0:  ct[n][m] = C[m][n], the plain product                    (ct2 must be null; no bias / gate / residual / accumulate / scale)
+     *   act 6:  ct[n][m] = C[m][n] = h                                   (ct2 must be null)
+     *   act 3:  ct[n][m] = C[m][n] = dg and ct2[n][m] = pre_out[m][n] = du   (both must be set)
+     * with leading dimensions ldct / ldct2 (elements, multiples of 8, >= M).  C, pre_out and pre_out2 are written exactly as without
+     * it.  Why: the Gemma MLP's weight gradients contract over the rows of h, dg and du; with those operands K-contiguous they run
+     * the 64-deep NT loop instead of the 32-deep TN ring (ops.GegluMlpFn), and the producer's epilogue, which already passes the tile
+     * through LDS while the HBM write path idles, is the one place where the transposed copy costs no pass over memory.
+     * Needs the 256 x 256 tile (K-contiguous operands; kai0_gemm_plan_t.tile), M % 8 == 0, one batch entry, no split-K, no f32
+     * output, no column segments, no output row map, and for act 0 / act 3 the plain form (no bias / gate / residual / accumulate /
+     * scale).  Other acts are rejected. */
+    void* ct;
+    int64_t ldct;
+    void* ct2;
+    int64_t ldct2;
     /* A/B and test hooks, all 0 in production.  They are per CALL: the library keeps no process-wide mutable switches (SURVEY.md §8b
      * "no globals beyond a per-device handle" — what remains static is per-device set-up: kernel LDS attributes, the CU count and
      * the persistent kernel's self-cleaning counter slots).
@@ -191,7 +208,7 @@ typedef struct kai0_gemm_plan_t {
     int32_t tiles_m, tiles_n; /* tiles of that size over M and over the logical width (2 N for act 6) */
     int32_t k_chunk;          /* contraction length per split-K slice (K when split_k <= 1); slices past K are empty */
     int32_t simple_epilogue;  /* 1: the 256 x 256 store-with-little-else epilogue applies (see general_epilogue) */
-    int32_t _pad;
+    int32_t transposed_store; /* 1: the launch also stores ct (/ ct2), the transposed second copy (was padding) */
 } kai0_gemm_plan_t;
 int kai0_gemm_plan(const kai0_gemm_desc* d, kai0_gemm_plan_t* out);
 int kai0_gemm_plan_size(void); /* sizeof the plan struct as compiled, as kai0_gemm_desc_size */

@@ -47,6 +47,7 @@ class GemmDesc(C.Structure):
         ("B2", c_p), ("pre_out2", c_p),
         ("norm_out", c_p), ("norm_w", c_p), ("norm_b", c_p), ("norm_eps", C.c_float), ("norm_kind", C.c_int32),
         ("rope_cos", c_p), ("rope_sin", c_p), ("rope_half", C.c_int32), ("rope_n_end", C.c_int32),
+        ("ct", c_p), ("ldct", c_i64), ("ct2", c_p), ("ldct2", c_i64),
         ("persist", C.c_int32), ("general_epilogue", C.c_int32), ("small_w8", C.c_int32), ("_pad3", C.c_int32),
     ]  # fmt: skip
 
@@ -55,7 +56,7 @@ class GemmPlan(C.Structure):
     """Mirror of `kai0_gemm_plan_t` (include/kai0hip.h): the kernel kai0_gemm_bf16 selects for a descriptor."""
 
     _fields_ = [("tile", C.c_int32), ("waves", C.c_int32), ("loop", C.c_int32), ("tiles_m", C.c_int32), ("tiles_n", C.c_int32),
-                ("k_chunk", C.c_int32), ("simple_epilogue", C.c_int32), ("_pad", C.c_int32)]  # fmt: skip
+                ("k_chunk", C.c_int32), ("simple_epilogue", C.c_int32), ("transposed_store", C.c_int32)]  # fmt: skip
 
 
 GEMM_LOOPS = ("plain2", "plain4", "quadrant", "ring", "persistent")  # KAI0_GEMM_LOOP_* in order

@@ -100,6 +100,10 @@ struct GemmArgs {
     const bf16_t* rope_cos;
     const bf16_t* rope_sin;
     int rope_half, rope_n_end;
+    // transposed second store (kai0hip.h ct / ct2): CT[n][m] = C[m][n] (act 6: h; act 3: dg) and CT2[n][m] = pre_out[m][n] (act 3: du)
+    bf16_t* ct;
+    bf16_t* ct2;
+    int64_t ldct, ldct2;
 };
 
 // LDS-DMA through a raw buffer descriptor: 16 B per lane from base + voff (bytes) to lds_dst + lane*16.  An offset at
@@ -118,6 +122,73 @@ __device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t vof
 __device__ __forceinline__ void store_pre8(bf16_t* dst, bf16x8 v, int nt) {
     if (nt) __builtin_nontemporal_store(v, reinterpret_cast<bf16x8*>(dst));
     else *reinterpret_cast<bf16x8*>(dst) = v;
+}
+
+// act 3 on 8 columns of a row, for the passes that also store transposed: v = dh (f32 accumulators), g / u = the forward's saved pair;
+// du = bf16(dh * bf16(gelu(g))), dg = bf16(bf16(dh * u) * gelu'(g)) with dh = bf16(v) — the statements of the fused epilogues' own act-3
+// branch, which stay where they are so that launches without a transposed store compile as they did.
+__device__ __forceinline__ void geglu_bwd8(const float (&v)[8], bf16x8 g, bf16x8 u, bf16x8& du, bf16x8& dg) {
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) {
+        const f32x2 dh = rbf2(f32x2{v[e], v[e + 1]});
+        f32x2 gl, gr;
+        gelu_tanh_both2(f32x2{bf2f(g[e]), bf2f(g[e + 1])}, gl, gr);
+        const f32x2 a = dh * rbf2(gl);
+        const f32x2 b = rbf2(dh * f32x2{bf2f(u[e]), bf2f(u[e + 1])}) * gr;
+        du[e] = f2bf(a[0]);
+        du[e + 1] = f2bf(a[1]);
+        dg[e] = f2bf(b[0]);
+        dg[e + 1] = f2bf(b[1]);
+    }
+}
+
+// Transposed second store (kai0hip.h ct / ct2) of one pass of a wave's 256 x 256 epilogue.  The pass's 512 bf16 results — 8 consecutive
+// columns of one row per lane, the very bits of the row-major store — go back, row-major, into the part of the wave's slab whose
+// accumulators the pass has just consumed, and leave it through ds_read_b64_tr_b16, which hands every lane 8 consecutive ROWS of one
+// column: one 16-byte store along m of CT.  The image is 16 rows x 32 columns (COLS = 32, act 6: lane = (row lane >> 2, column group
+// lane & 3), 64-byte rows) or 8 x 64 (COLS = 64, act 3: lane = (lane >> 3, lane & 7), rows of 192 bytes with 128 used); with these
+// pitches the four rows a 32-lane half of the transposed read touches cover the 64 banks once, and the b128 writes are contiguous
+// per 8 lanes.  EVERY lane of the wave must execute it (the transposed read gathers across lanes): lanes outside the problem hand in
+// zeros that no lane stores.  M % 8 == 0 (host), so a 16-byte run is inside the problem or outside it as a whole.
+template <int COLS>
+__device__ __forceinline__ void ct_pass(char* img, bf16x8 v, int lane, bf16_t* ct, int64_t ldct, int row0, int col0, int M, int ncols) {
+    constexpr int LD = COLS == 32 ? 32 : 96;  // image pitch (elements)
+    constexpr int CB = COLS / 16;             // 16-column blocks per image row
+    const int wr = COLS == 32 ? lane >> 2 : lane >> 3, wc = (COLS == 32 ? lane & 3 : lane & 7) * 8;
+    asm volatile("" ::: "memory");  // the pass's slab reads stay in front of the image's writes (one wave's LDS operations run in order)
+    *reinterpret_cast<bf16x8*>(img + (wr * LD + wc) * 2) = v;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    const int l15 = lane & 15, g = lane >> 4, cb = g % CB, ro = g / CB;
+    const char* q = img + ((8 * ro + (l15 >> 2)) * LD + 16 * cb + 4 * (l15 & 3)) * 2;
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LDS_PTR(bf16x4))(q));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LDS_PTR(bf16x4))(q + 4 * LD * 2));
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the image is free again: the next pass may write the slab
+    __builtin_amdgcn_wave_barrier();
+    const int col = col0 + 16 * cb + l15, row = row0 + 8 * ro;
+    if (col < ncols && row < M) *reinterpret_cast<bf16x8*>(ct + (int64_t)col * ldct + row) = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// The persistent kernel's form of the transposed store: its slab is 4 KiB per wave, so it keeps the bf16 results of four passes in
+// registers, lays 64 rows x 32 columns of them into the slab at once (64-byte rows; the caller writes them, 16 bytes per lane and
+// row) and calls this to empty it: four pairs of transposed reads, each handing a 16-lane group 8 rows x 16 columns, and four stores
+// that write, for each of 16 columns, the 64 contiguous bytes (32 rows) the four groups hold — a quarter of the write transactions
+// of ct_pass's 16-byte runs, which is what the producer's growth is made of (profiles/mlp_wgrad_nt.txt).  Every lane executes it.
+__device__ __forceinline__ void ct_round(const char* img, int lane, bf16_t* ct, int64_t ldct, int row0, int col0, int M, int ncols) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    const int l15 = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int cb = j & 1, oct = (j >> 1) * 4 + g;
+        const char* q = img + ((8 * oct + (l15 >> 2)) * 32 + 16 * cb + 4 * (l15 & 3)) * 2;
+        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LDS_PTR(bf16x4))(q));
+        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LDS_PTR(bf16x4))(q + 4 * 64));
+        const int col = col0 + 16 * cb + l15, row = row0 + 8 * oct;
+        if (col < ncols && row < M) *reinterpret_cast<bf16x8*>(ct + (int64_t)col * ldct + row) = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slab is free again
+    __builtin_amdgcn_wave_barrier();
 }
 
 // The fused epilogue on 8 consecutive columns [ccol, ccol+8) of output row `row` (v = f32 accumulators), shared by the
@@ -287,8 +358,11 @@ __device__ __forceinline__ void lds_barrier() {
 //   ring (SCH = 3; NS = 4, BKT = 32): 4 slots of 32 KiB, three 32-deep sub-tiles in flight, every load slot carries 12
 //     fragment reads and every MFMA slot 32 MFMAs + the 4 DMA pieces of a sub-tile, with nothing conditional inside the loop
 //     (tail pieces are issued out of range = zero fill).
-template <bool A_KC, bool B_KC, int WM, int WN, int MT, int NT, bool PP, int NS = 2, int BKT = 64, int SCH = 0>
+// CT = true: the instantiation whose act-0 / act-6 / act-3 epilogues also store transposed (ct_pass) — a kernel of its own, so that every launch
+// without a transposed store runs the code it ran before (inside one kernel the extra branch cost the 256 x 256 NT tile 500 bytes of scratch).
+template <bool A_KC, bool B_KC, int WM, int WN, int MT, int NT, bool PP, int NS = 2, int BKT = 64, int SCH = 0, bool CT = false>
 __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_kernel(const GemmArgs p) {
+    static_assert(!CT || (MT == 8 && A_KC && B_KC && SCH == 1), "the transposed store is built for the 256 x 256 NT quadrant tile only");
     static_assert(PP ? (WM == 2 && WN == 4 && MT == 8 && ((SCH == 1 && NS == 2 && BKT == 64) || (SCH == 3 && NS == 4 && BKT == 32)))
                      : (SCH == 0 && NS >= 2 && BKT == 64),
                   "K loops: plain multi-stage (SCH 0, 64 deep), quadrant (SCH 1: 256x256x64, 2 stages), ring (SCH 3: 256x256x32, 4 slots)");
@@ -772,6 +846,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
     // the persistent kernel: 9.7 -> 4.6 us per tile for a plain store (profiles/r05_gemm_persistent_phases.txt).  Same order and rounding
     // points as epilogue8; kai0_gemm_desc.general_epilogue = 1 sends these launches through the general path (tests).
     const bool simple_fast = MT == 8 && SIMPLE_EPILOGUE_APPLIES(p.simple_epi, p.act, p.split_k, p.gate, p.out_f32, p.scale, p.cmap.rpb, p.N);
+    constexpr bool CT_TILE = CT;  // (the host launches this instantiation exactly when p.ct is set)
     auto epi_half = [&](auto hc) {
         constexpr int h = decltype(hc)::value;
         if constexpr (((MT == 4 && WM == 2) || (MT == 2 && WM == 4)) && WN == 2 && A_KC && B_KC) if (p.act == 7) {
@@ -850,25 +925,61 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
                 const float* sp = slab + lr * 64 + (lane & 3) * 8;
                 const f32x4 g0 = *reinterpret_cast<const f32x4*>(sp), g1 = *reinterpret_cast<const f32x4*>(sp + 4);
                 const f32x4 u0 = *reinterpret_cast<const f32x4*>(sp + 32), u1 = *reinterpret_cast<const f32x4*>(sp + 36);
-                if (row >= p.M || !ocol_ok) continue;
-                const float gv[8] = {g0[0], g0[1], g0[2], g0[3], g1[0], g1[1], g1[2], g1[3]};
-                const float uv[8] = {u0[0], u0[1], u0[2], u0[3], u1[0], u1[1], u1[2], u1[3]};
-                bf16x8 gb, ub, hb;
+                bf16x8 hb = bf16x8{};
+                if (row < p.M && ocol_ok) {
+                    const float gv[8] = {g0[0], g0[1], g0[2], g0[3], g1[0], g1[1], g1[2], g1[3]};
+                    const float uv[8] = {u0[0], u0[1], u0[2], u0[3], u1[0], u1[1], u1[2], u1[3]};
+                    bf16x8 gb, ub;
 #pragma unroll
-                for (int e = 0; e < 8; e += 2) {
-                    const f32x2 gr = rbf2(f32x2{gv[e], gv[e + 1]}), ur = rbf2(f32x2{uv[e], uv[e + 1]});
-                    const f32x2 hv = rbf2(gelu_tanh2(gr)) * ur;
-                    gb[e] = f2bf(gr[0]);
-                    gb[e + 1] = f2bf(gr[1]);
-                    ub[e] = f2bf(ur[0]);
-                    ub[e + 1] = f2bf(ur[1]);
-                    hb[e] = f2bf(hv[0]);
-                    hb[e + 1] = f2bf(hv[1]);
+                    for (int e = 0; e < 8; e += 2) {
+                        const f32x2 gr = rbf2(f32x2{gv[e], gv[e + 1]}), ur = rbf2(f32x2{uv[e], uv[e + 1]});
+                        const f32x2 hv = rbf2(gelu_tanh2(gr)) * ur;
+                        gb[e] = f2bf(gr[0]);
+                        gb[e + 1] = f2bf(gr[1]);
+                        ub[e] = f2bf(ur[0]);
+                        ub[e + 1] = f2bf(ur[1]);
+                        hb[e] = f2bf(hv[0]);
+                        hb[e + 1] = f2bf(hv[1]);
+                    }
+                    const int64_t o = cz + p.cmap(row) * p.ldc + ocol;
+                    *reinterpret_cast<bf16x8*>(cb + o) = hb;
+                    if (p.pre_out != nullptr) store_pre8(p.pre_out + o, gb, p.nt_pre);
+                    if (p.pre_out2 != nullptr) store_pre8(p.pre_out2 + o, ub, p.nt_pre);
                 }
-                const int64_t o = cz + p.cmap(row) * p.ldc + ocol;
-                *reinterpret_cast<bf16x8*>(cb + o) = hb;
-                if (p.pre_out != nullptr) store_pre8(p.pre_out + o, gb, p.nt_pre);
-                if (p.pre_out2 != nullptr) store_pre8(p.pre_out2 + o, ub, p.nt_pre);
+                if constexpr (CT_TILE)  // hT: the image takes the 16 slab rows this pass has just read
+                    ct_pass<32>(reinterpret_cast<char*>(slab + it * 16 * 64), hb, lane, p.ct, p.ldct, row_base(h) + it * 16,
+                                (n0 >> 1) + wn * 32, p.M, p.N >> 1);
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            return;
+        }
+        if constexpr (CT_TILE) if (p.act == 0) {
+            // the plain product with CT (host: no bias / gate / residual / accumulate / scale / segments): C = bf16(acc), as the
+            // store-with-little-else epilogue rounds it, and each 8-row pass transposed out of the slab rows it has just read
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) slab[(i * 16 + 4 * g + r) * 64 + j * 16 + l15] = acc[h * 4 + i][j][r];
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            bf16_t* cb = reinterpret_cast<bf16_t*>(p.C);
+            const int rbase = row_base(h) + (lane >> 3);
+#pragma unroll
+            for (int it = 0; it < 8; ++it) {
+                const int row = rbase + it * 8;
+                const float* sp = slab + (it * 8 + (lane >> 3)) * 64 + (lane & 7) * 8;
+                const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp), v1 = *reinterpret_cast<const f32x4*>(sp + 4);
+                const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                bf16x8 ov = bf16x8{};
+                if (row < p.M && col_ok) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) ov[e] = f2bf(rbf(v[e]));
+                    store_pre8(cb + cz + p.cmap(row) * p.ldc + ccol, ov, p.nt_c);
+                }
+                ct_pass<64>(reinterpret_cast<char*>(slab + it * 8 * 64), ov, lane, p.ct, p.ldct, row_base(h) + it * 8, n0 + wn * 64, p.M, p.N);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
@@ -907,6 +1018,20 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
                 const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp);
                 const f32x4 v1 = *reinterpret_cast<const f32x4*>(sp + 4);
                 const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                if constexpr (CT_TILE) {  // act 3 with dgT / duT (host: of the fused forms only act 3 reaches this instantiation)
+                    // the arithmetic of the act-3 branch below, then the two transposed stores, outside the edge test: every lane takes part
+                    bf16x8 du = bf16x8{}, dgv = bf16x8{};
+                    if (row < p.M && col_ok) {
+                        const int64_t o = cz + p.cmap(row) * p.ldc + ccol;
+                        geglu_bwd8(v, s0[it], s1[it], du, dgv);
+                        *reinterpret_cast<bf16x8*>(p.pre_out + o) = du;
+                        *reinterpret_cast<bf16x8*>(cb + o) = dgv;
+                    }
+                    char* img = reinterpret_cast<char*>(slab + it * 8 * 64);  // the 8 slab rows this pass has just read
+                    ct_pass<64>(img, dgv, lane, p.ct, p.ldct, row_base(h) + it * 8, n0 + wn * 64, p.M, p.N);
+                    ct_pass<64>(img, du, lane, p.ct2, p.ldct2, row_base(h) + it * 8, n0 + wn * 64, p.M, p.N);
+                    continue;
+                }
                 if (row >= p.M || !col_ok) continue;
                 const int64_t o = cz + p.cmap(row) * p.ldc + ccol;
                 bf16x8 ov;
@@ -1204,6 +1329,7 @@ __device__ long long g_ps_trace[256][8];
 #define PS_STAMP(i) do { } while (0)
 #endif
 
+template <bool CT>  // CT: also the transposed second store (ct_pass), as gemm_bf16_kernel's CT — a kernel of its own for the same reason
 __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmArgs p, unsigned int* __restrict__ ctr) {
     constexpr int TBM = 256, TBN = 256, A_TILE = TBM * BK * 2, STAGE = 2 * A_TILE, GROUP = 4, MT = 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1423,6 +1549,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
             const int ocol = (n0c >> 1) + wn * 32 + (lane & 3) * 8;
             const bool ocol_ok = ocol < (p.N >> 1);
             bf16_t* cb = reinterpret_cast<bf16_t*>(p.C);
+            bf16x8 hk[4];  // (CT only)
 #pragma unroll
             for (int ti = 0; ti < MT; ++ti) {
                 to_slab(ti);
@@ -1430,10 +1557,11 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
                 const float* sp = slab + (lane >> 2) * 64 + (lane & 3) * 8;
                 const f32x4 g0 = *reinterpret_cast<const f32x4*>(sp), g1 = *reinterpret_cast<const f32x4*>(sp + 4);
                 const f32x4 u0 = *reinterpret_cast<const f32x4*>(sp + 32), u1 = *reinterpret_cast<const f32x4*>(sp + 36);
+                bf16x8 hb = bf16x8{};
                 if (row < p.M && ocol_ok) {
                     const float gv[8] = {g0[0], g0[1], g0[2], g0[3], g1[0], g1[1], g1[2], g1[3]};
                     const float uv[8] = {u0[0], u0[1], u0[2], u0[3], u1[0], u1[1], u1[2], u1[3]};
-                    bf16x8 gb, ub, hb;
+                    bf16x8 gb, ub;
 #pragma unroll
                     for (int e = 0; e < 8; e += 2) {
                         const f32x2 gr = rbf2(f32x2{gv[e], gv[e + 1]}), ur = rbf2(f32x2{uv[e], uv[e + 1]});
@@ -1447,6 +1575,16 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
                     if (p.pre_out != nullptr) store_pre8(p.pre_out + o, gb, p.nt_pre);
                     if (p.pre_out2 != nullptr) store_pre8(p.pre_out2 + o, ub, p.nt_pre);
                 }
+                if constexpr (CT) {  // hT (ct_round): four passes' results = 64 rows x 32 columns, into the slab the fourth has just read
+                    hk[ti & 3] = hb;
+                    if ((ti & 3) == 3) {
+                        char* img = reinterpret_cast<char*>(slab);
+                        asm volatile("" ::: "memory");  // this pass's slab reads stay in front of the image's writes
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) *reinterpret_cast<bf16x8*>(img + ((k * 16 + (lane >> 2)) * 32 + (lane & 3) * 8) * 2) = hk[k];
+                        ct_round(img, lane, p.ct, p.ldct, m0c + wm * 128 + (ti - 3) * 16, (n0c >> 1) + wn * 32, p.M, p.N >> 1);
+                    }
+                }
             }
         } else if (fused_fast) {
             bf16_t* cb = reinterpret_cast<bf16_t*>(p.C);
@@ -1454,6 +1592,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
             for (int h = 0; h < 2; ++h) {
                 // the extra [M][N] operands of this 64-row half requested before its accumulators go through the slab
                 bf16x8 s0[8], s1[8];
+                bf16x8 rdg[8], rdu[8];  // (CT only)
                 float ds[8];
                 const int rbase = m0c + wm * 128 + h * 64 + (lane >> 3);
 #pragma unroll
@@ -1479,6 +1618,17 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
                         const float* sp = slab + (it2 * 8 + (lane >> 3)) * 64 + (lane & 7) * 8;
                         const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp), v1 = *reinterpret_cast<const f32x4*>(sp + 4);
                         const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                        if constexpr (CT) {  // act 3 with dgT / duT: the half's results stay in registers (where s0 / s1 were) for ct_round below
+                            rdg[it] = bf16x8{};
+                            rdu[it] = bf16x8{};
+                            if (row < p.M && col_ok) {
+                                const int64_t o = p.cmap(row) * p.ldc + ccol;
+                                geglu_bwd8(v, s0[it], s1[it], rdu[it], rdg[it]);
+                                *reinterpret_cast<bf16x8*>(p.pre_out + o) = rdu[it];
+                                *reinterpret_cast<bf16x8*>(cb + o) = rdg[it];
+                            }
+                            continue;
+                        }
                         if (row >= p.M || !col_ok) continue;
                         const int64_t o = p.cmap(row) * p.ldc + ccol;
                         bf16x8 ov;
@@ -1522,6 +1672,42 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
                         }
                         *reinterpret_cast<bf16x8*>(cb + o) = ov;
                     }
+                }
+                if constexpr (CT) {
+                    // dgT, duT of this 64-row half (ct_round): the slab has been read out; four images of 64 rows x 32 columns — dg's and
+                    // du's left and right column halves, written by the lanes that hold those columns
+                    char* img = reinterpret_cast<char*>(slab);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        asm volatile("" ::: "memory");
+                        if (((lane & 7) >> 2) == (r & 1)) {
+#pragma unroll
+                            for (int it = 0; it < 8; ++it)
+                                *reinterpret_cast<bf16x8*>(img + ((it * 8 + (lane >> 3)) * 32 + (lane & 3) * 8) * 2) = r < 2 ? rdg[it] : rdu[it];
+                        }
+                        ct_round(img, lane, r < 2 ? p.ct : p.ct2, r < 2 ? p.ldct : p.ldct2, m0c + wm * 128 + h * 64, n0c + wn * 64 + (r & 1) * 32, p.M, p.N);
+                    }
+                }
+            }
+        } else if (CT && p.act == 0) {
+            // the plain product with CT, as in gemm_bf16_kernel (16-byte runs: no production launch takes this form)
+            bf16_t* cb = reinterpret_cast<bf16_t*>(p.C);
+#pragma unroll
+            for (int ti = 0; ti < MT; ++ti) {
+                to_slab(ti);
+#pragma unroll
+                for (int it2 = 0; it2 < 2; ++it2) {
+                    const int row0 = m0c + wm * 128 + ti * 16 + it2 * 8, row = row0 + (lane >> 3);
+                    const float* sp = slab + (it2 * 8 + (lane >> 3)) * 64 + (lane & 7) * 8;
+                    const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp), v1 = *reinterpret_cast<const f32x4*>(sp + 4);
+                    const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                    bf16x8 ov = bf16x8{};
+                    if (row < p.M && col_ok) {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) ov[e] = f2bf(rbf(v[e]));
+                        store_pre8(cb + p.cmap(row) * p.ldc + ccol, ov, p.nt_c);
+                    }
+                    ct_pass<64>(reinterpret_cast<char*>(slab + it2 * 8 * 64), ov, lane, p.ct, p.ldct, row0, n0c + wn * 64, p.M, p.N);
                 }
             }
         } else if (simple_fast) {
@@ -1802,7 +1988,7 @@ constexpr int layout_bit(bool a_kc, bool b_kc) { return 1 << (2 * a_kc + b_kc); 
 constexpr int L_NT = layout_bit(true, true), L_NN = layout_bit(true, false), L_TT = layout_bit(false, true), L_TN = layout_bit(false, false);
 constexpr int L_ALL = L_NT | L_NN | L_TT | L_TN;
 
-template <int LAYOUTS, int WM, int WN, int MT, int NT, bool PP, int NS = 2, int BKT = 64, int SCH = 0>
+template <int LAYOUTS, int WM, int WN, int MT, int NT, bool PP, int NS = 2, int BKT = 64, int SCH = 0, bool CT = false>
 int launch_cfg(const kai0_gemm_desc* d, GemmArgs& p, int batch, hipStream_t s) {
     constexpr int TBM = WM * MT * 16, TBN = WN * NT * 16;
     constexpr int LDS = NS * (TBM + TBN) * BKT * 2;
@@ -1813,7 +1999,7 @@ int launch_cfg(const kai0_gemm_desc* d, GemmArgs& p, int batch, hipStream_t s) {
     if constexpr ((LAYOUTS & layout_bit(AK, BK_)) != 0)                                                          \
         if ((d->a_kc != 0) == AK && (d->b_kc != 0) == BK_) {                                                      \
             static bool attr_set = false;                                                                         \
-            auto kern = gemm_bf16_kernel<AK, BK_, WM, WN, MT, NT, PP, NS, BKT, SCH>;                              \
+            auto kern = gemm_bf16_kernel<AK, BK_, WM, WN, MT, NT, PP, NS, BKT, SCH, CT>;                             \
             if (!attr_set) {                                                                                      \
                 hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); \
                 if (e != hipSuccess) {                                                                            \
@@ -1842,6 +2028,8 @@ KAI0_API int kai0_debug_ps_trace(long long* host_out) {
     return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_ps_trace), sizeof(long long) * 256 * 8);
 }
 #endif
+
+static kai0_gemm_plan_t gemm_select(const kai0_gemm_desc* d);
 
 // Everything kai0_gemm_bf16 refuses, checked on the descriptor alone (no device call): shared by the launch and by kai0_gemm_plan.
 static int gemm_validate(const kai0_gemm_desc* d) {
@@ -1921,6 +2109,23 @@ static int gemm_validate(const kai0_gemm_desc* d) {
                      "kai0_gemm_bf16: split_k=%d needs a workspace of batch*split*M*N*4 bytes", d->split_k);
         KAI0_REQUIRE((d->N % 8) == 0, "kai0_gemm_bf16: split_k needs N %% 8 == 0");
     }
+    if (d->ct != nullptr || d->ct2 != nullptr) {
+        // the transposed second store lives in the 256 x 256 NT epilogues of act 6 and of the plain fused act 3 (ct_pass); any other
+        // launch would drop it silently, so it is refused
+        KAI0_REQUIRE(((d->act == 6 || d->act == 0) && d->ct && !d->ct2) || (d->act == 3 && d->ct && d->ct2),
+                     "kai0_gemm_bf16: a transposed store needs act=0 or act=6 with ct (no ct2), or act=3 with ct and ct2 (act=%d)", d->act);
+        KAI0_REQUIRE(d->split_k <= 1 && !d->out_f32 && d->nseg == 0 && d->c_rpb == 0 && d->batch <= 1,
+                     "kai0_gemm_bf16: a transposed store excludes split-K, an f32 output, column segments, an output row map and batches");
+        KAI0_REQUIRE((d->M % 8) == 0 && (d->ldct % 8) == 0 && d->ldct >= d->M && ((uintptr_t)d->ct % 16) == 0 &&
+                         (!d->ct2 || ((d->ldct2 % 8) == 0 && d->ldct2 >= d->M && ((uintptr_t)d->ct2 % 16) == 0)),
+                     "kai0_gemm_bf16: a transposed store needs M %% 8 == 0, ldct %% 8 == 0, ldct >= M and 16-byte aligned ct / ct2 (M=%d ldct=%lld "
+                     "ldct2=%lld)", d->M, (long long)d->ldct, (long long)d->ldct2);
+        KAI0_REQUIRE(d->act == 6 || (!d->bias && !d->gate && !d->residual && !d->accumulate && (d->scale == 0.0f || d->scale == 1.0f)),
+                     "kai0_gemm_bf16: a transposed store with act=0 / act=3 needs the plain form (no bias / gate / residual / accumulate / scale)");
+        KAI0_REQUIRE(d->act != 0 || ((d->N % 8) == 0 && !d->pre_out), "kai0_gemm_bf16: a transposed store with act=0 needs N %% 8 == 0 and no pre_out");
+        KAI0_REQUIRE(d->a_kc && d->b_kc && gemm_select(d).tile == 256,
+                     "kai0_gemm_bf16: a transposed store needs K-contiguous operands and a problem of the 256 x 256 tile (>= 160 tiles, K >= 256)");
+    }
     return 0;
 }
 
@@ -1974,6 +2179,7 @@ static kai0_gemm_plan_t gemm_select(const kai0_gemm_desc* d) {
     // the kernels' own condition, on the values the launch hands them (GemmArgs: simple_epi, the normalised scale, the logical width)
     pl.simple_epilogue = big && SIMPLE_EPILOGUE_APPLIES(d->general_epilogue == 0, d->act, split, d->gate, d->out_f32,
                                                         (d->scale == 0.0f ? 1.0f : d->scale), d->c_rpb, N);
+    pl.transposed_store = d->ct != nullptr;  // (validated: only launches whose epilogue carries it get this far with ct set)
     return pl;
 }
 
@@ -2005,6 +2211,7 @@ KAI0_API int kai0_gemm_bf16(const kai0_gemm_desc* d, kai0_stream_t stream) {
     p.rope_sin = (const bf16_t*)d->rope_sin;
     p.rope_half = d->rope_half;
     p.rope_n_end = d->rope_n_end;
+    p.ct = (bf16_t*)d->ct; p.ct2 = (bf16_t*)d->ct2; p.ldct = d->ldct; p.ldct2 = d->ldct2;
     p.lda = d->lda; p.ldb = d->ldb; p.ldc = d->ldc;
     p.batch_inner = d->batch_inner > 0 ? d->batch_inner : 1;
     p.sA1 = d->sA1; p.sA2 = d->sA2; p.sB1 = d->sB1; p.sB2 = d->sB2; p.sC1 = d->sC1; p.sC2 = d->sC2;
@@ -2058,7 +2265,8 @@ KAI0_API int kai0_gemm_bf16(const kai0_gemm_desc* d, kai0_stream_t stream) {
         if (pd.ctr == nullptr) {
             void* sym = nullptr;
             hipError_t e = hipGetSymbolAddress(&sym, HIP_SYMBOL(g_ps_ctr));
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_nt_persistent_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_nt_persistent_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_nt_persistent_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
             hipDeviceProp_t pr;
             if (e == hipSuccess) e = hipGetDeviceProperties(&pr, dv);
             KAI0_REQUIRE(e == hipSuccess, "kai0_gemm_bf16: persistent kernel setup failed: %s", hipGetErrorString(e));
@@ -2070,10 +2278,12 @@ KAI0_API int kai0_gemm_bf16(const kai0_gemm_desc* d, kai0_stream_t stream) {
         p.tiles_n = (p.N + 255) / 256;
         const int nblk = (int)std::min<int64_t>(big_tiles, pd.cus);
         unsigned int* ctr = ctr_base + (size_t)(next_slot.fetch_add(1) % PS_SLOTS) * 16;
-        hipLaunchKernelGGL(gemm_nt_persistent_kernel, dim3(nblk), dim3(512), LDS, s, p, ctr);
+        if (p.ct != nullptr) hipLaunchKernelGGL(gemm_nt_persistent_kernel<true>, dim3(nblk), dim3(512), LDS, s, p, ctr);
+        else hipLaunchKernelGGL(gemm_nt_persistent_kernel<false>, dim3(nblk), dim3(512), LDS, s, p, ctr);
         return kai0_check_launch("kai0_gemm_bf16 (persistent)");
     }
-    if (pl.tile == 256 && pl.loop == KAI0_GEMM_LOOP_QUADRANT) rc = launch_cfg<L_NT, 2, 4, 8, 4, true, 2, 64, 1>(d, p, batch, s);
+    if (pl.tile == 256 && pl.loop == KAI0_GEMM_LOOP_QUADRANT && p.ct != nullptr) rc = launch_cfg<L_NT, 2, 4, 8, 4, true, 2, 64, 1, true>(d, p, batch, s);
+    else if (pl.tile == 256 && pl.loop == KAI0_GEMM_LOOP_QUADRANT) rc = launch_cfg<L_NT, 2, 4, 8, 4, true, 2, 64, 1>(d, p, batch, s);
     else if (pl.tile == 256 && pl.loop == KAI0_GEMM_LOOP_RING) rc = launch_cfg<L_TN, 2, 4, 8, 4, true, 4, 32, 3>(d, p, batch, s);
     else if (pl.tile == 256) rc = launch_cfg<L_NN | L_TT, 2, 4, 8, 4, false>(d, p, batch, s);
     else if (pl.waves == 8) rc = launch_cfg<L_NT, 4, 2, 2, 4, false, 4>(d, p, batch, s);

@@ -78,6 +78,7 @@ def gemm(
     accumulate: bool = False, a_off_elems: int = 0, b_off_elems: int = 0, c_off_elems: int = 0, split_k: int = 1,
     aux1: torch.Tensor | None = None, aux2: torch.Tensor | None = None, segs=None, rowvec=None, rv=(0, 0, 1),
     B2: torch.Tensor | None = None, pre_out2: torch.Tensor | None = None, norm=None, nt_out: bool = False, rope=None,
+    ct: torch.Tensor | None = None, ldct: int = 0, ct2: torch.Tensor | None = None, ldct2: int = 0,
     _plan: "_lib.GemmPlan | None" = None,
 ) -> torch.Tensor:  # fmt: skip
     """kai0_gemm_bf16. `*_map` = (rows_per_batch, batch_stride_rows, row_offset). `*_off_elems` shift the base
@@ -125,6 +126,10 @@ def gemm(
             raise TypeError("gemm: B2 must be a bf16 HIP tensor")
         d.B2 = B2.data_ptr()
     d.pre_out2 = _p(pre_out2)
+    for name, t in (("ct", ct), ("ct2", ct2)):  # transposed second store (kai0hip.h): act 0 and act 6 -> ct = C^T; act 3 -> ct = C^T, ct2 = pre_out^T
+        if t is not None and (t.dtype != BF16 or not t.is_cuda):
+            raise TypeError(f"gemm: {name} must be a bf16 HIP tensor")
+    d.ct, d.ldct, d.ct2, d.ldct2 = _p(ct), ldct, _p(ct2), ldct2
     if gate is not None:
         d.gate = gate.data_ptr()
         d.gate_rpb = gate_rpb
@@ -165,14 +170,20 @@ def gemm(
     return out
 
 
+_gemm = gemm  # gemm_plan's handle: a plan is no launch, so a wrapper installed over `ops.gemm` to time or count launches never sees one
+
+
 def gemm_plan(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, **kw) -> dict:
     """kai0_gemm_plan for exactly the descriptor `gemm(A, B, out, **kw)` would launch (the GEMM_TUNING hooks included): which tile,
-    wave count and K loop the library selects, its tile counts, the split-K chunk and whether the simple epilogue applies.  Launches
-    nothing."""
+    wave count and K loop the library selects, its tile counts, the split-K chunk, whether the simple epilogue applies and, for a
+    descriptor with `ct`, that the launch stores it.  Launches nothing."""
     pl = _lib.GemmPlan()
-    gemm(A, B, out, _plan=pl, **kw)
-    return {"tile": pl.tile, "waves": pl.waves, "loop": _lib.GEMM_LOOPS[pl.loop], "tiles_m": pl.tiles_m, "tiles_n": pl.tiles_n,
+    _gemm(A, B, out, _plan=pl, **kw)
+    plan = {"tile": pl.tile, "waves": pl.waves, "loop": _lib.GEMM_LOOPS[pl.loop], "tiles_m": pl.tiles_m, "tiles_n": pl.tiles_n,
             "k_chunk": pl.k_chunk, "simple_epilogue": bool(pl.simple_epilogue)}
+    if kw.get("ct") is not None:  # (reported for the descriptors that ask for it)
+        plan["transposed_store"] = bool(pl.transposed_store)
+    return plan
 
 
 def skinny_split_k(N: int, K: int) -> int:
@@ -996,6 +1007,26 @@ def set_geglu_pair(on: bool) -> bool:
     return old
 
 
+# The Gemma MLP's weight gradients with both operands K-contiguous (NT, the 64-deep loop: +24 % over the TN ring on the 30976-row
+# contraction, profiles/mlp_wgrad_nt.txt).  hT, dgT and duT come out of the producers' epilogues (kai0hip.h ct / ct2), xT and doutT
+# ([D][rows], small) from kai0_transpose_bf16.  Long row counts only: the expert's 1600 rows keep the TN path (their GEMMs are too
+# small for the 256 x 256 tile that stores transposed, and a transpose launch each would cost what NT saves), and so does every MLP
+# whose producer launch does not take that tile (kai0_gemm_plan is asked: no stand-alone transpose of a [rows][F] operand is ever
+# made).  Same bits as TN wherever both run one K split.  set_mlp_wgrad_nt(False): the TN path everywhere (tests).
+_MLP_WGRAD_NT = True
+_MLP_WGRAD_NT_MIN_ROWS = 4096
+
+
+def set_mlp_wgrad_nt(on: bool) -> bool:
+    global _MLP_WGRAD_NT
+    old, _MLP_WGRAD_NT = _MLP_WGRAD_NT, bool(on)
+    return old
+
+
+def _mlp_wgrad_nt(rows: int) -> bool:
+    return _MLP_WGRAD_NT and rows >= _MLP_WGRAD_NT_MIN_ROWS and rows % 8 == 0
+
+
 class GegluMlpFn(torch.autograd.Function):
     """Gemma MLP `down(gelu_tanh(gate(x)) * up(x)) (+ residual)` (modeling_gemma.py:113-126) as three GEMMs with the
     GeGLU fused into epilogues: forward in the up-projection GEMM (reads g, writes u and h), backward in the
@@ -1009,16 +1040,26 @@ class GegluMlpFn(torch.autograd.Function):
         F = wg.shape[0]
         u = torch.empty((M, F), dtype=BF16, device=x.device)
         h = torch.empty((M, F), dtype=BF16, device=x.device)
-        if _GEGLU_PAIR and F % 32 == 0:
+        pair = _GEGLU_PAIR and F % 32 == 0
+        hT = None
+        if pair:
             # gate | up as ONE GEMM over the two weights, GeGLU in registers (act 6): no read-back of g in an epilogue
             g = torch.empty((M, F), dtype=BF16, device=x.device)
-            gemm(x, wg, h, M=M, N=F, K=D, lda=D, ldb=D, ldc=F, act=6, B2=wu, pre_out=g, pre_out2=u)
+            kw = dict(M=M, N=F, K=D, lda=D, ldb=D, ldc=F, act=6, B2=wu, pre_out=g, pre_out2=u)
+            if _mlp_wgrad_nt(M) and ctx.needs_input_grad[3] and gemm_plan(x, wg, h, **kw)["tile"] == 256:
+                # hT [F][rows] for the NT down wgrad, stored by this launch's epilogue
+                hT = torch.empty((F, M), dtype=BF16, device=x.device)
+                kw.update(ct=hT, ldct=M)
+            gemm(x, wg, h, **kw)
         else:
             g = linear_fwd(x, wg)
             gemm(x, wu, h, M=M, N=F, K=D, lda=D, ldb=D, ldc=F, act=2, pre_out=u, aux1=g, split_k=1)
         out = linear_fwd(h, wd, residual=residual)
-        ctx.save_for_backward(x, wg, wu, wd, g, u, h)
+        # (the NT backward reads hT where the TN one reads h: one of the two is saved, never both)
+        ctx.save_for_backward(x, wg, wu, wd, g, u, h if hT is None else hT)
         ctx.has_res = residual is not None
+        ctx.nt_gate_up = pair and _mlp_wgrad_nt(M)
+        ctx.h_transposed = hT is not None
         return out
 
     @staticmethod
@@ -1034,15 +1075,38 @@ class GegluMlpFn(torch.autograd.Function):
             gemm(dy, inp, dw, M=n, N=k, K=M, a_kc=False, b_kc=False, lda=n, ldb=k, ldc=k, split_k=pick_split_k_wgrad(n, k, M), nt_out=True)
             return dw
 
-        dwd = wgrad(dout, h, wd, D, F) if ctx.needs_input_grad[3] else None
+        def wgrad_nt(dyT, inpT, dw, n, k):  # dW [n][k] = dyT [n][rows] @ inpT [k][rows]^T: both operands K-contiguous
+            return gemm(dyT, inpT, dw, M=n, N=k, K=M, lda=M, ldb=M, ldc=k, split_k=pick_split_k_wgrad(n, k, M), nt_out=True)
+
+        dwd = None
+        if ctx.needs_input_grad[3]:
+            dwd = wgrad_nt(transpose(dout), h, _grad_dst(wd, BF16), D, F) if ctx.h_transposed else wgrad(dout, h, wd, D, F)
         # dh = dout @ wd (through wd^T, K-contiguous) with the GeGLU backward in the epilogue: C = dg, pre_out = du
         dg = torch.empty((M, F), dtype=BF16, device=dev)
         du = torch.empty((M, F), dtype=BF16, device=dev)
         wdt = transpose(wd)  # [F, D]
-        gemm(dout, wdt, dg, M=M, N=F, K=D, lda=D, ldb=D, ldc=F, act=3, pre_out=du, aux1=g, aux2=u)
+        kw = dict(M=M, N=F, K=D, lda=D, ldb=D, ldc=F, act=3, pre_out=du, aux1=g, aux2=u)
+        need_g, need_u = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        dgduT = None
+        if ctx.nt_gate_up and need_g and need_u and gemm_plan(dout, wdt, dg, **kw)["tile"] == 256:
+            # dgT | duT [2F][rows], back to back, for the NT gate / up wgrads, stored by the act-3 epilogue
+            dgduT = torch.empty((2 * F, M), dtype=BF16, device=dev)
+            kw.update(ct=dgduT[:F], ldct=M, ct2=dgduT[F:], ldct2=M)
+        gemm(dout, wdt, dg, **kw)
         del wdt
-        dwg = wgrad(dg, x, wg, F, D) if ctx.needs_input_grad[1] else None
-        dwu = wgrad(du, x, wu, F, D) if ctx.needs_input_grad[2] else None
+        if dgduT is not None:
+            xT = transpose(x)  # [D][rows]
+            dwg, dwu = _grad_dst(wg, BF16), _grad_dst(wu, BF16)
+            both = _as_rows([dwg, dwu])
+            if both is not None:  # the gradient destinations lie back to back: one M = 2F launch
+                wgrad_nt(dgduT, xT, both, 2 * F, D)
+            else:
+                wgrad_nt(dgduT[:F], xT, dwg, F, D)
+                wgrad_nt(dgduT[F:], xT, dwu, F, D)
+            del xT, dgduT
+        else:
+            dwg = wgrad(dg, x, wg, F, D) if need_g else None
+            dwu = wgrad(du, x, wu, F, D) if need_u else None
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty((M, D), dtype=BF16, device=dev)
