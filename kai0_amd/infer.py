@@ -700,6 +700,7 @@ class InferenceEngine:
     def _dgrad(self, dy, w, *, a_map=None, into=None):
         """dx [M, K] = dy [M, N] @ w [N, K] (ops.LinearFn.backward's dgrad form); `into`: dx is added to it (one bf16 rounding).
         a_map: dy's rows addressed through kai0_gemm_desc's row remap."""
+        # (not ops.dgrad: this is the NN form inside a captured graph, and must never start transposing weights at 4096 rows)
         N, K = w.shape
         M = self.B * self.Hs
         if into is None:

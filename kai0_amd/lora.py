@@ -35,7 +35,7 @@ from typing import NamedTuple
 import torch
 
 from . import _lib, ops
-from .ops import BF16, F32, _grad_dst, _grad_ret, _stream, gemm
+from .ops import BF16, F32, _grad_dst, _grad_ret, _stream, dgrad, gemm, wgrad
 
 DOWN_KERNEL_R = (16, 32, 48, 64)  # kai0_lora_down's R
 # The measured dispatch rule (profiles/lora.txt, tools/probes/lora.py): kai0_lora_down beats kai0_gemm_bf16 at K = 1024 / 2048 (1.3-1.7 x),
@@ -205,30 +205,6 @@ def _dx_acc(dT, ad: Adapter, dx, t_off: int = 0, ldt: int | None = None):
     return dx
 
 
-def _dgrad(dy, w, dx=None, accumulate: bool = False):
-    """dx (+)= dy W through the base weight, as ops.LinearFn.backward does."""
-    M, N = dy.shape
-    K = w.shape[1]
-    if dx is None:
-        dx = torch.empty((M, K), dtype=BF16, device=dy.device)
-    if M >= 4096 and N % 8 == 0 and K % 8 == 0:
-        wt = ops.transpose(w)
-        gemm(dy, wt, dx, M=M, N=K, K=N, lda=N, ldb=N, ldc=K, accumulate=accumulate)
-    else:
-        gemm(dy, w, dx, M=M, N=K, K=N, b_kc=False, lda=N, ldb=K, ldc=K, accumulate=accumulate,
-             split_k=1 if accumulate else ops.pick_split_k(M, K, N))  # fmt: skip
-    return dx
-
-
-def _wgrad(dy, x, w):
-    """dW = dy^T x into the parameter's gradient destination."""
-    M, N = dy.shape
-    K = x.shape[1]
-    dw = _grad_dst(w, BF16)
-    gemm(dy, x, dw, M=N, N=K, K=M, a_kc=False, b_kc=False, lda=N, ldb=K, ldc=K, split_k=ops.pick_split_k_wgrad(N, K, M), nt_out=True)
-    return dw
-
-
 # -------------------------------------------------------------------------------------------------- autograd
 class LoraLinearFn(torch.autograd.Function):
     """y = x W^T + s bf16(bf16(x A^T) B^T) (+ residual, added after the delta): o_proj, and any single adapted Linear."""
@@ -260,8 +236,8 @@ class LoraLinearFn(torch.autograd.Function):
             dT = _dT(dy, ad, torch.empty_like(T))
         dx = None
         if need_x:
-            dx = _dx_acc(dT, ad, _dgrad(dy, w))
-        dw = _wgrad(dy, x, w) if need_w else None
+            dx = _dx_acc(dT, ad, dgrad(dy, w))
+        dw = wgrad(dy, x, w) if need_w else None
         da = _grad_a(x, dT, ad) if need_a else None
         db = _grad_b(dy, T, ad) if need_b else None
         return dx, _grad_ret(w, dw), _grad_ret(a, da), _grad_ret(b, db), (dout if ctx.has_res else None), None, None, None
@@ -325,10 +301,10 @@ class LoraLinearMultiFn(torch.autograd.Function):
             wcat = ops._as_rows([w.detach() for w in ws])
             if dycat is not None or wcat is not None:  # one dgrad over the stacked projection
                 dycat = torch.cat(dys, dim=1) if dycat is None else dycat
-                dx = _dgrad(dycat, torch.cat(ws, dim=0) if wcat is None else wcat)
+                dx = dgrad(dycat, torch.cat(ws, dim=0) if wcat is None else wcat)
             else:
                 for i, (dy, w) in enumerate(zip(dys, ws)):
-                    dx = _dgrad(dy.contiguous(), w, dx, accumulate=i > 0)
+                    dx = dgrad(dy.contiguous(), w, dx, accumulate=i > 0, split=i == 0)  # (the accumulating ones unsplit: as found)
             scales = {ad.scale for ad in ads}
             if len(scales) == 1:  # dx += s dT Acat: one launch over the stacked adapters
                 _dx_acc(dT, Adapter(acat, acat, scales.pop()), dx)
@@ -342,7 +318,7 @@ class LoraLinearMultiFn(torch.autograd.Function):
         for i, (dy, w, ad) in enumerate(zip(dys, ws, ads)):
             dyc = dy if dy.is_contiguous() else dy.contiguous()
             if need_w[i]:
-                dws[i] = _grad_ret(w, _wgrad(dyc, x, w))
+                dws[i] = _grad_ret(w, wgrad(dyc, x, w))
             if need_a[i]:
                 das[i] = _grad_ret(ad.a, _grad_a(x, dT, ad, t_off=off, ldt=Rt))
             if need_b[i]:
@@ -406,7 +382,7 @@ class LoraGegluMlpFn(torch.autograd.Function):
         r = ag.shape[0]
         dev = x.device
         need = ctx.needs_input_grad
-        dwd = _wgrad(dout, h, wd) if need[3] else None
+        dwd = wgrad(dout, h, wd) if need[3] else None
         dbd = _grad_b(dout, Td, Ad) if need[9] else None
         # [dout | dTd] [M, D + r] and [Wd^T | Ad^T] [F, D + r]: dh = dout Wd + dTd Ad in one contraction
         Kc = D + r
@@ -421,8 +397,8 @@ class LoraGegluMlpFn(torch.autograd.Function):
         du = torch.empty((M, F), dtype=BF16, device=dev)
         gemm(lhs, rhs, dg, M=M, N=F, K=Kc, lda=Kc, ldb=Kc, ldc=F, act=3, pre_out=du, aux1=g, aux2=u)
         del lhs, rhs
-        dwg = _wgrad(dg, x, wg) if need[1] else None
-        dwu = _wgrad(du, x, wu) if need[2] else None
+        dwg = wgrad(dg, x, wg) if need[1] else None
+        dwu = wgrad(du, x, wu) if need[2] else None
         dbg = _grad_b(dg, Tgu, Ag, t_off=0, ldt=2 * r) if need[5] else None
         dbu = _grad_b(du, Tgu, Au, t_off=r, ldt=2 * r) if need[7] else None
         dag = dau = dx = None
@@ -442,7 +418,7 @@ class LoraGegluMlpFn(torch.autograd.Function):
                     dsts[1].copy_(dagu[r:])
                 dag, dau = (dsts[0] if need[4] else None), (dsts[1] if need[6] else None)
             if need[0]:
-                dx = _dgrad(du, wu, _dgrad(dg, wg), accumulate=True)
+                dx = dgrad(du, wu, dgrad(dg, wg), accumulate=True, split=False)  # (the accumulating one unsplit: as found)
                 _dx_acc(dTgu, Adapter(agu, agu), dx)
         return (dx, _grad_ret(wg, dwg), _grad_ret(wu, dwu), _grad_ret(wd, dwd), _grad_ret(ag, dag), _grad_ret(bg, dbg),
                 _grad_ret(au, dau), _grad_ret(bu, dbu), _grad_ret(ad_, dad), _grad_ret(bd, dbd), (dout if ctx.has_res else None))  # fmt: skip

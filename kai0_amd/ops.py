@@ -446,6 +446,53 @@ def _grad_ret(param, g):
     return g
 
 
+# The two gradient GEMMs of a Linear, for every autograd shim here and in lora.py (the per-site table: DESIGN.md section 3).
+NT_MIN_ROWS = 4096  # from this many rows a weight is worth transposing for the K-contiguous (NT) loop
+
+
+def dgrad(dy, w, dx=None, *, ldy=None, ldx=None, accumulate=False, split=True, nt=None, wt=None, plan=False, **epilogue):
+    """dx [M, K] (+)= dy [M, N] @ w [N, K]; `dx` is allocated when none is given.  Many rows (and N % 8 == 0, the leading dimension
+    of W^T): W is transposed once (2 x |W| bytes, ~0.2 % of what the GEMM streams) for the NT form, ~30 % faster than reading W
+    through ds_read_b64_tr_b16; otherwise the NN form.  (No K % 8 term: kai0_gemm_bf16 refuses such a leading dimension before
+    either form could run.)  What a site decides for itself:
+      ldy, ldx     row strides of dy / dx where their rows are padded (default N / K)
+      split        the NN form takes pick_split_k (True) or stays unsplit; the NT form is never split
+      nt           True: through W^T at every row count;  wt: W^T where the caller already holds it (implies nt)
+      epilogue     act, aux1, aux2, pre_out, ct, ldct, ct2, ldct2: passed on to `gemm`
+      plan         launch nothing, return gemm_plan's answer for the launch these arguments would make (it needs `wt`: a query
+                   transposes nothing) — one keyword set for both, so the query and the launch cannot differ."""
+    M = dy.shape[0]
+    N, K = w.shape
+    if dx is None:
+        dx = torch.empty((M, K), dtype=BF16, device=dy.device)
+    kw = dict(M=M, N=K, K=N, a_kc=True, lda=ldy or N, ldc=ldx or K, accumulate=accumulate, **epilogue)
+    if wt is not None or nt or (nt is None and M >= NT_MIN_ROWS and N % 8 == 0):
+        b = transpose(w) if wt is None else wt  # [K, N]
+        kw.update(b_kc=True, ldb=N)
+    else:  # B stored [N][K] = [contraction][columns]
+        b = w
+        kw.update(b_kc=False, ldb=K, split_k=pick_split_k(M, K, N) if split else 1)
+    if plan:
+        return gemm_plan(dy, b, dx, **kw)
+    gemm(dy, b, dx, **kw)
+    return dx
+
+
+def wgrad(dy, x, w=None, *, into=None, ldy=None, ldx=None, kc=False, nt_out=True):
+    """dW [N, K] = dy [M, N]^T @ x [M, K] (TN: both operands stored [contraction][columns]) into `w`'s gradient destination
+    (_grad_dst: the trainer's flat gradient buffer where it publishes one, so no copy follows) or `into`, split by
+    pick_split_k_wgrad.  Returns the raw gradient: the caller hands it to _grad_ret when the trainer is to hear of it.
+      ldy, ldx     row strides of dy / x where their rows are padded (default N / K)
+      kc           dy and x are handed in transposed, [N][M] and [K][M]: both operands K-contiguous, the 64-deep NT loop
+      nt_out       store past the caches (kai0hip.h c_nontemporal)"""
+    dw = _grad_dst(w, BF16) if into is None else into
+    N, K = dw.shape
+    M = dy.shape[1] if kc else dy.shape[0]
+    gemm(dy, x, dw, M=N, N=K, K=M, a_kc=kc, b_kc=kc, lda=M if kc else ldy or N, ldb=M if kc else ldx or K, ldc=K,
+         split_k=pick_split_k_wgrad(N, K, M), nt_out=nt_out)  # fmt: skip
+    return dw
+
+
 # ------------------------------------------------------------------------------------------ second HIP stream
 # model.forward_joint runs the action expert's chain on a second stream (and autograd its backward): (main, side) per device.
 _DUAL: dict = {}
@@ -605,22 +652,9 @@ class LinearFn(torch.autograd.Function):
             _lib.call("kai0_gelu_bwd", dout.data_ptr(), pre.data_ptr(), dy.data_ptr(), dout.numel(), _stream())
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = torch.empty((M, K), dtype=BF16, device=x.device)
-            if M >= 4096 and N % 8 == 0 and K % 8 == 0:
-                # many rows: transpose W once (2 x |W| bytes, ~0.2 % of what the GEMM streams) and run dgrad in the
-                # K-contiguous (NT) form, which is ~30 % faster than reading W through ds_read_b64_tr_b16
-                wt = transpose(w)
-                gemm(dy, wt, dx, M=M, N=K, K=N, a_kc=True, b_kc=True, lda=N, ldb=N, ldc=K)
-                del wt
-            else:
-                # dx[M,K] = dy[M,N] @ w[N,K]  (A K-contig over N; B stored [N][K] = [contraction][cols])
-                gemm(dy, w, dx, M=M, N=K, K=N, a_kc=True, b_kc=False, lda=N, ldb=K, ldc=K, split_k=pick_split_k(M, K, N))
+            dx = dgrad(dy, w)
         if ctx.needs_input_grad[1]:
-            # the sharded trainer publishes each parameter's slice of its flat gradient buffer: write dW there
-            # directly, so no gradient copy is needed afterwards (sharded.py)
-            dw = _grad_dst(w, BF16)
-            # dw[N,K] = dy[M,N]^T @ x[M,K]  (both stored [contraction][cols])
-            gemm(dy, x, dw, M=N, N=K, K=M, a_kc=False, b_kc=False, lda=N, ldb=K, ldc=K, split_k=pick_split_k_wgrad(N, K, M), nt_out=True)
+            dw = wgrad(dy, x, w)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             (db,) = _bias_grads(dy, M, N, N, [(ctx.bias, 0, N)])
         return dx, _grad_ret(w, dw), db, dres, None
@@ -721,15 +755,8 @@ class LinearMultiFn(torch.autograd.Function):
         dy = _as_fused(douts, widths)
         if dy is None:
             dy = torch.cat([d if d.dtype == BF16 else d.to(BF16) for d in douts], dim=1)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty((M, K), dtype=BF16, device=dev)
-            if M >= 4096:
-                wt = transpose(wcat)  # [K, Nt]: K-contiguous operand for the fast NT schedule
-                gemm(dy, wt, dx, M=M, N=K, K=Nt, lda=Nt, ldb=Nt, ldc=K)
-                del wt
-            else:
-                gemm(dy, wcat, dx, M=M, N=K, K=Nt, a_kc=True, b_kc=False, lda=Nt, ldb=K, ldc=K)
+        # (the NN form unsplit, unlike LinearFn's on the same shape: kept as found, not measured)
+        dx = dgrad(dy, wcat, split=False) if ctx.needs_input_grad[0] else None
         dws, dbs = [None] * n, [None] * n
         if any(ctx.needs_input_grad[2 + i] for i in range(n)):
             dsts = [_grad_dst(w, BF16) for w in ws]
@@ -737,7 +764,8 @@ class LinearMultiFn(torch.autograd.Function):
             tmp = dwcat is None
             if tmp:
                 dwcat = torch.empty((Nt, K), dtype=BF16, device=dev)
-            gemm(dy, x, dwcat, M=Nt, N=K, K=M, a_kc=False, b_kc=False, lda=Nt, ldb=K, ldc=K, split_k=pick_split_k_wgrad(Nt, K, M))
+            # (no non-temporal store, even into the trainer's flat buffer, unlike every other wgrad: kept as found, not measured)
+            wgrad(dy, x, into=dwcat, nt_out=False)
             r = 0
             for i, (w, dst) in enumerate(zip(ws, dsts)):
                 if tmp:
@@ -763,17 +791,10 @@ class LinearMultiFn(torch.autograd.Function):
             dy = dy.contiguous()
             N = w.shape[0]
             if dx is not None:
-                if M >= 4096 and N % 8 == 0:
-                    wt = transpose(w)
-                    gemm(dy, wt, dx, M=M, N=K, K=N, lda=N, ldb=N, ldc=K, accumulate=not first)
-                    del wt
-                else:
-                    gemm(dy, w, dx, M=M, N=K, K=N, a_kc=True, b_kc=False, lda=N, ldb=K, ldc=K, accumulate=not first)
+                dgrad(dy, w, dx, accumulate=not first, split=False)  # (unsplit, the first one too: kept as found, not measured)
                 first = False
             if ctx.needs_input_grad[2 + i]:
-                dw = _grad_dst(w, BF16)
-                gemm(dy, x, dw, M=N, N=K, K=M, a_kc=False, b_kc=False, lda=N, ldb=K, ldc=K, split_k=pick_split_k_wgrad(N, K, M), nt_out=True)
-                dws[i] = _grad_ret(w, dw)
+                dws[i] = _grad_ret(w, wgrad(dy, x, w))
             if b is not None and ctx.needs_input_grad[2 + n + i]:
                 (dbs[i],) = _bias_grads(dy, M, N, N, [(b, 0, N)])
         if dx is not None and first:
@@ -1014,7 +1035,6 @@ def set_geglu_pair(on: bool) -> bool:
 # whose producer launch does not take that tile (kai0_gemm_plan is asked: no stand-alone transpose of a [rows][F] operand is ever
 # made).  Same bits as TN wherever both run one K split.  set_mlp_wgrad_nt(False): the TN path everywhere (tests).
 _MLP_WGRAD_NT = True
-_MLP_WGRAD_NT_MIN_ROWS = 4096
 
 
 def set_mlp_wgrad_nt(on: bool) -> bool:
@@ -1024,7 +1044,7 @@ def set_mlp_wgrad_nt(on: bool) -> bool:
 
 
 def _mlp_wgrad_nt(rows: int) -> bool:
-    return _MLP_WGRAD_NT and rows >= _MLP_WGRAD_NT_MIN_ROWS and rows % 8 == 0
+    return _MLP_WGRAD_NT and rows >= NT_MIN_ROWS and rows % 8 == 0
 
 
 class GegluMlpFn(torch.autograd.Function):
@@ -1069,52 +1089,37 @@ class GegluMlpFn(torch.autograd.Function):
         M, D = x.shape
         F = wg.shape[0]
         dev = x.device
-
-        def wgrad(dy, inp, w, n, k):
-            dw = _grad_dst(w, BF16)
-            gemm(dy, inp, dw, M=n, N=k, K=M, a_kc=False, b_kc=False, lda=n, ldb=k, ldc=k, split_k=pick_split_k_wgrad(n, k, M), nt_out=True)
-            return dw
-
-        def wgrad_nt(dyT, inpT, dw, n, k):  # dW [n][k] = dyT [n][rows] @ inpT [k][rows]^T: both operands K-contiguous
-            return gemm(dyT, inpT, dw, M=n, N=k, K=M, lda=M, ldb=M, ldc=k, split_k=pick_split_k_wgrad(n, k, M), nt_out=True)
-
         dwd = None
-        if ctx.needs_input_grad[3]:
-            dwd = wgrad_nt(transpose(dout), h, _grad_dst(wd, BF16), D, F) if ctx.h_transposed else wgrad(dout, h, wd, D, F)
+        if ctx.needs_input_grad[3]:  # (h is hT [F][rows] where the forward's epilogue stored it)
+            dwd = wgrad(transpose(dout), h, wd, kc=True) if ctx.h_transposed else wgrad(dout, h, wd)
         # dh = dout @ wd (through wd^T, K-contiguous) with the GeGLU backward in the epilogue: C = dg, pre_out = du
         dg = torch.empty((M, F), dtype=BF16, device=dev)
         du = torch.empty((M, F), dtype=BF16, device=dev)
-        wdt = transpose(wd)  # [F, D]
-        kw = dict(M=M, N=F, K=D, lda=D, ldb=D, ldc=F, act=3, pre_out=du, aux1=g, aux2=u)
+        act3 = dict(wt=transpose(wd), act=3, pre_out=du, aux1=g, aux2=u)  # wd^T [F, D]; the plan query and the launch take this one set
         need_g, need_u = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         dgduT = None
-        if ctx.nt_gate_up and need_g and need_u and gemm_plan(dout, wdt, dg, **kw)["tile"] == 256:
+        if ctx.nt_gate_up and need_g and need_u and dgrad(dout, wd, dg, plan=True, **act3)["tile"] == 256:
             # dgT | duT [2F][rows], back to back, for the NT gate / up wgrads, stored by the act-3 epilogue
             dgduT = torch.empty((2 * F, M), dtype=BF16, device=dev)
-            kw.update(ct=dgduT[:F], ldct=M, ct2=dgduT[F:], ldct2=M)
-        gemm(dout, wdt, dg, **kw)
-        del wdt
+            act3.update(ct=dgduT[:F], ldct=M, ct2=dgduT[F:], ldct2=M)
+        dgrad(dout, wd, dg, **act3)
+        del act3
         if dgduT is not None:
             xT = transpose(x)  # [D][rows]
             dwg, dwu = _grad_dst(wg, BF16), _grad_dst(wu, BF16)
             both = _as_rows([dwg, dwu])
             if both is not None:  # the gradient destinations lie back to back: one M = 2F launch
-                wgrad_nt(dgduT, xT, both, 2 * F, D)
+                wgrad(dgduT, xT, into=both, kc=True)
             else:
-                wgrad_nt(dgduT[:F], xT, dwg, F, D)
-                wgrad_nt(dgduT[F:], xT, dwu, F, D)
+                wgrad(dgduT[:F], xT, into=dwg, kc=True)
+                wgrad(dgduT[F:], xT, into=dwu, kc=True)
             del xT, dgduT
         else:
-            dwg = wgrad(dg, x, wg, F, D) if need_g else None
-            dwu = wgrad(du, x, wu, F, D) if need_u else None
+            dwg = wgrad(dg, x, wg) if need_g else None
+            dwu = wgrad(du, x, wu) if need_u else None
         dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty((M, D), dtype=BF16, device=dev)
-            wgt = transpose(wg)  # [D, F]
-            gemm(dg, wgt, dx, M=M, N=D, K=F, lda=F, ldb=F, ldc=D, split_k=1)
-            wut = transpose(wu)
-            gemm(du, wut, dx, M=M, N=D, K=F, lda=F, ldb=F, ldc=D, accumulate=True, split_k=1)
-            del wgt, wut
+        if ctx.needs_input_grad[0]:  # through the transposed weights at every row count, the expert's 1600 too
+            dx = dgrad(du, wu, dgrad(dg, wg, nt=True), nt=True, accumulate=True)
         return dx, _grad_ret(wg, dwg), _grad_ret(wu, dwu), _grad_ret(wd, dwd), (dout if ctx.has_res else None)
 
 
@@ -1154,40 +1159,24 @@ class GeluMlpFn(torch.autograd.Function):
         F, Do = w1.shape[0], w2.shape[0]
         ldh = pre.shape[1]
         dev = x.device
-        big = M >= 4096
 
         def colsum(dy, N, ld, b):
             return _bias_grads(dy, M, N, ld, [(b, 0, N)])[0]
 
         dw2 = db2 = dw1 = db1 = dx = None
         if ctx.needs_input_grad[3]:
-            dw2 = _grad_dst(w2, BF16)
-            gemm(dout, h, dw2, M=Do, N=F, K=M, a_kc=False, b_kc=False, lda=Do, ldb=ldh, ldc=F, split_k=pick_split_k_wgrad(Do, F, M), nt_out=True)
-            dw2 = _grad_ret(w2, dw2)
+            dw2 = _grad_ret(w2, wgrad(dout, h, w2, ldx=ldh))
         if b2 is not None and ctx.needs_input_grad[4]:
             db2 = colsum(dout, Do, Do, b2)
-        # dpre = (dout @ w2) * gelu'(pre): the GELU backward runs in the dgrad GEMM's epilogue (kai0hip.h act 5)
-        dpre = torch.empty((M, ldh), dtype=BF16, device=dev)
-        if big:
-            w2t = transpose(w2)  # [F, Do]
-            gemm(dout, w2t, dpre, M=M, N=F, K=Do, lda=Do, ldb=Do, ldc=ldh, act=5, aux1=pre)  # dh never reaches HBM
-            del w2t
-        else:
-            gemm(dout, w2, dpre, M=M, N=F, K=Do, a_kc=True, b_kc=False, lda=Do, ldb=F, ldc=ldh, act=5, aux1=pre)
+        # dpre = (dout @ w2) * gelu'(pre): the GELU backward runs in the dgrad GEMM's epilogue (kai0hip.h act 5), dh never reaches HBM
+        # (the NN form unsplit, unlike dx's below: kept as found, not measured)
+        dpre = dgrad(dout, w2, torch.empty((M, ldh), dtype=BF16, device=dev), ldx=ldh, split=False, act=5, aux1=pre)
         if ctx.needs_input_grad[1]:
-            dw1 = _grad_dst(w1, BF16)
-            gemm(dpre, x, dw1, M=F, N=D, K=M, a_kc=False, b_kc=False, lda=ldh, ldb=D, ldc=D, split_k=pick_split_k_wgrad(F, D, M), nt_out=True)
-            dw1 = _grad_ret(w1, dw1)
+            dw1 = _grad_ret(w1, wgrad(dpre, x, w1, ldy=ldh))
         if b1 is not None and ctx.needs_input_grad[2]:
             db1 = colsum(dpre, F, ldh, b1)
         if ctx.needs_input_grad[0]:
-            dx = torch.empty((M, D), dtype=BF16, device=dev)
-            if big:
-                w1t = transpose(w1)  # [D, F]
-                gemm(dpre, w1t, dx, M=M, N=D, K=F, lda=ldh, ldb=F, ldc=D)
-                del w1t
-            else:
-                gemm(dpre, w1, dx, M=M, N=D, K=F, a_kc=True, b_kc=False, lda=ldh, ldb=D, ldc=D, split_k=pick_split_k(M, D, F))
+            dx = dgrad(dpre, w1, ldy=ldh)
         return dx, dw1, db1, dw2, db2, (dout if ctx.has_res else None)
 
 
