@@ -664,7 +664,10 @@ int kai0_sum_chunks(const void* src, int is_f32, int chunks, int64_t chunk_strid
 /* Fused AdamW on a flat shard: master/m/v f32, grad bf16 or f32, writes the bf16 (or f32) model copy.
  * clip_coef is read from device memory (coef[0]) so the step stays graph/stream ordered:
  *   g = grad * coef[0]; m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
- *   p = p - lr * (m/(1-b1^t) / (sqrt(v/(1-b2^t)) + eps) + wd * p)    (torch.optim.AdamW semantics) */
+ *   p = p - lr * (m/(1-b1^t) / (sqrt(v/(1-b2^t)) + eps) + wd * p)    (torch.optim.AdamW semantics)
+ * For this and the three forms below: every buffer aligned to its element size; buffers may start at any element (shard
+ * slices): 16-byte accesses are used when all of them reach their vector alignment at the same element (in the row forms: at
+ * element 0, with row_len a multiple of 4), scalar ones otherwise.  One kernel body serves all four, so they agree bit for bit. */
 int kai0_adamw(float* master, float* m, float* v, const void* grad, int grad_f32, void* model_param,
                int param_f32, int64_t n, float lr, float beta1, float beta2, float eps, float wd,
                float bias_c1, float bias_c2, const float* clip_coef, kai0_stream_t stream);
@@ -679,8 +682,7 @@ int kai0_adamw_rows(float* master, float* m, float* v, const void* grad, int gra
 /* kai0_adamw with the parameter EMA in the same pass (the JAX trainer's ema_decay, scripts/train.py:172-177): after the update
  * that gives the new master p,  ema = ema + (1 - ema_decay) * (p - ema)  in f32 (= d * ema + (1 - d) * p in the form for which
  * ema == p is a fixed point; no bias correction, no warm-up of the decay).  master, m, v and the model copy come out bit-identical
- * to kai0_adamw on the same inputs.  ema: f32 [n], non-null; 0 <= ema_decay < 1.  Buffers may start at any element (shard slices):
- * 16-byte accesses are used when all of them reach their vector alignment at the same element, scalar ones otherwise. */
+ * to kai0_adamw on the same inputs.  ema: f32 [n], non-null; 0 <= ema_decay < 1. */
 int kai0_adamw_ema(float* master, float* m, float* v, float* ema, const void* grad, int grad_f32, void* model_param,
                    int param_f32, int64_t n, float lr, float beta1, float beta2, float eps, float wd, float bias_c1,
                    float bias_c2, float ema_decay, const float* clip_coef, kai0_stream_t stream);
@@ -696,7 +698,7 @@ int kai0_adamw_rows_ema(float* master, float* m, float* v, float* ema, const voi
  * sumsq_out != NULL: additionally sumsq_out[0] += sum_i acc_new[i]^2, from per-block partials added in a fixed order by a
  * second launch (as kai0_sumsq: no atomics, reproducible bit for bit); scratch: 4096 floats, required iff sumsq_out.
  * first != 0 OVERWRITES: acc's previous bytes (uninitialised memory, NaN) must not reach the result.
- * Buffers may start at any element (shard slices), like kai0_adamw_ema: 16-byte accesses where acc and grad reach their
+ * Buffers may start at any element (shard slices), like kai0_adamw: 16-byte accesses where acc and grad reach their
  * vector alignment at the same element, scalar head / tail / fallback otherwise. */
 int kai0_grad_accum(float* acc, const void* grad, int grad_f32, int64_t n, int first,
                     float* sumsq_out, float* scratch, kai0_stream_t stream);

@@ -91,6 +91,35 @@ __global__ __launch_bounds__(256) void sum_chunks_kernel(const void* __restrict_
     }
 }
 
+// ---- one bf16-or-f32 stream as f32: the loads of the AdamW, grad_accum, mix and multi_dot bodies ------------------------------------
+template <bool F32>
+__device__ __forceinline__ float load_one(const void* p, int64_t i) {
+    return F32 ? reinterpret_cast<const float*>(p)[i] : bf2f(reinterpret_cast<const bf16_t*>(p)[i]);
+}
+
+// V elements at i, V = 4 or 8: 16-byte accesses (two of them for 8 f32 elements), 8-byte for 4 bf16 elements; the caller guarantees
+// the alignment
+template <bool F32, int V>
+__device__ __forceinline__ void load_vec(const void* p, int64_t i, float (&x)[V]) {
+    if constexpr (F32) {
+#pragma unroll
+        for (int q = 0; q < V / 4; ++q) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p) + i + 4 * q);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[4 * q + e] = v[e];
+        }
+    } else if constexpr (V == 8) {
+        const bf16x8 v = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16_t*>(p) + i);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = bf2f(v[e]);
+    } else {
+        const bf16x4 v = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16_t*>(p) + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = bf2f(v[e]);
+    }
+}
+
+// ---- AdamW, optionally with the parameter EMA in the same pass (kai0_adamw / _rows / _ema / _rows_ema) ---------------------------------
 // One element of torch.optim.AdamW on f32 state: returns the new master, updates the moments in place.  EVERY AdamW kernel of this
 // file goes through this one function, so the dense, the row-sparse and the EMA forms agree bit for bit.
 //   p *= 1 - lr*wd ; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
@@ -104,24 +133,86 @@ __device__ __forceinline__ float adamw_element(float g, float p, float& mi, floa
     return p - (lr * inv_bc1) * (mi / denom);
 }
 
-template <bool GF32, bool PF32>
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
-                                                    const void* __restrict__ grad, void* __restrict__ param, int64_t n,
-                                                    float lr, float b1, float b2, float eps, float wd, float bc1,
-                                                    float bc2, const float* __restrict__ coef) {
-    const float cc = coef ? coef[0] : 1.0f;
-    const float inv_bc1 = 1.0f / bc1;
-    const float inv_sqrt_bc2 = rsqrtf(bc2);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float g = GF32 ? reinterpret_cast<const float*>(grad)[i] : bf2f(reinterpret_cast<const bf16_t*>(grad)[i]);
-        float mi = m[i], vi = v[i];
-        const float p = adamw_element(g, master[i], mi, vi, cc, lr, b1, b2, eps, wd, inv_bc1, inv_sqrt_bc2);
-        master[i] = p;
-        m[i] = mi;
-        v[i] = vi;
-        if (PF32) reinterpret_cast<float*>(param)[i] = p;
-        else reinterpret_cast<bf16_t*>(param)[i] = f2bf(p);
+// ema <- ema + (1 - d) (p - ema) with p the master just computed (still in a register): d * ema + (1 - d) * p in the form for which
+// ema == p is a fixed point, which lets the row-sparse form keep skipping idle rows.
+__device__ __forceinline__ float ema_element(float e, float p, float omd) { return e + omd * (p - e); }
+
+// The argument block of every form; omd = 1 - ema_decay is unused without the EMA.
+struct AdamwEmaK {
+    float cc, lr, b1, b2, eps, wd, inv_bc1, inv_sqrt_bc2, omd;
+    // the host passes bc1 / bc2 in the inv_* slots; this is the one place where the device turns them into the factors
+    __device__ __forceinline__ void finish(const float* coef) {
+        cc = coef ? coef[0] : 1.0f;
+        inv_bc1 = 1.0f / inv_bc1;
+        inv_sqrt_bc2 = rsqrtf(inv_sqrt_bc2);
     }
+};
+
+// EMA = false never touches `ema` (the host passes a null pointer).  With it: five f32 streams and two 16-bit ones per element.
+template <bool GF32, bool PF32, bool EMA>
+__device__ __forceinline__ void adamw_one(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
+                                          float* __restrict__ ema, const void* __restrict__ grad, void* __restrict__ param, int64_t i,
+                                          const AdamwEmaK& k) {
+    float mi = m[i], vi = v[i];
+    const float p = adamw_element(load_one<GF32>(grad, i), master[i], mi, vi, k.cc, k.lr, k.b1, k.b2, k.eps, k.wd, k.inv_bc1,
+                                  k.inv_sqrt_bc2);
+    master[i] = p;
+    m[i] = mi;
+    v[i] = vi;
+    if constexpr (EMA) ema[i] = ema_element(ema[i], p, k.omd);
+    if constexpr (PF32) reinterpret_cast<float*>(param)[i] = p;
+    else reinterpret_cast<bf16_t*>(param)[i] = f2bf(p);
+}
+
+// elements [i, i + 4): the caller guarantees 16-byte alignment of the f32 streams at i (8-byte of a bf16 gradient / model copy)
+template <bool GF32, bool PF32, bool EMA>
+__device__ __forceinline__ void adamw_vec4(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
+                                           float* __restrict__ ema, const void* __restrict__ grad, void* __restrict__ param, int64_t i,
+                                           const AdamwEmaK& k) {
+    float g[4];
+    load_vec<GF32, 4>(grad, i, g);
+    f32x4 p = *reinterpret_cast<const f32x4*>(master + i);
+    f32x4 mi = *reinterpret_cast<const f32x4*>(m + i);
+    f32x4 vi = *reinterpret_cast<const f32x4*>(v + i);
+    f32x4 e;
+    if constexpr (EMA) e = *reinterpret_cast<const f32x4*>(ema + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float mj = mi[j], vj = vi[j];
+        p[j] = adamw_element(g[j], p[j], mj, vj, k.cc, k.lr, k.b1, k.b2, k.eps, k.wd, k.inv_bc1, k.inv_sqrt_bc2);
+        mi[j] = mj;
+        vi[j] = vj;
+        if constexpr (EMA) e[j] = ema_element(e[j], p[j], k.omd);
+    }
+    *reinterpret_cast<f32x4*>(master + i) = p;
+    *reinterpret_cast<f32x4*>(m + i) = mi;
+    *reinterpret_cast<f32x4*>(v + i) = vi;
+    if constexpr (EMA) *reinterpret_cast<f32x4*>(ema + i) = e;
+    if constexpr (PF32) {
+        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(param) + i) = p;
+    } else {
+        *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(param) + i) = bf16x4{f2bf(p[0]), f2bf(p[1]), f2bf(p[2]), f2bf(p[3])};
+    }
+}
+
+// Elements [0, head) and [head + 4 * n4, n) go one at a time, [head, head + 4 * n4) four at a time.  The host picks `head` (< 4) so
+// that every stream is aligned at element `head` — shard slices start at arbitrary element offsets, but all of them at the SAME one,
+// so one head serves all seven pointers — or, if no such head exists, head = n: everything scalar (stream_plan below).
+// Every block takes ONE contiguous run of vectors (256 of them — one per lane, no loop — up to 2^22 blocks, longer runs beyond): the
+// blocks resident at any moment then cover one contiguous window of each of the buffers.  Measured with the EMA on a 256 Mi-element
+// shard (bf16 gradient and model copy): 1.62 ms against 1.81 ms for a grid-stride scalar loop over 4096 blocks, whose co-resident
+// lanes touch every stream at 16 MiB intervals; non-temporal loads / stores and two vectors per lane changed nothing.
+template <bool GF32, bool PF32, bool EMA>
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
+                                                    float* __restrict__ ema, const void* __restrict__ grad, void* __restrict__ param,
+                                                    int64_t n, int64_t head, AdamwEmaK k, const float* __restrict__ coef) {
+    k.finish(coef);
+    const int64_t n4 = (n - head) >> 2;
+    const int64_t per = (n4 + gridDim.x - 1) / gridDim.x, lo = per * blockIdx.x, hi = lo + per < n4 ? lo + per : n4;
+    for (int64_t j = lo + threadIdx.x; j < hi; j += 256) adamw_vec4<GF32, PF32, EMA>(master, m, v, ema, grad, param, head + 4 * j, k);
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = tid; i < head; i += stride) adamw_one<GF32, PF32, EMA>(master, m, v, ema, grad, param, i, k);
+    for (int64_t i = head + 4 * n4 + tid; i < n; i += stride) adamw_one<GF32, PF32, EMA>(master, m, v, ema, grad, param, i, k);
 }
 
 // The same update for a [rows][row_len] parameter whose gradient is zero in most rows (the 257152 x 2048 embedding table: a step
@@ -130,14 +221,15 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ master, 
 // rows are skipped after reading only their gradient; `active[row]` (persistent, uint8) records that a row has ever seen a nonzero
 // gradient, i.e. that its moments may be nonzero.  Every element that IS updated goes through exactly adamw_kernel's arithmetic,
 // so the result is bit-identical to the dense pass — at 2 B instead of 28 B per element of an idle row.
-template <bool GF32, bool PF32>
+// With the EMA a skipped row stays skipped, EMA included, which is exact when ema == master on it (ema_element's fixed point) — the
+// host sets `active` for every row whose moments may be nonzero OR whose ema may differ from its master.
+template <bool GF32, bool PF32, bool EMA>
 __global__ __launch_bounds__(256) void adamw_rows_kernel(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
-                                                         const void* __restrict__ grad, void* __restrict__ param, int64_t n_rows,
-                                                         int row_len, unsigned char* __restrict__ active, float lr, float b1, float b2,
-                                                         float eps, float wd, float bc1, float bc2, const float* __restrict__ coef) {
-    const float cc = coef ? coef[0] : 1.0f;
-    const float inv_bc1 = 1.0f / bc1;
-    const float inv_sqrt_bc2 = rsqrtf(bc2);
+                                                         float* __restrict__ ema, const void* __restrict__ grad,
+                                                         void* __restrict__ param, int64_t n_rows, int row_len,
+                                                         unsigned char* __restrict__ active, int vec, AdamwEmaK k,
+                                                         const float* __restrict__ coef) {
+    k.finish(coef);
     for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
         const int64_t base = row * row_len;
         int nz = 0;
@@ -148,145 +240,15 @@ __global__ __launch_bounds__(256) void adamw_rows_kernel(float* __restrict__ mas
                 nz |= ((u.x | u.y | u.z | u.w) & 0x7fff7fffu) != 0u;
             }
         } else {
-            for (int c = threadIdx.x; c < row_len; c += 256) {
-                const float g = GF32 ? reinterpret_cast<const float*>(grad)[base + c] : bf2f(reinterpret_cast<const bf16_t*>(grad)[base + c]);
-                nz |= (g != 0.0f);
-            }
-        }
-        const int any = __syncthreads_or(nz);
-        if (!any && !active[row]) continue;  // (block-uniform)
-        if (any && threadIdx.x == 0) active[row] = 1;
-        for (int c = threadIdx.x; c < row_len; c += 256) {
-            const int64_t i = base + c;
-            const float g = GF32 ? reinterpret_cast<const float*>(grad)[i] : bf2f(reinterpret_cast<const bf16_t*>(grad)[i]);
-            float mi = m[i], vi = v[i];
-            const float p = adamw_element(g, master[i], mi, vi, cc, lr, b1, b2, eps, wd, inv_bc1, inv_sqrt_bc2);
-            master[i] = p;
-            m[i] = mi;
-            v[i] = vi;
-            if (PF32) reinterpret_cast<float*>(param)[i] = p;
-            else reinterpret_cast<bf16_t*>(param)[i] = f2bf(p);
-        }
-    }
-}
-
-// ---- AdamW + parameter EMA in the same pass (kai0_adamw_ema / kai0_adamw_rows_ema) -------------------------------------------------
-// ema <- ema + (1 - d) (p - ema) with p the master just computed (still in a register): d * ema + (1 - d) * p in the form for which
-// ema == p is a fixed point, which lets the row-sparse form keep skipping idle rows.  Five f32 streams and two 16-bit ones per
-// element: four elements per lane, 16-byte accesses on the f32 streams, 8-byte (bf16) / 16-byte (f32) ones on gradient and model copy.
-struct AdamwEmaK {
-    float cc, lr, b1, b2, eps, wd, inv_bc1, inv_sqrt_bc2, omd;  // omd = 1 - ema_decay
-    // the host passes bc1 / bc2 in the inv_* slots; the kernel turns them into the factors with adamw_kernel's own device arithmetic
-    __device__ __forceinline__ void finish(const float* coef) {
-        cc = coef ? coef[0] : 1.0f;
-        inv_bc1 = 1.0f / inv_bc1;
-        inv_sqrt_bc2 = rsqrtf(inv_sqrt_bc2);
-    }
-};
-
-__device__ __forceinline__ float ema_element(float e, float p, float omd) { return e + omd * (p - e); }
-
-template <bool GF32, bool PF32>
-__device__ __forceinline__ void adamw_ema_one(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
-                                              float* __restrict__ ema, const void* __restrict__ grad, void* __restrict__ param,
-                                              int64_t i, const AdamwEmaK& k) {
-    const float g = GF32 ? reinterpret_cast<const float*>(grad)[i] : bf2f(reinterpret_cast<const bf16_t*>(grad)[i]);
-    float mi = m[i], vi = v[i];
-    const float p = adamw_element(g, master[i], mi, vi, k.cc, k.lr, k.b1, k.b2, k.eps, k.wd, k.inv_bc1, k.inv_sqrt_bc2);
-    master[i] = p;
-    m[i] = mi;
-    v[i] = vi;
-    ema[i] = ema_element(ema[i], p, k.omd);
-    if (PF32) reinterpret_cast<float*>(param)[i] = p;
-    else reinterpret_cast<bf16_t*>(param)[i] = f2bf(p);
-}
-
-// elements [i, i + 4): the caller guarantees 16-byte alignment of the f32 streams at i (8-byte of a bf16 gradient / model copy)
-template <bool GF32, bool PF32>
-__device__ __forceinline__ void adamw_ema_vec4(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
-                                               float* __restrict__ ema, const void* __restrict__ grad, void* __restrict__ param,
-                                               int64_t i, const AdamwEmaK& k) {
-    f32x4 g;
-    if constexpr (GF32) {
-        g = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(grad) + i);
-    } else {
-        const bf16x4 gb = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16_t*>(grad) + i);
-        g = f32x4{bf2f(gb[0]), bf2f(gb[1]), bf2f(gb[2]), bf2f(gb[3])};
-    }
-    f32x4 p = *reinterpret_cast<const f32x4*>(master + i);
-    f32x4 mi = *reinterpret_cast<const f32x4*>(m + i);
-    f32x4 vi = *reinterpret_cast<const f32x4*>(v + i);
-    f32x4 e = *reinterpret_cast<const f32x4*>(ema + i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float mj = mi[j], vj = vi[j];
-        p[j] = adamw_element(g[j], p[j], mj, vj, k.cc, k.lr, k.b1, k.b2, k.eps, k.wd, k.inv_bc1, k.inv_sqrt_bc2);
-        mi[j] = mj;
-        vi[j] = vj;
-        e[j] = ema_element(e[j], p[j], k.omd);
-    }
-    *reinterpret_cast<f32x4*>(master + i) = p;
-    *reinterpret_cast<f32x4*>(m + i) = mi;
-    *reinterpret_cast<f32x4*>(v + i) = vi;
-    *reinterpret_cast<f32x4*>(ema + i) = e;
-    if constexpr (PF32) {
-        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(param) + i) = p;
-    } else {
-        *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(param) + i) = bf16x4{f2bf(p[0]), f2bf(p[1]), f2bf(p[2]), f2bf(p[3])};
-    }
-}
-
-// Elements [0, head) and [head + 4 * n4, n) go one at a time, [head, head + 4 * n4) four at a time.  The host picks `head` (< 4) so
-// that every stream is aligned at element `head` — shard slices start at arbitrary element offsets, but all of them at the SAME one,
-// so one head serves all seven pointers — or, if no such head exists, head = n: everything scalar.
-// Every block takes ONE contiguous run of vectors (256 of them — one per lane, no loop — up to 2^22 blocks, longer runs beyond): the
-// blocks resident at any moment then cover one contiguous window of each of the six buffers.  Measured on a 256 Mi-element shard
-// (bf16 gradient and model copy): 1.62 ms against 1.81 ms for the grid-stride loop over 4096 blocks that adamw_kernel uses, whose
-// co-resident lanes touch every stream at 16 MiB intervals; non-temporal loads / stores and two vectors per lane changed nothing.
-template <bool GF32, bool PF32>
-__global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
-                                                        float* __restrict__ ema, const void* __restrict__ grad,
-                                                        void* __restrict__ param, int64_t n, int64_t head, AdamwEmaK k,
-                                                        const float* __restrict__ coef) {
-    k.finish(coef);
-    const int64_t n4 = (n - head) >> 2;
-    const int64_t per = (n4 + gridDim.x - 1) / gridDim.x, lo = per * blockIdx.x, hi = lo + per < n4 ? lo + per : n4;
-    for (int64_t j = lo + threadIdx.x; j < hi; j += 256) adamw_ema_vec4<GF32, PF32>(master, m, v, ema, grad, param, head + 4 * j, k);
-    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = tid; i < head; i += stride) adamw_ema_one<GF32, PF32>(master, m, v, ema, grad, param, i, k);
-    for (int64_t i = head + 4 * n4 + tid; i < n; i += stride) adamw_ema_one<GF32, PF32>(master, m, v, ema, grad, param, i, k);
-}
-
-// adamw_rows_kernel with the EMA: a skipped row stays skipped, EMA included, which is exact when ema == master on it (the fixed
-// point above) — the host sets `active` for every row whose moments may be nonzero OR whose ema may differ from its master.
-template <bool GF32, bool PF32>
-__global__ __launch_bounds__(256) void adamw_rows_ema_kernel(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
-                                                             float* __restrict__ ema, const void* __restrict__ grad,
-                                                             void* __restrict__ param, int64_t n_rows, int row_len,
-                                                             unsigned char* __restrict__ active, int vec, AdamwEmaK k,
-                                                             const float* __restrict__ coef) {
-    k.finish(coef);
-    for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
-        const int64_t base = row * row_len;
-        int nz = 0;
-        if (!GF32 && (row_len & 7) == 0 && ((uintptr_t)grad & 15) == 0) {
-            for (int c = threadIdx.x * 8; c < row_len; c += 256 * 8) {
-                const uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(grad) + base + c);
-                nz |= ((u.x | u.y | u.z | u.w) & 0x7fff7fffu) != 0u;
-            }
-        } else {
-            for (int c = threadIdx.x; c < row_len; c += 256) {
-                const float g = GF32 ? reinterpret_cast<const float*>(grad)[base + c] : bf2f(reinterpret_cast<const bf16_t*>(grad)[base + c]);
-                nz |= (g != 0.0f);
-            }
+            for (int c = threadIdx.x; c < row_len; c += 256) nz |= (load_one<GF32>(grad, base + c) != 0.0f);
         }
         const int any = __syncthreads_or(nz);
         if (!any && !active[row]) continue;  // (block-uniform)
         if (any && threadIdx.x == 0) active[row] = 1;
         if (vec) {  // row_len % 4 == 0 and every stream aligned at element 0 (host-checked): every row starts aligned
-            for (int c = threadIdx.x * 4; c < row_len; c += 256 * 4) adamw_ema_vec4<GF32, PF32>(master, m, v, ema, grad, param, base + c, k);
+            for (int c = threadIdx.x * 4; c < row_len; c += 256 * 4) adamw_vec4<GF32, PF32, EMA>(master, m, v, ema, grad, param, base + c, k);
         } else {
-            for (int c = threadIdx.x; c < row_len; c += 256) adamw_ema_one<GF32, PF32>(master, m, v, ema, grad, param, base + c, k);
+            for (int c = threadIdx.x; c < row_len; c += 256) adamw_one<GF32, PF32, EMA>(master, m, v, ema, grad, param, base + c, k);
         }
     }
 }
@@ -295,7 +257,7 @@ __global__ __launch_bounds__(256) void adamw_rows_ema_kernel(float* __restrict__
 // acc = (FIRST ? 0 : acc) + grad, one f32 add per element; FIRST never reads acc (it may hold NaN / uninitialised memory).
 template <bool GF32, bool FIRST>
 __device__ __forceinline__ float grad_accum_one(float* __restrict__ acc, const void* __restrict__ grad, int64_t i) {
-    const float g = GF32 ? reinterpret_cast<const float*>(grad)[i] : bf2f(reinterpret_cast<const bf16_t*>(grad)[i]);
+    const float g = load_one<GF32>(grad, i);
     const float a = FIRST ? g : acc[i] + g;
     acc[i] = a;
     return a * a;
@@ -304,23 +266,18 @@ __device__ __forceinline__ float grad_accum_one(float* __restrict__ acc, const v
 // elements [i, i + 4): acc 16-byte aligned at i, a bf16 gradient 8-byte aligned (host-checked).  Returns the sum of the four squares.
 template <bool GF32, bool FIRST>
 __device__ __forceinline__ float grad_accum_vec4(float* __restrict__ acc, const void* __restrict__ grad, int64_t i) {
-    f32x4 g;
-    if constexpr (GF32) {
-        g = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(grad) + i);
-    } else {
-        const bf16x4 gb = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16_t*>(grad) + i);
-        g = f32x4{bf2f(gb[0]), bf2f(gb[1]), bf2f(gb[2]), bf2f(gb[3])};
-    }
+    float g[4];
+    load_vec<GF32, 4>(grad, i, g);
     if constexpr (!FIRST) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(acc + i);
 #pragma unroll
         for (int j = 0; j < 4; ++j) g[j] = a[j] + g[j];
     }
-    *reinterpret_cast<f32x4*>(acc + i) = g;
+    *reinterpret_cast<f32x4*>(acc + i) = f32x4{g[0], g[1], g[2], g[3]};
     return ((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]) + g[3] * g[3];
 }
 
-// adamw_ema_kernel's layout (its comment has the measurement): scalar head, [head, head + 4 * n4) four at a time with every block on ONE
+// adamw_kernel's layout (its comment has the measurement): scalar head, [head, head + 4 * n4) four at a time with every block on ONE
 // contiguous run of vectors — one per lane up to 2^22 blocks without SUMSQ; with SUMSQ the grid is capped at the 4096 partials the
 // scratch buffer holds, so a block's run is longer and its lanes walk it 256 vectors at a time — scalar tail.  SUMSQ: partial[block] =
 // the block's sum of the squares of the NEW accumulator; sumsq_finish_kernel adds the partials in a fixed order.
@@ -349,37 +306,10 @@ struct MixK {
     float w[8];
 };
 
-template <bool F32>
-__device__ __forceinline__ float load_one(const void* p, int64_t i) {
-    return F32 ? reinterpret_cast<const float*>(p)[i] : bf2f(reinterpret_cast<const bf16_t*>(p)[i]);
-}
-
-// V elements at i, V = 4 or 8: 16-byte accesses (two of them for 8 f32 elements), 8-byte for 4 bf16 elements; the caller guarantees
-// the alignment
-template <bool F32, int V>
-__device__ __forceinline__ void load_vec(const void* p, int64_t i, float (&x)[V]) {
-    if constexpr (F32) {
-#pragma unroll
-        for (int q = 0; q < V / 4; ++q) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p) + i + 4 * q);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x[4 * q + e] = v[e];
-        }
-    } else if constexpr (V == 8) {
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16_t*>(p) + i);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = bf2f(v[e]);
-    } else {
-        const bf16x4 v = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16_t*>(p) + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) x[e] = bf2f(v[e]);
-    }
-}
-
 // dst = w0 x0 + w1 x1 + ... in source order, every product and every sum rounded to f32 on its own (-ffp-contract=off), one rounding
 // to dst's dtype (model_arithmetic/common.py:11-19, arithmetic_torch.py:188-195: the reference's per-tensor sum of w_i * p_i).
 // Every lane reads all its sources' elements before it writes the same elements of dst, so dst may be one of the sources (no
-// __restrict__ here); dst is never read.  Layout: adamw_ema_kernel's — scalar head, one contiguous run of V-element vectors per
+// __restrict__ here); dst is never read.  Layout: adamw_kernel's — scalar head, one contiguous run of V-element vectors per
 // block (V = 4 when everything is f32, else 8), scalar tail.
 template <bool SF32, bool DF32, int N>
 __global__ __launch_bounds__(256) void mix_kernel(MixK a, void* dst, int64_t n, int64_t head) {
@@ -497,6 +427,33 @@ inline int opt_grid(int64_t n) {
     return (int)b;
 }
 
+// ---- the launch shape of the "scalar head, one contiguous run of V-element vectors per block, scalar tail" kernels --------------------
+struct Stream {
+    const void* p;
+    int esz;  // bytes per element: 4 (f32) or 2 (bf16); p is a multiple of it (checked by the callers)
+};
+struct StreamPlan {
+    int64_t head, blocks;
+};
+
+// V (4 or 8) elements of a stream are one access of min(16, V * esz) bytes and need that alignment.  head = the elements before the
+// boundary of s[0], the anchor; every other stream must sit on its own boundary at the same element — shard slices all start at the
+// same element offset, so they do — otherwise head = n: scalar accesses throughout.  blocks = one vector per lane, at most `cap`
+// (beyond it a block's run is longer), and no fewer than the grid-strided scalar elements want (all n of them without a common head).
+inline StreamPlan stream_plan(int64_t n, int V, int64_t cap, const Stream* s, int n_streams) {
+    const auto boundary = [V](const Stream& t) { return (uintptr_t)(V * t.esz < 16 ? V * t.esz : 16); };
+    const uintptr_t b0 = boundary(s[0]);
+    int64_t head = (int64_t)((b0 - (uintptr_t)s[0].p % b0) % b0) / s[0].esz;
+    if (head > n) head = n;
+    for (int i = 1; i < n_streams; ++i)
+        if (((uintptr_t)s[i].p + (uintptr_t)(head * s[i].esz)) % boundary(s[i]) != 0) head = n;
+    const int64_t nv = (n - head) / V, rest = n - V * nv;
+    int64_t blocks = (nv + 255) / 256;
+    if (blocks > cap) blocks = cap;
+    if (blocks < opt_grid(rest)) blocks = opt_grid(rest);
+    return {head, blocks};
+}
+
 }  // namespace
 
 KAI0_API int kai0_sumsq(const void* g, int g_f32, int64_t n, float* out, float* scratch, kai0_stream_t stream) {
@@ -529,83 +486,122 @@ KAI0_API int kai0_clip_coef(const float* sumsq, float max_norm, float* coef, flo
     return kai0_check_launch("kai0_clip_coef");
 }
 
+namespace {
+
+// What the four AdamW entry points share.  `who`: the entry point, for the messages; `ema` null = no EMA (ema_decay is then unused).
+struct AdamwArgs {
+    const char* who;
+    float *master, *m, *v, *ema;
+    const void* grad;
+    int grad_f32;
+    void* param;
+    int param_f32;
+    float lr, beta1, beta2, eps, wd, bias_c1, bias_c2, ema_decay;
+    const float* clip_coef;
+    hipStream_t stream;
+
+    AdamwEmaK k() const { return AdamwEmaK{1.0f, lr, beta1, beta2, eps, wd, bias_c1, bias_c2, 1.0f - ema_decay}; }
+    // head and blocks of `n` elements from the alignment of the five or six streams; the anchor is the master
+    StreamPlan plan(int64_t n) const {
+        const Stream s[6] = {{master, 4}, {m, 4}, {v, 4}, {grad, grad_f32 ? 4 : 2}, {param, param_f32 ? 4 : 2}, {ema, 4}};
+        return stream_plan(n, 4, (int64_t)1 << 22, s, ema ? 6 : 5);
+    }
+};
+
+// the instantiation LAUNCH(G, P, E) for a.grad_f32, a.param_f32 and whether there is an EMA
+#define ADAMW_LAUNCH_GP(E)                                     \
+    do {                                                       \
+        if (a.grad_f32 && a.param_f32) LAUNCH(true, true, E);  \
+        else if (a.grad_f32) LAUNCH(true, false, E);           \
+        else if (a.param_f32) LAUNCH(false, true, E);          \
+        else LAUNCH(false, false, E);                          \
+    } while (0)
+#define ADAMW_LAUNCH()                         \
+    do {                                       \
+        if (a.ema) ADAMW_LAUNCH_GP(true);      \
+        else ADAMW_LAUNCH_GP(false);           \
+    } while (0)
+
+int adamw_check(const AdamwArgs& a) {
+    KAI0_REQUIRE(a.master && a.m && a.v && a.grad && a.param, "%s: null buffer", a.who);
+    const int gsz = a.grad_f32 ? 4 : 2, psz = a.param_f32 ? 4 : 2;
+    KAI0_REQUIRE(((uintptr_t)a.master % 4) == 0 && ((uintptr_t)a.m % 4) == 0 && ((uintptr_t)a.v % 4) == 0 && ((uintptr_t)a.ema % 4) == 0 &&
+                     ((uintptr_t)a.grad % gsz) == 0 && ((uintptr_t)a.param % psz) == 0,
+                 "%s: a buffer is not aligned to its element size", a.who);
+    return 0;
+}
+
+int adamw_dense(const AdamwArgs& a, int64_t n) {
+    if (n <= 0) return 0;
+    if (adamw_check(a)) return -1;
+    const StreamPlan pl = a.plan(n);
+    dim3 grid((unsigned)pl.blocks), block(256);
+#define LAUNCH(G, P, E)                                                                                                              \
+    hipLaunchKernelGGL((adamw_kernel<G, P, E>), grid, block, 0, a.stream, a.master, a.m, a.v, a.ema, a.grad, a.param, n, pl.head, a.k(), \
+                       a.clip_coef)
+    ADAMW_LAUNCH();
+#undef LAUNCH
+    return kai0_check_launch(a.who);
+}
+
+int adamw_rows(const AdamwArgs& a, int64_t n_rows, int row_len, unsigned char* row_active) {
+    if (n_rows <= 0) return 0;
+    KAI0_REQUIRE(row_active && row_len > 0, "%s: null buffer", a.who);
+    if (adamw_check(a)) return -1;
+    KAI0_REQUIRE(1.0f - a.lr * a.wd == 1.0f, "%s: lr * wd = %g does not round away (1 - lr*wd must be 1.0f): idle rows are not fixed points, use %s",
+                 a.who, (double)a.lr * (double)a.wd, a.ema ? "kai0_adamw_ema" : "kai0_adamw");
+    // four elements at a time if every row starts on every stream's boundary: rows a multiple of four long, no head
+    const int vec = (row_len % 4) == 0 && a.plan(n_rows * row_len).head == 0;
+    dim3 grid((unsigned)(n_rows < 16384 ? n_rows : 16384)), block(256);
+#define LAUNCH(G, P, E)                                                                                                                 \
+    hipLaunchKernelGGL((adamw_rows_kernel<G, P, E>), grid, block, 0, a.stream, a.master, a.m, a.v, a.ema, a.grad, a.param, n_rows, row_len, \
+                       row_active, vec, a.k(), a.clip_coef)
+    ADAMW_LAUNCH();
+#undef LAUNCH
+    return kai0_check_launch(a.who);
+}
+#undef ADAMW_LAUNCH
+#undef ADAMW_LAUNCH_GP
+
+int ema_check(const char* who, const float* ema, float ema_decay) {
+    KAI0_REQUIRE(ema != nullptr, "%s: null ema buffer", who);
+    KAI0_REQUIRE(ema_decay >= 0.0f && ema_decay < 1.0f, "%s: ema_decay = %g outside [0, 1)", who, (double)ema_decay);
+    return 0;
+}
+
+}  // namespace
+
 KAI0_API int kai0_adamw(float* master, float* m, float* v, const void* grad, int grad_f32, void* model_param,
                         int param_f32, int64_t n, float lr, float beta1, float beta2, float eps, float wd, float bias_c1,
                         float bias_c2, const float* clip_coef, kai0_stream_t stream) {
-    if (n <= 0) return 0;
-    KAI0_REQUIRE(master && m && v && grad && model_param, "kai0_adamw: null buffer");
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid(opt_grid(n)), block(256);
-#define LAUNCH(G, P)                                                                                              \
-    hipLaunchKernelGGL((adamw_kernel<G, P>), grid, block, 0, s, master, m, v, grad, model_param, n, lr, beta1, beta2, \
-                       eps, wd, bias_c1, bias_c2, clip_coef)
-    if (grad_f32 && param_f32) LAUNCH(true, true);
-    else if (grad_f32) LAUNCH(true, false);
-    else if (param_f32) LAUNCH(false, true);
-    else LAUNCH(false, false);
-#undef LAUNCH
-    return kai0_check_launch("kai0_adamw");
+    return adamw_dense({"kai0_adamw", master, m, v, nullptr, grad, grad_f32, model_param, param_f32, lr, beta1, beta2, eps, wd, bias_c1,
+                        bias_c2, 0.0f, clip_coef, (hipStream_t)stream}, n);
 }
 
 KAI0_API int kai0_adamw_rows(float* master, float* m, float* v, const void* grad, int grad_f32, void* model_param, int param_f32,
                              int64_t n_rows, int row_len, unsigned char* row_active, float lr, float beta1, float beta2, float eps,
                              float wd, float bias_c1, float bias_c2, const float* clip_coef, kai0_stream_t stream) {
-    if (n_rows <= 0) return 0;
-    KAI0_REQUIRE(master && m && v && grad && model_param && row_active && row_len > 0, "kai0_adamw_rows: null buffer");
-    KAI0_REQUIRE(1.0f - lr * wd == 1.0f, "kai0_adamw_rows: lr * wd = %g does not round away (1 - lr*wd must be 1.0f): idle rows are not fixed points, use kai0_adamw",
-                 (double)lr * (double)wd);
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid((unsigned)(n_rows < 16384 ? n_rows : 16384)), block(256);
-#define LAUNCH(G, P)                                                                                                          \
-    hipLaunchKernelGGL((adamw_rows_kernel<G, P>), grid, block, 0, s, master, m, v, grad, model_param, n_rows, row_len, row_active, lr, \
-                       beta1, beta2, eps, wd, bias_c1, bias_c2, clip_coef)
-    if (grad_f32 && param_f32) LAUNCH(true, true);
-    else if (grad_f32) LAUNCH(true, false);
-    else if (param_f32) LAUNCH(false, true);
-    else LAUNCH(false, false);
-#undef LAUNCH
-    return kai0_check_launch("kai0_adamw_rows");
+    return adamw_rows({"kai0_adamw_rows", master, m, v, nullptr, grad, grad_f32, model_param, param_f32, lr, beta1, beta2, eps, wd, bias_c1,
+                       bias_c2, 0.0f, clip_coef, (hipStream_t)stream}, n_rows, row_len, row_active);
 }
-
-namespace {
-// whether `p`, advanced by `head` elements of `esz` bytes, sits on the boundary a 4-element access of that type needs
-inline bool aligned4(const void* p, int64_t head, int esz) {
-    return (((uintptr_t)p + (uintptr_t)(head * esz)) % (4 * (uintptr_t)esz)) == 0;
-}
-}  // namespace
 
 KAI0_API int kai0_adamw_ema(float* master, float* m, float* v, float* ema, const void* grad, int grad_f32, void* model_param,
                             int param_f32, int64_t n, float lr, float beta1, float beta2, float eps, float wd, float bias_c1,
                             float bias_c2, float ema_decay, const float* clip_coef, kai0_stream_t stream) {
     if (n <= 0) return 0;
-    KAI0_REQUIRE(master && m && v && grad && model_param, "kai0_adamw_ema: null buffer");
-    KAI0_REQUIRE(ema != nullptr, "kai0_adamw_ema: null ema buffer");
-    KAI0_REQUIRE(ema_decay >= 0.0f && ema_decay < 1.0f, "kai0_adamw_ema: ema_decay = %g outside [0, 1)", (double)ema_decay);
-    const int gsz = grad_f32 ? 4 : 2, psz = param_f32 ? 4 : 2;
-    KAI0_REQUIRE(((uintptr_t)master % 4) == 0 && ((uintptr_t)m % 4) == 0 && ((uintptr_t)v % 4) == 0 && ((uintptr_t)ema % 4) == 0 &&
-                     ((uintptr_t)grad % gsz) == 0 && ((uintptr_t)model_param % psz) == 0,
-                 "kai0_adamw_ema: a buffer is not aligned to its element size");
-    // elements before the first 16-byte boundary of `master`; the other streams must reach theirs at the same element
-    int64_t head = (int64_t)(((16 - ((uintptr_t)master & 15)) & 15) / 4);
-    if (head > n) head = n;
-    if (!(aligned4(m, head, 4) && aligned4(v, head, 4) && aligned4(ema, head, 4) && aligned4(grad, head, gsz) &&
-          aligned4(model_param, head, psz)))
-        head = n;  // no common head: scalar accesses throughout
-    const int64_t n4 = (n - head) >> 2, rest = n - 4 * n4;
-    hipStream_t s = (hipStream_t)stream;
-    int64_t blocks = (n4 + 255) / 256;  // one vector per lane (see adamw_ema_kernel)
-    if (blocks > ((int64_t)1 << 22)) blocks = (int64_t)1 << 22;
-    if (blocks < opt_grid(rest)) blocks = opt_grid(rest);  // the scalar elements are grid-strided: all of them if there is no common head
-    dim3 grid((unsigned)blocks), block(256);
-    const AdamwEmaK k{1.0f, lr, beta1, beta2, eps, wd, bias_c1, bias_c2, 1.0f - ema_decay};
-#define LAUNCH(G, P) \
-    hipLaunchKernelGGL((adamw_ema_kernel<G, P>), grid, block, 0, s, master, m, v, ema, grad, model_param, n, head, k, clip_coef)
-    if (grad_f32 && param_f32) LAUNCH(true, true);
-    else if (grad_f32) LAUNCH(true, false);
-    else if (param_f32) LAUNCH(false, true);
-    else LAUNCH(false, false);
-#undef LAUNCH
-    return kai0_check_launch("kai0_adamw_ema");
+    if (ema_check("kai0_adamw_ema", ema, ema_decay)) return -1;
+    return adamw_dense({"kai0_adamw_ema", master, m, v, ema, grad, grad_f32, model_param, param_f32, lr, beta1, beta2, eps, wd, bias_c1,
+                        bias_c2, ema_decay, clip_coef, (hipStream_t)stream}, n);
+}
+
+KAI0_API int kai0_adamw_rows_ema(float* master, float* m, float* v, float* ema, const void* grad, int grad_f32, void* model_param,
+                                 int param_f32, int64_t n_rows, int row_len, unsigned char* row_active, float lr, float beta1,
+                                 float beta2, float eps, float wd, float bias_c1, float bias_c2, float ema_decay,
+                                 const float* clip_coef, kai0_stream_t stream) {
+    if (n_rows <= 0) return 0;
+    if (ema_check("kai0_adamw_rows_ema", ema, ema_decay)) return -1;
+    return adamw_rows({"kai0_adamw_rows_ema", master, m, v, ema, grad, grad_f32, model_param, param_f32, lr, beta1, beta2, eps, wd,
+                       bias_c1, bias_c2, ema_decay, clip_coef, (hipStream_t)stream}, n_rows, row_len, row_active);
 }
 
 KAI0_API int kai0_grad_accum(float* acc, const void* grad, int grad_f32, int64_t n, int first, float* sumsq_out, float* scratch,
@@ -617,19 +613,12 @@ KAI0_API int kai0_grad_accum(float* acc, const void* grad, int grad_f32, int64_t
     KAI0_REQUIRE(((uintptr_t)acc % 4) == 0 && ((uintptr_t)grad % gsz) == 0 && (sumsq_out == nullptr || ((uintptr_t)sumsq_out % 4) == 0) &&
                      (scratch == nullptr || ((uintptr_t)scratch % 4) == 0),
                  "kai0_grad_accum: a buffer is not aligned to its element size");
-    // elements before the first 16-byte boundary of `acc`; the gradient must reach its vector alignment at the same element
-    int64_t head = (int64_t)(((16 - ((uintptr_t)acc & 15)) & 15) / 4);
-    if (head > n) head = n;
-    if (!aligned4(grad, head, gsz)) head = n;  // no common head: scalar accesses throughout
-    const int64_t n4 = (n - head) >> 2, rest = n - 4 * n4;
-    // one vector per lane (see adamw_ema_kernel); with the sum of squares one partial per block, and the scratch buffer holds 4096
-    const int64_t cap = sumsq_out ? 4096 : ((int64_t)1 << 22);
-    int64_t blocks = (n4 + 255) / 256;
-    if (blocks > cap) blocks = cap;
-    if (blocks < opt_grid(rest)) blocks = opt_grid(rest);  // the scalar elements are grid-strided: all of them if there is no common head
+    // anchor: acc.  With the sum of squares one partial per block, and the scratch buffer holds 4096
+    const Stream st[2] = {{acc, 4}, {grad, gsz}};
+    const StreamPlan pl = stream_plan(n, 4, sumsq_out ? 4096 : ((int64_t)1 << 22), st, 2);
     hipStream_t s = (hipStream_t)stream;
-    dim3 grid((unsigned)blocks), block(256);
-#define LAUNCH(G, F, S) hipLaunchKernelGGL((grad_accum_kernel<G, F, S>), grid, block, 0, s, acc, grad, n, head, scratch)
+    dim3 grid((unsigned)pl.blocks), block(256);
+#define LAUNCH(G, F, S) hipLaunchKernelGGL((grad_accum_kernel<G, F, S>), grid, block, 0, s, acc, grad, n, pl.head, scratch)
 #define LAUNCH_GF(G, F)             \
     do {                            \
         if (sumsq_out) LAUNCH(G, F, true); \
@@ -641,43 +630,9 @@ KAI0_API int kai0_grad_accum(float* acc, const void* grad, int grad_f32, int64_t
     else LAUNCH_GF(false, false);
 #undef LAUNCH_GF
 #undef LAUNCH
-    if (sumsq_out) hipLaunchKernelGGL(sumsq_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)scratch, (int)blocks, sumsq_out);
+    if (sumsq_out) hipLaunchKernelGGL(sumsq_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)scratch, (int)pl.blocks, sumsq_out);
     return kai0_check_launch("kai0_grad_accum");
 }
-
-KAI0_API int kai0_adamw_rows_ema(float* master, float* m, float* v, float* ema, const void* grad, int grad_f32, void* model_param,
-                                 int param_f32, int64_t n_rows, int row_len, unsigned char* row_active, float lr, float beta1,
-                                 float beta2, float eps, float wd, float bias_c1, float bias_c2, float ema_decay,
-                                 const float* clip_coef, kai0_stream_t stream) {
-    if (n_rows <= 0) return 0;
-    KAI0_REQUIRE(master && m && v && grad && model_param && row_active && row_len > 0, "kai0_adamw_rows_ema: null buffer");
-    KAI0_REQUIRE(ema != nullptr, "kai0_adamw_rows_ema: null ema buffer");
-    KAI0_REQUIRE(ema_decay >= 0.0f && ema_decay < 1.0f, "kai0_adamw_rows_ema: ema_decay = %g outside [0, 1)", (double)ema_decay);
-    KAI0_REQUIRE(1.0f - lr * wd == 1.0f, "kai0_adamw_rows_ema: lr * wd = %g does not round away (1 - lr*wd must be 1.0f): idle rows are not fixed points, use kai0_adamw_ema",
-                 (double)lr * (double)wd);
-    const int gsz = grad_f32 ? 4 : 2, psz = param_f32 ? 4 : 2;
-    KAI0_REQUIRE(((uintptr_t)master % 4) == 0 && ((uintptr_t)m % 4) == 0 && ((uintptr_t)v % 4) == 0 && ((uintptr_t)ema % 4) == 0 &&
-                     ((uintptr_t)grad % gsz) == 0 && ((uintptr_t)model_param % psz) == 0,
-                 "kai0_adamw_rows_ema: a buffer is not aligned to its element size");
-    const int vec = (row_len % 4) == 0 && aligned4(master, 0, 4) && aligned4(m, 0, 4) && aligned4(v, 0, 4) && aligned4(ema, 0, 4) &&
-                    aligned4(grad, 0, gsz) && aligned4(model_param, 0, psz);
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid((unsigned)(n_rows < 16384 ? n_rows : 16384)), block(256);
-    const AdamwEmaK k{1.0f, lr, beta1, beta2, eps, wd, bias_c1, bias_c2, 1.0f - ema_decay};
-#define LAUNCH(G, P)                                                                                                              \
-    hipLaunchKernelGGL((adamw_rows_ema_kernel<G, P>), grid, block, 0, s, master, m, v, ema, grad, model_param, n_rows, row_len, \
-                       row_active, vec, k, clip_coef)
-    if (grad_f32 && param_f32) LAUNCH(true, true);
-    else if (grad_f32) LAUNCH(true, false);
-    else if (param_f32) LAUNCH(false, true);
-    else LAUNCH(false, false);
-#undef LAUNCH
-    return kai0_check_launch("kai0_adamw_rows_ema");
-}
-
-namespace {
-inline bool aligned16(const void* p, int64_t head, int esz) { return (((uintptr_t)p + (uintptr_t)(head * esz)) & 15) == 0; }
-}  // namespace
 
 // N = n_src as a template parameter (1..8, checked by the callers)
 #define KAI0_FOR_NSRC(n_src, LAUNCH_N) \
@@ -700,25 +655,19 @@ KAI0_API int kai0_mix(const void* const* srcs, int src_f32, const float* weights
     const int ssz = src_f32 ? 4 : 2, dsz = dst_f32 ? 4 : 2;
     KAI0_REQUIRE(((uintptr_t)dst % dsz) == 0, "kai0_mix: a buffer is not aligned to its element size");
     MixK k{};
+    Stream st[9] = {{dst, dsz}};  // anchor: dst
     for (int i = 0; i < n_src; ++i) {
         KAI0_REQUIRE(srcs[i] != nullptr, "kai0_mix: null buffer (source %d)", i);
         KAI0_REQUIRE(((uintptr_t)srcs[i] % ssz) == 0, "kai0_mix: a buffer is not aligned to its element size (source %d)", i);
         KAI0_REQUIRE(__builtin_isfinite(weights[i]), "kai0_mix: weight %d is not finite", i);
         k.src[i] = srcs[i];
         k.w[i] = weights[i];
+        st[1 + i] = {srcs[i], ssz};
     }
-    // elements before dst's first 16-byte boundary; every source must reach a 16-byte boundary at the same element
-    const int V = (src_f32 && dst_f32) ? 4 : 8;
-    int64_t head = (int64_t)(((16 - ((uintptr_t)dst & 15)) & 15) / dsz);
-    if (head > n) head = n;
-    for (int i = 0; i < n_src; ++i)
-        if (!aligned16(srcs[i], head, ssz)) head = n;  // no common head: scalar accesses throughout
-    const int64_t nv = (n - head) / V, rest = n - V * nv;
-    int64_t blocks = (nv + 255) / 256;  // one vector per lane (see adamw_ema_kernel)
-    if (blocks > ((int64_t)1 << 22)) blocks = (int64_t)1 << 22;
-    if (blocks < opt_grid(rest)) blocks = opt_grid(rest);  // the scalar elements are grid-strided: all of them if there is no common head
+    const StreamPlan pl = stream_plan(n, (src_f32 && dst_f32) ? 4 : 8, (int64_t)1 << 22, st, 1 + n_src);
+    const int64_t head = pl.head;
     hipStream_t s = (hipStream_t)stream;
-    dim3 grid((unsigned)blocks), block(256);
+    dim3 grid((unsigned)pl.blocks), block(256);
 #define LAUNCH_SD(S, D, N) hipLaunchKernelGGL((mix_kernel<S, D, N>), grid, block, 0, s, k, dst, n, head)
 #define LAUNCH_N(N)                                        \
     do {                                                   \
@@ -743,22 +692,17 @@ KAI0_API int kai0_multi_dot(const void* g, int g_f32, const void* const* srcs, i
     KAI0_REQUIRE(((uintptr_t)g % gsz) == 0 && ((uintptr_t)out % 8) == 0 && ((uintptr_t)scratch % 4) == 0,
                  "kai0_multi_dot: a buffer is not aligned to its element size");
     MixK k{};
+    Stream st[9] = {{g, gsz}};  // anchor: g
     for (int i = 0; i < n_src; ++i) {
         KAI0_REQUIRE(srcs[i] != nullptr, "kai0_multi_dot: null buffer (source %d)", i);
         KAI0_REQUIRE(((uintptr_t)srcs[i] % ssz) == 0, "kai0_multi_dot: a buffer is not aligned to its element size (source %d)", i);
         k.src[i] = srcs[i];
+        st[1 + i] = {srcs[i], ssz};
     }
-    // elements before g's first 4-element boundary; every source must reach its own at the same element
-    int64_t head = (int64_t)(((4 * gsz - ((uintptr_t)g % (4 * gsz))) % (4 * gsz)) / gsz);
-    if (head > n) head = n;
-    for (int i = 0; i < n_src; ++i)
-        if (!aligned4(srcs[i], head, ssz)) head = n;  // no common head: scalar accesses throughout
-    const int64_t n4 = (n - head) >> 2, rest = n - 4 * n4;
-    int64_t blocks = (n4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;  // one partial per block and source in the scratch buffer
-    if (blocks < opt_grid(rest)) blocks = opt_grid(rest);
+    const StreamPlan pl = stream_plan(n, 4, 4096, st, 1 + n_src);  // one partial per block and source in the scratch buffer
+    const int64_t head = pl.head;
     hipStream_t s = (hipStream_t)stream;
-    dim3 grid((unsigned)blocks), block(256);
+    dim3 grid((unsigned)pl.blocks), block(256);
 #define LAUNCH_GS(G, S, N) hipLaunchKernelGGL((multi_dot_kernel<G, S, N>), grid, block, 0, s, g, k, n, head, scratch)
 #define LAUNCH_N(N)                                      \
     do {                                                 \
@@ -770,7 +714,7 @@ KAI0_API int kai0_multi_dot(const void* g, int g_f32, const void* const* srcs, i
     KAI0_FOR_NSRC(n_src, LAUNCH_N)
 #undef LAUNCH_N
 #undef LAUNCH_GS
-    hipLaunchKernelGGL(multi_dot_finish_kernel, dim3(n_src), dim3(256), 0, s, (const float*)scratch, (int)blocks, out);
+    hipLaunchKernelGGL(multi_dot_finish_kernel, dim3(n_src), dim3(256), 0, s, (const float*)scratch, (int)pl.blocks, out);
     return kai0_check_launch("kai0_multi_dot");
 }
 #undef KAI0_FOR_NSRC

@@ -31,61 +31,49 @@ def lr_schedule(step: int, *, warmup_steps: int, peak_lr: float, decay_steps: in
 WEIGHT_UPDATES = [0]  # bumped by every parameter update made through the HIP kernels (see infer.InferenceEngine._fingerprint)
 
 
-def adamw_step_(master, m, v, grad, param, *, lr, beta1, beta2, eps, wd, step: int, clip_coef=None):
-    """One fused AdamW update of a flat f32 shard (kai0_adamw)."""
+def adamw_step_(master, m, v, grad, param, *, lr, beta1, beta2, eps, wd, step: int, clip_coef=None, ema=None, ema_decay=None,
+                row_len=None, row_active=None):
+    """One fused AdamW update of a flat f32 shard: kai0_adamw, or the entry point the optional arguments select.
+
+    ema, ema_decay (together): kai0_adamw_ema / kai0_adamw_rows_ema — master / moments / model copy bit-identical, and in the same
+        pass ema += (1 - ema_decay) * (new master - ema) in f32.
+    row_len, row_active (together): kai0_adamw_rows / kai0_adamw_rows_ema — the shard is [rows * row_len] with a gradient that is zero
+        in most rows (embedding table); bit-identical to the dense form, idle rows cost their gradient read only.  row_active: uint8
+        [rows], persistent; with the EMA it must also be set for every row whose ema may differ from its master
+        (sharded._sparse_segments builds the flags that way)."""
     WEIGHT_UPDATES[0] += 1
     n = master.numel()
+    assert (ema is None) == (ema_decay is None) and (row_len is None) == (row_active is None)
+    name, ema_args, ema_tail, size = "kai0_adamw", (), (), (n,)
+    if row_len is not None:
+        assert n % row_len == 0 and row_active.numel() == n // row_len and row_active.dtype == torch.uint8
+        name, size = name + "_rows", (n // row_len, row_len, row_active.data_ptr())
+    if ema is not None:
+        assert ema.numel() == n and ema.dtype == F32
+        name, ema_args, ema_tail = name + "_ema", (ema.data_ptr(),), (float(ema_decay),)
     bc1 = 1.0 - beta1**step
     bc2 = 1.0 - beta2**step
-    _lib.call("kai0_adamw", master.data_ptr(), m.data_ptr(), v.data_ptr(), grad.data_ptr(), int(grad.dtype == F32),
-              param.data_ptr(), int(param.dtype == F32), n, lr, beta1, beta2, eps, wd, bc1, bc2,
+    _lib.call(name, master.data_ptr(), m.data_ptr(), v.data_ptr(), *ema_args, grad.data_ptr(), int(grad.dtype == F32),
+              param.data_ptr(), int(param.dtype == F32), *size, lr, beta1, beta2, eps, wd, bc1, bc2, *ema_tail,
               None if clip_coef is None else clip_coef.data_ptr(), _stream())  # fmt: skip
+
+
+# adamw_step_ under the names, and with the argument order, of the C entry points they select
+def adamw_rows_step_(master, m, v, grad, param, row_len: int, row_active, **kw):
+    adamw_step_(master, m, v, grad, param, row_len=row_len, row_active=row_active, **kw)
+
+
+def adamw_ema_step_(master, m, v, ema, grad, param, **kw):
+    adamw_step_(master, m, v, grad, param, ema=ema, **kw)
+
+
+def adamw_rows_ema_step_(master, m, v, ema, grad, param, row_len: int, row_active, **kw):
+    adamw_step_(master, m, v, grad, param, ema=ema, row_len=row_len, row_active=row_active, **kw)
 
 
 def sparse_rows_ok(lr: float, wd: float) -> bool:
     """True if an idle row (zero moments, zero gradient) is a fixed point of the update: 1 - lr*wd rounds to 1 in f32."""
     return bool(np.float32(1.0) - np.float32(lr) * np.float32(wd) == np.float32(1.0))
-
-
-def adamw_rows_step_(master, m, v, grad, param, row_len: int, row_active, *, lr, beta1, beta2, eps, wd, step: int, clip_coef=None):
-    """kai0_adamw_rows: the same update on a flat [rows * row_len] range whose gradient is zero in most rows (embedding table);
-    bit-identical to adamw_step_, idle rows cost their gradient read only.  row_active: uint8 [rows], persistent."""
-    WEIGHT_UPDATES[0] += 1
-    n = master.numel()
-    assert n % row_len == 0 and row_active.numel() == n // row_len and row_active.dtype == torch.uint8
-    bc1 = 1.0 - beta1**step
-    bc2 = 1.0 - beta2**step
-    _lib.call("kai0_adamw_rows", master.data_ptr(), m.data_ptr(), v.data_ptr(), grad.data_ptr(), int(grad.dtype == F32),
-              param.data_ptr(), int(param.dtype == F32), n // row_len, row_len, row_active.data_ptr(), lr, beta1, beta2, eps, wd,
-              bc1, bc2, None if clip_coef is None else clip_coef.data_ptr(), _stream())  # fmt: skip
-
-
-def adamw_ema_step_(master, m, v, ema, grad, param, *, lr, beta1, beta2, eps, wd, step: int, ema_decay: float, clip_coef=None):
-    """kai0_adamw_ema: adamw_step_ (bit-identical master / moments / model copy) and, in the same pass over the shard,
-    ema += (1 - ema_decay) * (new master - ema) in f32."""
-    WEIGHT_UPDATES[0] += 1
-    n = master.numel()
-    assert ema.numel() == n and ema.dtype == F32
-    bc1 = 1.0 - beta1**step
-    bc2 = 1.0 - beta2**step
-    _lib.call("kai0_adamw_ema", master.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), grad.data_ptr(), int(grad.dtype == F32),
-              param.data_ptr(), int(param.dtype == F32), n, lr, beta1, beta2, eps, wd, bc1, bc2, float(ema_decay),
-              None if clip_coef is None else clip_coef.data_ptr(), _stream())  # fmt: skip
-
-
-def adamw_rows_ema_step_(master, m, v, ema, grad, param, row_len: int, row_active, *, lr, beta1, beta2, eps, wd, step: int,
-                         ema_decay: float, clip_coef=None):
-    """kai0_adamw_rows_ema: adamw_rows_step_ with the EMA.  An idle row is skipped, EMA included, so `row_active` must also be set
-    for every row whose ema may differ from its master (sharded._sparse_segments builds the flags that way)."""
-    WEIGHT_UPDATES[0] += 1
-    n = master.numel()
-    assert n % row_len == 0 and row_active.numel() == n // row_len and row_active.dtype == torch.uint8
-    assert ema.numel() == n and ema.dtype == F32
-    bc1 = 1.0 - beta1**step
-    bc2 = 1.0 - beta2**step
-    _lib.call("kai0_adamw_rows_ema", master.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), grad.data_ptr(),
-              int(grad.dtype == F32), param.data_ptr(), int(param.dtype == F32), n // row_len, row_len, row_active.data_ptr(), lr,
-              beta1, beta2, eps, wd, bc1, bc2, float(ema_decay), None if clip_coef is None else clip_coef.data_ptr(), _stream())  # fmt: skip
 
 
 def check_ema_decay(ema_decay):
@@ -240,12 +228,8 @@ class FusedAdamW:
             coef = self._coef
         for p in live:
             st = self.state[p]
-            if self.ema_decay is not None:
-                adamw_ema_step_(st["master"], st["exp_avg"], st["exp_avg_sq"], st["ema"], p.grad.contiguous(), p.data, lr=lr,
-                                beta1=b1, beta2=b2, eps=eps, wd=wd, step=self.step_count, ema_decay=self.ema_decay, clip_coef=coef)  # fmt: skip
-                continue
-            adamw_step_(st["master"], st["exp_avg"], st["exp_avg_sq"], p.grad.contiguous(), p.data, lr=lr, beta1=b1,
-                        beta2=b2, eps=eps, wd=wd, step=self.step_count, clip_coef=coef)  # fmt: skip
+            adamw_step_(st["master"], st["exp_avg"], st["exp_avg_sq"], p.grad.contiguous(), p.data, lr=lr, beta1=b1, beta2=b2, eps=eps,
+                        wd=wd, step=self.step_count, clip_coef=coef, ema=st.get("ema"), ema_decay=self.ema_decay)  # fmt: skip
         return self._norm
 
     def state_dict(self):

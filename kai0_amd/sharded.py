@@ -85,29 +85,26 @@ class HipShardOps:
 
         grad_accum_(acc, grad, first=first, sumsq_out=sumsq_out)
 
-    def adamw(self, master, m, v, grad, param, *, lr, beta1, beta2, eps, wd, step, clip_coef):
+    # the four forms of the ShardOps protocol (an ops object may lack the _ema / _rows ones): here all of them optim.adamw_step_
+    def adamw(self, master, m, v, grad, param, **kw):
         from .optim import adamw_step_
 
-        adamw_step_(master, m, v, grad, param, lr=lr, beta1=beta1, beta2=beta2, eps=eps, wd=wd, step=step, clip_coef=clip_coef)
+        adamw_step_(master, m, v, grad, param, **kw)
 
-    def adamw_rows(self, master, m, v, grad, param, row_len, row_active, *, lr, beta1, beta2, eps, wd, step, clip_coef):
-        from .optim import adamw_rows_step_
+    def adamw_rows(self, master, m, v, grad, param, row_len, row_active, **kw):
+        from .optim import adamw_step_
 
-        adamw_rows_step_(master, m, v, grad, param, row_len, row_active, lr=lr, beta1=beta1, beta2=beta2, eps=eps, wd=wd, step=step,
-                         clip_coef=clip_coef)  # fmt: skip
+        adamw_step_(master, m, v, grad, param, row_len=row_len, row_active=row_active, **kw)
 
-    def adamw_ema(self, master, m, v, ema, grad, param, *, lr, beta1, beta2, eps, wd, step, clip_coef, ema_decay):
-        from .optim import adamw_ema_step_
+    def adamw_ema(self, master, m, v, ema, grad, param, **kw):
+        from .optim import adamw_step_
 
-        adamw_ema_step_(master, m, v, ema, grad, param, lr=lr, beta1=beta1, beta2=beta2, eps=eps, wd=wd, step=step,
-                        ema_decay=ema_decay, clip_coef=clip_coef)  # fmt: skip
+        adamw_step_(master, m, v, grad, param, ema=ema, **kw)
 
-    def adamw_rows_ema(self, master, m, v, ema, grad, param, row_len, row_active, *, lr, beta1, beta2, eps, wd, step, clip_coef,
-                       ema_decay):
-        from .optim import adamw_rows_ema_step_
+    def adamw_rows_ema(self, master, m, v, ema, grad, param, row_len, row_active, **kw):
+        from .optim import adamw_step_
 
-        adamw_rows_ema_step_(master, m, v, ema, grad, param, row_len, row_active, lr=lr, beta1=beta1, beta2=beta2, eps=eps, wd=wd,
-                             step=step, ema_decay=ema_decay, clip_coef=clip_coef)  # fmt: skip
+        adamw_step_(master, m, v, grad, param, ema=ema, row_len=row_len, row_active=row_active, **kw)
 
 
 def ema_lerp_weight(ema_decay: float) -> float:
@@ -840,16 +837,15 @@ class ShardedDataParallel:
         kw = dict(lr=lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, wd=self.wd, step=self.step_count, clip_coef=coef)
         segs = []
         ema_on = self.ema_decay is not None
-        fused = ema_on and hasattr(self.ops, "adamw_ema")
 
-        def dense(lo, hi):
-            args = (b.exp_avg[lo:hi], b.exp_avg_sq[lo:hi])
-            if fused:
-                self.ops.adamw_ema(b.master[lo:hi], *args, b.ema[lo:hi], grad[lo:hi], b.param_shard[lo:hi],
-                                   ema_decay=self.ema_decay, **kw)  # fmt: skip
-                return
-            self.ops.adamw(b.master[lo:hi], *args, grad[lo:hi], b.param_shard[lo:hi], **kw)
-            if ema_on:  # an ops object without the fused form (the torch oracle of the CPU tests): the same update as a second pass
+        def update(lo, hi, rows=None):
+            """[lo, hi) of the shard; rows = (row_len, row_active): the row-sparse form."""
+            name = "adamw_rows" if rows else "adamw"
+            fused = ema_on and hasattr(self.ops, name + "_ema")
+            state = (b.master[lo:hi], b.exp_avg[lo:hi], b.exp_avg_sq[lo:hi]) + ((b.ema[lo:hi],) if fused else ())
+            ema_kw = {"ema_decay": self.ema_decay} if fused else {}
+            getattr(self.ops, name + "_ema" if fused else name)(*state, grad[lo:hi], b.param_shard[lo:hi], *(rows or ()), **ema_kw, **kw)
+            if ema_on and not fused:  # an ops object without the fused form (the torch oracle of the CPU tests): the same update as a second pass
                 b.ema[lo:hi].lerp_(b.master[lo:hi], ema_lerp_weight(self.ema_decay))
 
         # with EMA the row-sparse form must know about it (an ops object that does not falls back to the dense update)
@@ -866,17 +862,11 @@ class ShardedDataParallel:
         cur = 0
         for first, rows, rl, active in segs:
             if first > cur:
-                dense(cur, first)
-            end = first + rows * rl
-            if ema_on:
-                self.ops.adamw_rows_ema(b.master[first:end], b.exp_avg[first:end], b.exp_avg_sq[first:end], b.ema[first:end],
-                                        grad[first:end], b.param_shard[first:end], rl, active, ema_decay=self.ema_decay, **kw)  # fmt: skip
-            else:
-                self.ops.adamw_rows(b.master[first:end], b.exp_avg[first:end], b.exp_avg_sq[first:end], grad[first:end],
-                                    b.param_shard[first:end], rl, active, **kw)  # fmt: skip
-            cur = end
+                update(cur, first)
+            update(first, first + rows * rl, (rl, active))
+            cur = first + rows * rl
         if cur < b.shard:
-            dense(cur, b.shard)
+            update(cur, b.shard)
 
     # ------------------------------------------------------------------------------------------ checkpointing
     @torch.no_grad()

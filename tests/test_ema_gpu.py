@@ -180,6 +180,30 @@ def test_adamw_rows_ema_is_bit_identical_to_the_dense_ema_update():
     optim.adamw_ema_step_(d4[0], d4[1], d4[2], d4[3], g2, pd, **kw)
     optim.adamw_rows_ema_step_(s4[0], s4[1], s4[2], s4[3], g2, ps, rl2, act2, **kw)
     assert all(torch.equal(a, b) for a, b in zip(s4 + [ps], d4 + [pd])) and int(act2.sum()) == 20
+    # small tables, aligned (off = 0) and as views one element in (off = 1: scalar scan, scalar update).  (19, 12): scalar scan, vector
+    # update; (19, 6): scalar throughout; (5, 2056): a second trip of the 2048-element scan stride and of the 1024-element update stride.
+    # Every third row is idle (zeros and -0.0 for a gradient, ema == master, zero moments): it keeps its bytes and its clear flag.
+    for rows3, rl3 in ((37, 8), (19, 12), (19, 6), (5, 2056)):
+        for off in (0, 1):
+            n3 = rows3 * rl3
+            live = torch.tensor([i % 3 != 1 for i in range(rows3)], device=dev())
+            p3 = (torch.randn(rows3, rl3, device=dev(), generator=gen) * 0.02).to(BF16).float()
+            e3 = p3.clone()
+            e3[live] += 1e-3
+            g3 = torch.randn(rows3, rl3, device=dev(), generator=gen)
+            g3[~live] = 0
+            g3[~live, ::2] = -0.0
+            g3 = _view(n3, BF16, off, gen, like=g3.reshape(-1))
+            init = [p3.reshape(-1), torch.zeros(n3, device=dev()), torch.zeros(n3, device=dev()), e3.reshape(-1), p3.reshape(-1).to(BF16)]
+            d3, s3 = ([_view(n3, t.dtype, off, gen, like=t) for t in init] for _ in range(2))
+            act3 = torch.zeros(rows3, dtype=torch.uint8, device=dev())
+            optim.adamw_step_(d3[0], d3[1], d3[2], g3, d3[4], ema=d3[3], **kw)
+            optim.adamw_step_(s3[0], s3[1], s3[2], g3, s3[4], ema=s3[3], row_len=rl3, row_active=act3, **kw)
+            for a, b, t, what in zip(s3, d3, init, ("master", "m", "v", "ema", "param")):
+                assert torch.equal(a, b), (what, rows3, rl3, off)
+                assert torch.equal(a.view(rows3, rl3)[~live], t.view(rows3, rl3)[~live]), (what, rows3, rl3, off)
+            assert bool((s3[3].view(rows3, rl3)[live] != e3[live]).any(1).all())
+            assert torch.equal(act3.bool(), live), (rows3, rl3, off)
 
 
 # -------------------------------------------------------------------------------------------------- 10. Trainer

@@ -847,6 +847,30 @@ def test_adamw_rows_is_bit_identical_to_the_dense_update(ops, gdtype):
     with pytest.raises(Exception, match="does not round away"):
         m, e, v, p = state["rows"]
         optim.adamw_rows_step_(m, e, v, grad, p, rl, active, lr=1e-3, step=7, clip_coef=coef, beta1=0.9, beta2=0.95, eps=1e-8, wd=1e-2)
+    # small tables, aligned (off = 0) and as views one element in (off = 1: scalar scan, scalar update).  (19, 12): scalar scan, vector
+    # update; (19, 6): scalar throughout; (5, 2056): a second trip of the 2048-element scan stride and of the 1024-element update stride.
+    # Every third row is idle (zeros and -0.0 for a gradient, zero moments): it keeps its bytes and its clear flag.
+    for rows, rl in ((37, 8), (19, 12), (19, 6), (5, 2056)):
+        for off in (0, 1):
+            n = rows * rl
+            view = lambda t: torch.zeros(n + off + 8, dtype=t.dtype, device=dev())[off : off + n].copy_(t.reshape(-1))  # noqa: E731
+            live = torch.tensor([i % 3 != 1 for i in range(rows)], device=dev())
+            p0 = (torch.randn(rows, rl, device=dev(), generator=g0) * 0.02).to(BF16)
+            grad = torch.randn(rows, rl, device=dev(), generator=g0)
+            grad[~live] = 0
+            grad[~live, ::2] = -0.0
+            grad = view(grad.to(gdtype))
+            init = [p0.float(), torch.zeros(rows, rl, device=dev()), torch.zeros(rows, rl, device=dev()), p0]
+            dense, sparse = ([view(t) for t in init] for _ in range(2))
+            assert dense[0].data_ptr() % 16 == 4 * off and grad.data_ptr() % 16 == grad.element_size() * off
+            active = torch.zeros(rows, dtype=torch.uint8, device=dev())
+            optim.adamw_step_(*dense[:3], grad, dense[3], lr=2.5e-5, step=3, clip_coef=coef, **kw)
+            optim.adamw_step_(*sparse[:3], grad, sparse[3], row_len=rl, row_active=active, lr=2.5e-5, step=3, clip_coef=coef, **kw)
+            for a, b, t in zip(sparse, dense, init):
+                assert torch.equal(a, b), (rows, rl, off)
+                assert torch.equal(a.view(rows, rl)[~live], t[~live]), (rows, rl, off)
+            assert not torch.equal(sparse[0].view(rows, rl)[live], init[0][live])
+            assert torch.equal(active.bool(), live), (rows, rl, off)
 
 
 @pytest.mark.parametrize("kind,M,N,K,split", [(2, 768, 1152, 4304, 4), (2, 768, 1152, 1152, 3), (1, 968, 2048, 16384, 6), (1, 50, 64, 512, 2),

@@ -50,19 +50,22 @@ def P(t):
 
 
 class Out:
-    """An output between two bands of GUARD sentinel elements, pre-filled with NaN (or a copy of `init` for in-place kernels)."""
+    """An output between two bands of GUARD sentinel elements, pre-filled with NaN (or a copy of `init` for in-place kernels).
+    `off`: the output starts that many elements past the 16-byte boundary (the front band is that much longer)."""
 
-    def __init__(self, shape, dtype, fill=NAN, init=None):
+    def __init__(self, shape, dtype, fill=NAN, init=None, off=0):
         n = math.prod(shape)
-        self.buf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=dtype, device=DEV)
-        self.t = self.buf[GUARD : GUARD + n].view(shape)
+        self.front = GUARD + off
+        self.buf = torch.full((self.front + n + GUARD,), SENTINEL, dtype=dtype, device=DEV)
+        self.t = self.buf[self.front : self.front + n].view(shape)
+        assert self.t.data_ptr() % 16 == (off * self.t.element_size()) % 16
         if init is not None:
             self.t.copy_(init)
         else:
             self.t.fill_(fill)
 
     def check(self, what):
-        assert bool((self.buf[:GUARD] == SENTINEL).all()) and bool((self.buf[-GUARD:] == SENTINEL).all()), f"{what}: wrote outside its output"
+        assert bool((self.buf[: self.front] == SENTINEL).all()) and bool((self.buf[-GUARD:] == SENTINEL).all()), f"{what}: wrote outside its output"
         left = int(torch.isnan(self.t).sum())
         assert left == 0, f"{what}: {left} of {self.t.numel()} elements never written (first at flat index {int(torch.isnan(self.t).reshape(-1).nonzero()[0])})"
 
@@ -619,24 +622,78 @@ def _adam_args(k):
 
 
 def test_adamw_past_the_grid_cap():
-    """opt_grid(n): 2^20 elements a trip; n = 2^20 + 4099.  bf16 gradient and model copy, clip coefficient from device memory."""
+    """n = 2^20 + 4099, bf16 gradient and model copy, clip coefficient from device memory.  With every stream 16-byte aligned the
+    vectors go one per lane (one contiguous run of 256 per block, 1025 blocks + 3 tail elements): no cap is passed — the vector
+    path caps its grid at 2^22 blocks, i.e. past 2^32 elements, which no test reaches (for the EMA form neither);
+    kai0_grad_accum with its 4096-block cap walks the same per-block run loop (tests/test_grad_accum_gpu.py).  With the f32
+    streams one element in and the 16-bit ones aligned there is no common head: the scalar form, grid-strided over opt_grid's
+    4096 blocks x 256 lanes = 2^20 elements a trip, takes a second trip."""
     n = 2**20 + 4099
     master0 = rnd(n, seed=1, scale=0.02).float()
     m0, v0 = rnd(n, dtype=F32, seed=2, scale=1e-2), rnd(n, dtype=F32, seed=3, scale=1e-2).abs()
     grad, coef = rnd(n, seed=4), torch.tensor([0.37], device=DEV)
+    ref = R.adamw(master0, m0, v0, grad, coef, *_adam_args(ADAM), F64)
 
     def launch(lo, hi, o):
         call("kai0_adamw", P(o["master"].t[lo:]), P(o["m"].t[lo:]), P(o["v"].t[lo:]), P(grad[lo:]), 0, P(o["param"].t[lo:]), 0, hi - lo,
              *_adam_args(ADAM), P(coef))
 
-    def new():
-        return dict(master=Out((n,), F32, init=master0), m=Out((n,), F32, init=m0), v=Out((n,), F32, init=v0), param=Out((n,), BF16))
+    for what, off32 in (("adamw", 0), ("adamw no common head", 1)):
 
-    o = whole_and_sliced(launch, new, n, 2**19, "adamw")
-    ref = R.adamw(master0, m0, v0, grad, coef, *_adam_args(ADAM), F64)
-    for k in ("master", "m", "v"):
-        within(o[k].t, ref[k], f"A adamw.{k}")
-    exact(o["param"].t, o["master"].t.to(BF16), "adamw model copy")
+        def new():
+            return dict(master=Out((n,), F32, init=master0, off=off32), m=Out((n,), F32, init=m0, off=off32),
+                        v=Out((n,), F32, init=v0, off=off32), param=Out((n,), BF16))  # fmt: skip
+
+        o = whole_and_sliced(launch, new, n, 2**19, what)
+        for k in ("master", "m", "v"):
+            within(o[k].t, ref[k], f"A {what}.{k}")
+        exact(o["param"].t, o["master"].t.to(BF16), f"{what} model copy")
+
+
+ADAMW_N = (1, 3, 5, 255, 1027, 4099)
+# elements past a 16-byte boundary at which the f32 / the 16-bit streams start
+ADAMW_LAYOUTS = {"aligned": (0, 0), "one_in": (1, 1), "no_common_head": (1, 0)}
+_ADAMW_CASES = {}
+
+
+def _adamw_case(n):
+    """Inputs and float64 references (without and with the clip coefficient) of one length, computed once and never written to.
+    The gradient values are bf16 numbers, so one reference serves both gradient dtypes."""
+    if n not in _ADAMW_CASES:
+        c = dict(master=rnd(n, seed=1, scale=0.02).float(), m=rnd(n, dtype=F32, seed=2, scale=1e-2),
+                 v=rnd(n, dtype=F32, seed=3, scale=1e-2).abs(), grad=rnd(n, seed=4), coef=torch.tensor([0.37], device=DEV))  # fmt: skip
+        c["ref"] = {clip: R.adamw(c["master"], c["m"], c["v"], c["grad"], c["coef"] if clip else torch.ones(1, device=DEV),
+                                  *_adam_args(ADAM), F64) for clip in (False, True)}  # fmt: skip
+        _ADAMW_CASES[n] = c
+    return _ADAMW_CASES[n]
+
+
+@pytest.mark.parametrize("g_f32,p_f32", [(0, 0), (0, 1), (1, 0), (1, 1)])
+@pytest.mark.parametrize("layout", list(ADAMW_LAYOUTS))
+def test_adamw_heads_tails_and_layouts(layout, g_f32, p_f32):
+    """kai0_adamw's scalar head, vectors and scalar tail: n = 1 and 3 (the head clamped to n), 5 (head 1 + one vector with every
+    stream one element in), 255, 1027 (one block's 256 vectors + a 3-element tail), 4099; every stream 16-byte aligned, every
+    stream one element in (a common head of 3), f32 streams one element in with aligned 16-bit ones (no common head: the scalar
+    form; with f32 gradient and model copy this is `one_in` again); every (grad, param) dtype pair; clip coefficient absent and
+    from device memory.  Moments and master within the float64 bound, the model copy exactly the rounded master, guard bands."""
+    off32, off16 = ADAMW_LAYOUTS[layout]
+    gdt, goff = (F32, off32) if g_f32 else (BF16, off16)
+    pdt, poff = (F32, off32) if p_f32 else (BF16, off16)
+    for n in ADAMW_N:
+        c = _adamw_case(n)
+        grad = Out((n,), gdt, init=c["grad"], off=goff).t
+        for clip in (False, True):
+            o = dict(master=Out((n,), F32, init=c["master"], off=off32), m=Out((n,), F32, init=c["m"], off=off32),
+                     v=Out((n,), F32, init=c["v"], off=off32), param=Out((n,), pdt, off=poff))  # fmt: skip
+            call("kai0_adamw", P(o["master"].t), P(o["m"].t), P(o["v"].t), P(grad), g_f32, P(o["param"].t), p_f32, n, *_adam_args(ADAM),
+                 P(c["coef"]) if clip else None)
+            torch.cuda.synchronize()
+            what = f"B adamw n={n} {layout} g_f32={g_f32} p_f32={p_f32} clip={clip}"
+            for k in ("master", "m", "v", "param"):
+                o[k].check(f"{what}.{k}")
+            for k in ("master", "m", "v"):
+                within(o[k].t, c["ref"][clip][k], f"{what}.{k}")
+            exact(o["param"].t, o["master"].t.to(pdt), f"{what} model copy")
 
 
 @pytest.mark.parametrize("g_f32", [0, 1])
@@ -681,6 +738,42 @@ def test_adamw_rows_past_the_grid_cap(g_f32):
         exact(small[key].t, big[key].t, f"adamw_rows.{key} sliced")
     assert torch.equal(active["big"].bool(), live) and torch.equal(active["small"].bool(), live)
     assert bool((big["m"].t.view(rows, rl)[~live] == 0).all())
+    for rows, rl in ROWS_SHAPES:
+        for off in (0, 1):
+            _adamw_rows_small(rows, rl, g_f32, off, k, coef)
+
+
+# (19, 12): scalar scan, vector update; (19, 6): scalar throughout; (5, 2056): a second trip of the 2048-element scan stride and of the
+# 1024-element update stride
+ROWS_SHAPES = [(37, 8), (19, 12), (19, 6), (5, 2056)]
+
+
+def _adamw_rows_small(rows, rl, g_f32, off, k, coef):
+    """kai0_adamw_rows on [rows][rl] with every stream `off` elements past a 16-byte boundary (1: no vector scan, no vector
+    update) against kai0_adamw on clones: all four outputs equal, every third row idle (zeros and -0.0 for a gradient) keeps its
+    bytes and its clear flag, the other rows get their flag."""
+    n, gdt = rows * rl, F32 if g_f32 else BF16
+    master0 = rnd(n, seed=1, scale=0.02).float()
+    live = torch.tensor([i % 3 != 1 for i in range(rows)], device=DEV)
+    g = rnd(rows, rl, dtype=gdt, seed=4)
+    g[~live] = 0
+    g[~live, ::2] = -0.0
+    grad = Out((n,), gdt, init=g.reshape(-1), off=off).t
+    init = dict(master=master0, m=torch.zeros(n, device=DEV), v=torch.zeros(n, device=DEV), param=master0.to(BF16))
+    sparse, dense = ({key: Out((n,), t.dtype, init=t, off=off) for key, t in init.items()} for _ in range(2))
+    active = torch.zeros(rows, dtype=torch.uint8, device=DEV)
+    call("kai0_adamw_rows", P(sparse["master"].t), P(sparse["m"].t), P(sparse["v"].t), P(grad), g_f32, P(sparse["param"].t), 0, rows, rl,
+         P(active), *_adam_args(k), P(coef))
+    call("kai0_adamw", P(dense["master"].t), P(dense["m"].t), P(dense["v"].t), P(grad), g_f32, P(dense["param"].t), 0, n, *_adam_args(k), P(coef))
+    torch.cuda.synchronize()
+    what = f"adamw_rows {rows}x{rl} off={off}"
+    for key, t in init.items():
+        sparse[key].check(f"{what}.{key}")
+        dense[key].check(f"{what}.{key} (dense)")
+        exact(sparse[key].t, dense[key].t, f"{what}.{key} vs kai0_adamw")
+        assert torch.equal(sparse[key].t.view(rows, rl)[~live], t.view(rows, rl)[~live]), f"{what}.{key}: an idle row changed"
+    assert not torch.equal(sparse["master"].t.view(rows, rl)[live], master0.view(rows, rl)[live])
+    assert torch.equal(active.bool(), live), what
 
 
 # =================================================================================================== B. the rest

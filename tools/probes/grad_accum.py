@@ -42,7 +42,7 @@ step = [0]
 
 
 def a():
-    optim.adamw_ema_step_(master, m, v, ema, grad, param, step=step[0], ema_decay=D, **kw)
+    optim.adamw_step_(master, m, v, grad, param, step=step[0], ema=ema, ema_decay=D, **kw)
 
 
 def b():
