@@ -29,7 +29,6 @@
 
 namespace {
 
-constexpr uint32_t OOB = 0x80000000u;
 // timing ablations (phases switched off; results wrong) exist only in builds made with KAI0_HIPCC_FLAGS=-DKAI0_ABLATE
 #ifdef KAI0_ABLATE
 #define KAI0_ABL(p) ((p).ablate)
@@ -37,17 +36,6 @@ constexpr uint32_t OOB = 0x80000000u;
 #define KAI0_ABL(p) 0
 #endif
 constexpr int KC_LDS_MAX = 2048;  // key codes staged in LDS per block (8 KiB): covers S = 1018 and the estimator's 1786
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, char* lds_dst_wave_uniform) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LDS_PTR(void))lds_dst_wave_uniform, 16, (int)voff, 0, 0, 0);
-}
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
 
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(4))) int i32x4v;

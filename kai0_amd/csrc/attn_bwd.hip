@@ -30,19 +30,6 @@
 
 namespace {
 
-constexpr uint32_t OOB = 0x80000000u;
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, char* lds_dst_wave_uniform) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LDS_PTR(void))lds_dst_wave_uniform, 16, (int)voff, 0, 0, 0);
-}
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 
 constexpr int AB_KC_MAX = 2048;  // key codes staged in LDS (RC): covers S = 1018 and the estimator's 1786

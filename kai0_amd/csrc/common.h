@@ -18,6 +18,22 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 #define LDS_PTR(T) __attribute__((address_space(3))) T*
 #define GLB_PTR(T) __attribute__((address_space(1))) T*
 
+// LDS-DMA through a raw buffer descriptor: 16 B per lane from base + voff (bytes) to lds_dst + lane*16.  An offset at
+// or beyond the descriptor's 2 GiB range returns zeros — that is how tile edges and the K tail are zero-filled
+// (no second source pointer, no per-lane 64-bit address).
+constexpr uint32_t OOB = 0x80000000u;
+__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, char* lds_dst_wave_uniform) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LDS_PTR(void))lds_dst_wave_uniform, 16, (int)voff, 0, 0, 0);
+}
+// block barrier that does NOT drain the LDS-DMA queue behind the compiler's back: the kernel places its own vmcnt.
+__device__ __forceinline__ void lds_barrier() {
+    __builtin_amdgcn_sched_barrier(0);  // keep register-only MFMAs on their side of the barrier (they ignore "memory")
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 // ---- error plumbing (host side) -------------------------------------------------------------
 void kai0_set_error(const char* fmt, ...);
 int kai0_check_launch(const char* what);

@@ -106,15 +106,8 @@ struct GemmArgs {
     int64_t ldct, ldct2;
 };
 
-// LDS-DMA through a raw buffer descriptor: 16 B per lane from base + voff (bytes) to lds_dst + lane*16.  An offset at
-// or beyond the descriptor's 2 GiB range returns zeros — that is how tile edges and the K tail are zero-filled
-// (no second source pointer, no per-lane 64-bit address).
-typedef __attribute__((ext_vector_type(4))) int i32x4_t;
-constexpr uint32_t OOB = 0x80000000u;
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, char* lds_dst_wave_uniform) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LDS_PTR(void))lds_dst_wave_uniform, 16, (int)voff, 0, 0, 0);
-}
-
+// (glds16 / OOB, the LDS-DMA that stages every operand and zero-fills tile edges and the K tail: common.h)
+//
 // Swizzle key of a contraction-strided (MC) tile row r: key(r) = (r & 3) | (((r >> 3) & 1) << 2).
 // It spreads the 8 k-rows that a 32-lane half of ds_read_b64_tr_b16 touches ({0..3, 8..11} + 4h) over the 8
 // distinct 32-B segments of the 256-B bank row.  Both the DMA source address and the read address apply it.
@@ -122,6 +115,42 @@ __device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t vof
 __device__ __forceinline__ void store_pre8(bf16_t* dst, bf16x8 v, int nt) {
     if (nt) __builtin_nontemporal_store(v, reinterpret_cast<bf16x8*>(dst));
     else *reinterpret_cast<bf16x8*>(dst) = v;
+}
+
+// ---- row helpers of the epilogue passes of gemm_bf16_kernel and gemm_nt_persistent_kernel ----
+// The 256 x 256 kernels sit at the register limit, so a helper is called only where tools/device_asm_diff.py shows every kernel's machine
+// code unchanged by it; a site where the call changes the code keeps the statements, with a note (profiles/gemm_epilogue_helpers_resources.txt).
+
+// the bias of a lane's 8 columns [ccol, ccol + 8), f32 or bf16, as f32
+__device__ __forceinline__ void load_bias8(const void* bias, int bias_f32, int ccol, float (&bv)[8]) {
+    if (bias_f32) {
+        const f32x4 b0 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(bias) + ccol);
+        const f32x4 b1 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(bias) + ccol + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { bv[e] = b0[e]; bv[4 + e] = b1[e]; }
+    } else {
+        const bf16x8 b = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16_t*>(bias) + ccol);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) bv[e] = bf2f(b[e]);
+    }
+}
+
+// N accumulator row-tiles (16 rows x 64 columns each) of a wave, from tile `first`, -> its slab.  C layout of a 16x16 tile: col = lane&15, row = 4*(lane>>4) + reg.
+// `first` is a compile-time constant at every call, so acc[] keeps static indices.
+template <int N, int MT>
+__device__ __forceinline__ void acc_to_slab(float* slab, const f32x4 (&acc)[MT][4], int first, int g, int l15) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) slab[(i * 16 + 4 * g + r) * 64 + j * 16 + l15] = acc[first + i][j][r];
+}
+
+// a lane's 8 consecutive f32 columns of a slab row (two 16-byte LDS reads)
+__device__ __forceinline__ void slab_row8(const float* sp, float (&v)[8]) {
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp), v1 = *reinterpret_cast<const f32x4*>(sp + 4);
+    v[0] = v0[0], v[1] = v0[1], v[2] = v0[2], v[3] = v0[3], v[4] = v1[0], v[5] = v1[1], v[6] = v1[2], v[7] = v1[3];  // (no loop: as the initialiser lists it replaces)
 }
 
 // act 3 on 8 columns of a row, for the passes that also store transposed: v = dh (f32 accumulators), g / u = the forward's saved pair;
@@ -139,6 +168,42 @@ __device__ __forceinline__ void geglu_bwd8(const float (&v)[8], bf16x8 g, bf16x8
         du[e + 1] = f2bf(a[1]);
         dg[e] = f2bf(b[0]);
         dg[e + 1] = f2bf(b[1]);
+    }
+}
+
+// act 6 (GeGLU pair) on 8 columns of a row: gv / uv = the gate's and the up projection's f32 accumulators.  Rounding points of act 2:
+// gb = bf16(gv), ub = bf16(uv), hb = bf16(bf16(gelu_tanh(gb)) * ub)
+__device__ __forceinline__ void geglu_pair8(const float (&gv)[8], const float (&uv)[8], bf16x8& gb, bf16x8& ub, bf16x8& hb) {
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) {
+        const f32x2 gr = rbf2(f32x2{gv[e], gv[e + 1]}), ur = rbf2(f32x2{uv[e], uv[e + 1]});
+        const f32x2 hv = rbf2(gelu_tanh2(gr)) * ur;
+        gb[e] = f2bf(gr[0]);
+        gb[e + 1] = f2bf(gr[1]);
+        ub[e] = f2bf(ur[0]);
+        ub[e + 1] = f2bf(ur[1]);
+        hb[e] = f2bf(hv[0]);
+        hb[e + 1] = f2bf(hv[1]);
+    }
+}
+
+// Where a lane's 8 bf16 output columns [ccol, ccol + 8) go: C, or one of up to 3 column segments (fused q|k|v projection) -> the address of
+// row 0's 8 columns and the row pitch; resolved once, the columns do not change with the row.  Constant indices only: a run-time index
+// would put the whole argument block into scratch.
+__device__ __forceinline__ void route_cols8(const GemmArgs& p, int ccol, int64_t cz, bf16_t*& cl, int64_t& ldl) {
+    cl = reinterpret_cast<bf16_t*>(p.C) + cz + ccol;
+    ldl = p.ldc;
+    if (p.nseg > 0) {
+        cl = p.seg_dst[0] + (ccol - p.seg_begin[0]);
+        ldl = p.seg_ld[0];
+        if (p.nseg > 1 && ccol >= p.seg_begin[1]) {
+            cl = p.seg_dst[1] + (ccol - p.seg_begin[1]);
+            ldl = p.seg_ld[1];
+        }
+        if (p.nseg > 2 && ccol >= p.seg_begin[2]) {
+            cl = p.seg_dst[2] + (ccol - p.seg_begin[2]);
+            ldl = p.seg_ld[2];
+        }
     }
 }
 
@@ -333,15 +398,6 @@ __device__ __forceinline__ void epilogue8(const GemmArgs& p, float (&v)[8], int 
 // not) makes hipcc allocate the 256 x 256 kernels' registers differently.
 #define SIMPLE_EPILOGUE_APPLIES(simple_epi, act, split_k, gate, out_f32, scale, c_rpb, n) \
     ((simple_epi) && (act) <= 1 && (split_k) == 1 && (gate) == nullptr && !(out_f32) && (scale) == 1.0f && (c_rpb) == 0 && (N_ALIGNED8(n)))
-
-// block barrier that does NOT drain the LDS-DMA queue behind the compiler's back: the kernel places its own vmcnt.
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_sched_barrier(0);  // keep register-only MFMAs on their side of the barrier (they ignore "memory")
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
 
 // Block tile = (WM*MT*16) x (WN*NT*16) x BKT, WM x WN waves, each wave MT x NT MFMA 16x16x32 tiles.  Three K loops:
 // plain multi-stage (PP = false, SCH = 0): NS LDS stages of BKT = 64.  NS = 2: one K-tile of prefetch, enough when a second
@@ -866,12 +922,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
                 cs[it] = *reinterpret_cast<const bf16x8*>(p.rope_cos + (rot ? tr : 0));
                 sn[it] = *reinterpret_cast<const bf16x8*>(p.rope_sin + (rot ? tr : 0));
             }
-#pragma unroll
-            for (int i = 0; i < AH; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) slab[(i * 16 + 4 * g + r) * 64 + j * 16 + l15] = acc[i][j][r];
+            acc_to_slab<AH>(slab, acc, h * AH, g, l15);  // (h == 0: these tiles have one half)
             lds_barrier();
             const float* pslab = reinterpret_cast<const float*>(smem + (wave ^ 1) * (AH * 4096));
             int si = 0;
@@ -883,6 +934,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
                 const int lr = it * 8 + (lane >> 3);
                 const int row = rbase + it * 8;
                 const int so = lr * 64 + (lane & 7) * 8;
+                // (not slab_row8: with the spread in front of the edge test these kernels' machine code changes)
                 const f32x4 v0 = *reinterpret_cast<const f32x4*>(slab + so), v1 = *reinterpret_cast<const f32x4*>(slab + so + 4);
                 const f32x4 w0 = *reinterpret_cast<const f32x4*>(pslab + so), w1 = *reinterpret_cast<const f32x4*>(pslab + so + 4);
                 if (row >= p.M || !rcol_ok) continue;
@@ -907,12 +959,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
             // GeGLU in registers: slab columns [0, 32) = gate, [32, 64) = up of the wave's 32 output columns n0/2 + wn*32 + ..;
             // each lane takes 8 of them for one row (16 rows per pass).  Rounding points of act 2: g = bf16(acc), u = bf16(acc),
             // h = bf16(bf16(gelu_tanh(g)) * u)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) slab[(i * 16 + 4 * g + r) * 64 + j * 16 + l15] = acc[h * 4 + i][j][r];
+            acc_to_slab<AH>(slab, acc, h * AH, g, l15);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
             const int ocol = (n0 >> 1) + wn * 32 + (lane & 3) * 8;
@@ -923,6 +970,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
                 const int lr = it * 16 + (lane >> 2);
                 const int row = row_base(h) + lr;
                 const float* sp = slab + lr * 64 + (lane & 3) * 8;
+                // (slab_row8 / geglu_pair8's statements in place, as in the persistent kernel before it took them: here they change every tile kernel's machine code)
                 const f32x4 g0 = *reinterpret_cast<const f32x4*>(sp), g1 = *reinterpret_cast<const f32x4*>(sp + 4);
                 const f32x4 u0 = *reinterpret_cast<const f32x4*>(sp + 32), u1 = *reinterpret_cast<const f32x4*>(sp + 36);
                 bf16x8 hb = bf16x8{};
@@ -957,12 +1005,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
         if constexpr (CT_TILE) if (p.act == 0) {
             // the plain product with CT (host: no bias / gate / residual / accumulate / scale / segments): C = bf16(acc), as the
             // store-with-little-else epilogue rounds it, and each 8-row pass transposed out of the slab rows it has just read
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) slab[(i * 16 + 4 * g + r) * 64 + j * 16 + l15] = acc[h * 4 + i][j][r];
+            acc_to_slab<AH>(slab, acc, h * AH, g, l15);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
             bf16_t* cb = reinterpret_cast<bf16_t*>(p.C);
@@ -970,9 +1013,8 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
 #pragma unroll
             for (int it = 0; it < 8; ++it) {
                 const int row = rbase + it * 8;
-                const float* sp = slab + (it * 8 + (lane >> 3)) * 64 + (lane & 7) * 8;
-                const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp), v1 = *reinterpret_cast<const f32x4*>(sp + 4);
-                const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                float v[8];
+                slab_row8(slab + (it * 8 + (lane >> 3)) * 64 + (lane & 7) * 8, v);
                 bf16x8 ov = bf16x8{};
                 if (row < p.M && col_ok) {
 #pragma unroll
@@ -1002,22 +1044,15 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
                     if (p.act == 4) ds[it] = p.rowvec[vz + (int64_t)row * p.rv_ld];
                 }
             }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) slab[(i * 16 + 4 * g + r) * 64 + j * 16 + l15] = acc[h * 4 + i][j][r];
+            acc_to_slab<AH>(slab, acc, h * AH, g, l15);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
             bf16_t* cb = reinterpret_cast<bf16_t*>(p.C);
 #pragma unroll
             for (int it = 0; it < 8; ++it) {
                 const int row = rbase + it * 8;
-                const float* sp = slab + (it * 8 + (lane >> 3)) * 64 + (lane & 7) * 8;
-                const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp);
-                const f32x4 v1 = *reinterpret_cast<const f32x4*>(sp + 4);
-                const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                float v[8];
+                slab_row8(slab + (it * 8 + (lane >> 3)) * 64 + (lane & 7) * 8, v);
                 if constexpr (CT_TILE) {  // act 3 with dgT / duT (host: of the fused forms only act 3 reaches this instantiation)
                     // the arithmetic of the act-3 branch below, then the two transposed stores, outside the edge test: every lane takes part
                     bf16x8 du = bf16x8{}, dgv = bf16x8{};
@@ -1035,6 +1070,8 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
                 if (row >= p.M || !col_ok) continue;
                 const int64_t o = cz + p.cmap(row) * p.ldc + ccol;
                 bf16x8 ov;
+                // (this act 2 / 3 / 5 / 4 row stands once more in the persistent kernel: as one function it grows every tile kernel by 100-200
+                // instructions and moves the persistent kernel's spills, 59 -> 62)
                 if (p.act == 2) {  // same order and rounding points as epilogue8
                     if (p.pre_out != nullptr) {
                         bf16x8 uv;
@@ -1087,18 +1124,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
             // all of its rows), the 8 residual rows of the half before the accumulators go to the slab.  In the rolled loop below every
             // iteration waited out a bias and a residual round trip of its own — most of the fixed cost of the small (B = 1) GEMMs.
             float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (p.bias != nullptr && col_ok) {
-                if (p.bias_f32) {
-                    const f32x4 b0 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.bias) + ccol);
-                    const f32x4 b1 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.bias) + ccol + 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { bv[e] = b0[e]; bv[4 + e] = b1[e]; }
-                } else {
-                    const bf16x8 b = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16_t*>(p.bias) + ccol);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) bv[e] = bf2f(b[e]);
-                }
-            }
+            if (p.bias != nullptr && col_ok) load_bias8(p.bias, p.bias_f32, ccol, bv);
             bf16x8 rs[AH * 2];
             const int rbase = row_base(h) + (lane >> 3);
 #pragma unroll
@@ -1107,12 +1133,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
                 rs[it] = bf16x8{};
                 if (p.residual != nullptr && row < p.M && col_ok) rs[it] = *reinterpret_cast<const bf16x8*>(p.residual + rz + p.cmap(row) * p.ldr + ccol);
             }
-#pragma unroll
-            for (int i = 0; i < AH; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) slab[(i * 16 + 4 * g + r) * 64 + j * 16 + l15] = acc[h * AH + i][j][r];
+            acc_to_slab<AH>(slab, acc, h * AH, g, l15);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
             bf16_t* cb = reinterpret_cast<bf16_t*>(p.C);
@@ -1123,7 +1144,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
                 const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp);
                 const f32x4 v1 = *reinterpret_cast<const f32x4*>(sp + 4);
                 if (row >= p.M || !col_ok) continue;
-                float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};  // (not slab_row8: the spread in front of the edge test changes the machine code)
                 const int64_t o = cz + p.cmap(row) * p.ldc + ccol;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = rbf(v[e] + bv[e]);  // same order and rounding points as epilogue8
@@ -1167,33 +1188,10 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
             bf16_t* pre_ = p.pre_out;
             const int64_t ldr_ = p.ldr, ldc_ = p.ldc;
             float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (has_bias && col_ok) {  // a lane's 8 columns are the same for all of its rows
-                if (p.bias_f32) {
-                    const f32x4 b0 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.bias) + ccol);
-                    const f32x4 b1 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.bias) + ccol + 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { bv[e] = b0[e]; bv[4 + e] = b1[e]; }
-                } else {
-                    const bf16x8 b = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16_t*>(p.bias) + ccol);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) bv[e] = bf2f(b[e]);
-                }
-            }
-            // destination of the lane's 8 columns (column routing resolved once: the columns do not change with the row)
-            bf16_t* cl = reinterpret_cast<bf16_t*>(p.C) + cz + ccol;
-            int64_t ldl = p.ldc;
-            if (p.nseg > 0) {  // (constant indices only: a run-time index would put the whole argument block into scratch)
-                cl = p.seg_dst[0] + (ccol - p.seg_begin[0]);
-                ldl = p.seg_ld[0];
-                if (p.nseg > 1 && ccol >= p.seg_begin[1]) {
-                    cl = p.seg_dst[1] + (ccol - p.seg_begin[1]);
-                    ldl = p.seg_ld[1];
-                }
-                if (p.nseg > 2 && ccol >= p.seg_begin[2]) {
-                    cl = p.seg_dst[2] + (ccol - p.seg_begin[2]);
-                    ldl = p.seg_ld[2];
-                }
-            }
+            if (has_bias && col_ok) load_bias8(p.bias, p.bias_f32, ccol, bv);  // a lane's 8 columns are the same for all of its rows
+            bf16_t* cl;  // destination of the lane's 8 columns
+            int64_t ldl;
+            route_cols8(p, ccol, cz, cl, ldl);
             const int rbase = row_base(h) + (lane >> 3);
             auto res_row = [&](int it) -> bf16x8 {
                 const int row = rbase + it * 8;
@@ -1205,12 +1203,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
                 return (accum && row < M_ && col_ok) ? *reinterpret_cast<const bf16x8*>(cl + (int64_t)row * ldl) : bf16x8{};
             };
             bf16x8 rnext = res_row(0), onext = old_row(0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) slab[(i * 16 + 4 * g + r) * 64 + j * 16 + l15] = acc[h * 4 + i][j][r];
+            acc_to_slab<AH>(slab, acc, h * AH, g, l15);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -1225,6 +1218,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
                     onext = old_row(it + 1);
                 }
                 if (row >= M_ || !col_ok) continue;
+                // (not slab_row8, and the row below stands once more in the persistent kernel: as one function it regroups the bf16 conversions of both kernels)
                 float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
                 if (has_bias) {
 #pragma unroll
@@ -1263,6 +1257,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void gemm_bf16_
             __builtin_amdgcn_wave_barrier();
             return;
         }
+        // (acc_to_slab's and slab_row8's statements in place: acc_to_slab called here flips branches in every tile kernel, slab_row8 changes the CT one)
 #pragma unroll
         for (int i = 0; i < AH; ++i)
 #pragma unroll
@@ -1538,10 +1533,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
         auto to_slab = [&](int ti) {  // MFMA row-tile ti of the wave's sub-tile (16 rows x 64 columns) -> slab
             __builtin_amdgcn_wave_barrier();
             // (static indexing of acc: callers pass compile-time ti through the unrolled loops below)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) slab[(4 * g + r) * 64 + j * 16 + l15] = acc[ti][j][r];
+            acc_to_slab<1>(slab, acc, ti, g, l15);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
         };
@@ -1555,21 +1547,13 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
                 to_slab(ti);
                 const int row = m0c + wm * 128 + ti * 16 + (lane >> 2);
                 const float* sp = slab + (lane >> 2) * 64 + (lane & 3) * 8;
-                const f32x4 g0 = *reinterpret_cast<const f32x4*>(sp), g1 = *reinterpret_cast<const f32x4*>(sp + 4);
-                const f32x4 u0 = *reinterpret_cast<const f32x4*>(sp + 32), u1 = *reinterpret_cast<const f32x4*>(sp + 36);
+                float gv[8], uv[8];
+                slab_row8(sp, gv);
+                slab_row8(sp + 32, uv);
                 bf16x8 hb = bf16x8{};
                 if (row < p.M && ocol_ok) {
-                    const float gv[8] = {g0[0], g0[1], g0[2], g0[3], g1[0], g1[1], g1[2], g1[3]};
-                    const float uv[8] = {u0[0], u0[1], u0[2], u0[3], u1[0], u1[1], u1[2], u1[3]};
                     bf16x8 gb, ub;
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) {
-                        const f32x2 gr = rbf2(f32x2{gv[e], gv[e + 1]}), ur = rbf2(f32x2{uv[e], uv[e + 1]});
-                        const f32x2 hv = rbf2(gelu_tanh2(gr)) * ur;
-                        gb[e] = f2bf(gr[0]); gb[e + 1] = f2bf(gr[1]);
-                        ub[e] = f2bf(ur[0]); ub[e + 1] = f2bf(ur[1]);
-                        hb[e] = f2bf(hv[0]); hb[e + 1] = f2bf(hv[1]);
-                    }
+                    geglu_pair8(gv, uv, gb, ub, hb);
                     const int64_t o = p.cmap(row) * p.ldc + ocol;
                     *reinterpret_cast<bf16x8*>(cb + o) = hb;
                     if (p.pre_out != nullptr) store_pre8(p.pre_out + o, gb, p.nt_pre);
@@ -1615,9 +1599,8 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
                     for (int it2 = 0; it2 < 2; ++it2) {
                         const int it = 2 * i + it2;
                         const int row = rbase + it * 8;
-                        const float* sp = slab + (it2 * 8 + (lane >> 3)) * 64 + (lane & 7) * 8;
-                        const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp), v1 = *reinterpret_cast<const f32x4*>(sp + 4);
-                        const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                        float v[8];
+                        slab_row8(slab + (it2 * 8 + (lane >> 3)) * 64 + (lane & 7) * 8, v);
                         if constexpr (CT) {  // act 3 with dgT / duT: the half's results stay in registers (where s0 / s1 were) for ct_round below
                             rdg[it] = bf16x8{};
                             rdu[it] = bf16x8{};
@@ -1632,7 +1615,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
                         if (row >= p.M || !col_ok) continue;
                         const int64_t o = p.cmap(row) * p.ldc + ccol;
                         bf16x8 ov;
-                        if (p.act == 2) {
+                        if (p.act == 2) {  // (as gemm_bf16_kernel's fused_fast row: see there why it stands twice)
                             if (p.pre_out != nullptr) {
                                 bf16x8 uv;
 #pragma unroll
@@ -1698,9 +1681,8 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
 #pragma unroll
                 for (int it2 = 0; it2 < 2; ++it2) {
                     const int row0 = m0c + wm * 128 + ti * 16 + it2 * 8, row = row0 + (lane >> 3);
-                    const float* sp = slab + (it2 * 8 + (lane >> 3)) * 64 + (lane & 7) * 8;
-                    const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp), v1 = *reinterpret_cast<const f32x4*>(sp + 4);
-                    const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                    float v[8];
+                    slab_row8(slab + (it2 * 8 + (lane >> 3)) * 64 + (lane & 7) * 8, v);
                     bf16x8 ov = bf16x8{};
                     if (row < p.M && col_ok) {
 #pragma unroll
@@ -1718,32 +1700,10 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
             bf16_t* pre_ = p.pre_out;
             const int64_t ldr_ = p.ldr, ldc_ = p.ldc;
             float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (has_bias && col_ok) {
-                if (p.bias_f32) {
-                    const f32x4 b0 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.bias) + ccol);
-                    const f32x4 b1 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.bias) + ccol + 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { bv[e] = b0[e]; bv[4 + e] = b1[e]; }
-                } else {
-                    const bf16x8 b = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16_t*>(p.bias) + ccol);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) bv[e] = bf2f(b[e]);
-                }
-            }
-            bf16_t* cl = reinterpret_cast<bf16_t*>(p.C) + ccol;
-            int64_t ldl = p.ldc;
-            if (p.nseg > 0) {  // (constant indices only: a run-time index would put the whole argument block into scratch)
-                cl = p.seg_dst[0] + (ccol - p.seg_begin[0]);
-                ldl = p.seg_ld[0];
-                if (p.nseg > 1 && ccol >= p.seg_begin[1]) {
-                    cl = p.seg_dst[1] + (ccol - p.seg_begin[1]);
-                    ldl = p.seg_ld[1];
-                }
-                if (p.nseg > 2 && ccol >= p.seg_begin[2]) {
-                    cl = p.seg_dst[2] + (ccol - p.seg_begin[2]);
-                    ldl = p.seg_ld[2];
-                }
-            }
+            if (has_bias && col_ok) load_bias8(p.bias, p.bias_f32, ccol, bv);
+            bf16_t* cl;
+            int64_t ldl;
+            route_cols8(p, ccol, 0, cl, ldl);
             const int rbase = m0c + wm * 128 + (lane >> 3);
             auto res_row = [&](int k) -> bf16x8 {  // k = 16-row pass * 2 + 8-row step
                 const int row = rbase + k * 8;
@@ -1762,16 +1722,15 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
                 for (int it2 = 0; it2 < 2; ++it2) {
                     const int k = ti * 2 + it2;
                     const int row = rbase + k * 8;
-                    const float* sp = slab + (it2 * 8 + (lane >> 3)) * 64 + (lane & 7) * 8;
-                    const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp), v1 = *reinterpret_cast<const f32x4*>(sp + 4);
+                    float v[8];
+                    slab_row8(slab + (it2 * 8 + (lane >> 3)) * 64 + (lane & 7) * 8, v);
                     const bf16x8 rv = rnext, ov0 = onext;
                     if (k + 1 < 2 * MT) {
                         rnext = res_row(k + 1);
                         onext = old_row(k + 1);
                     }
                     if (row >= M_ || !col_ok) continue;
-                    float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                    if (has_bias) {
+                    if (has_bias) {  // (as gemm_bf16_kernel's simple_fast row: see there why it stands twice)
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] += bv[e];
                     }
@@ -1814,9 +1773,8 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_persistent_kernel(const GemmAr
                     const int lr = it2 * 8 + (lane >> 3);
                     const int row = m0c + wm * 128 + ti * 16 + lr;
                     if (row >= p.M || !col_ok) continue;
-                    const float* sp = slab + lr * 64 + (lane & 7) * 8;
-                    const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp), v1 = *reinterpret_cast<const f32x4*>(sp + 4);
-                    float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                    float v[8];
+                    slab_row8(slab + lr * 64 + (lane & 7) * 8, v);
                     epilogue8(p, v, row, ccol, cz, rz, vz, p.C, p.out_f32 != 0);
                 }
             }
