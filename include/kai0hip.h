@@ -635,16 +635,22 @@ int kai0_denoise_glue_rows(const void* xs, const float* mod, int64_t mod_ld, int
 int kai0_linear_f32_rows(const float* x, int64_t ldx, const float* W, int64_t ldw, const float* bias, int M, int N, int K, int act,
                          float* out_f32, int64_t ldo_f32, void* out_bf16, int64_t ldo_bf16, int out_rpb, int64_t out_bs, int64_t out_off,
                          float* rowsq_out, int64_t rowsq_ld, kai0_stream_t stream);
-/* Real-time chunking (pi0_rtc.py:293-349): the two element-wise seams of a guided Euler step, around the vector-Jacobian product of
+/* Real-time chunking (pi0_rtc.py:293-349): the element-wise seams of a guided Euler step, around the vector-Jacobian product of
  * the denoiser that the engine runs as a reverse sweep over the backward entry points above.  All buffers f32 [rows][A], contiguous,
  * at any element (16-byte accesses where they all reach a 16-byte boundary at the same element, scalar head / tail / fallback
  * otherwise); every product and sum rounds to f32 on its own.
+ * kai0_rtc_overwrite (pi0_rtc.py:322-327, `mask_prefix_delay`: `overwrite = where(mask_time, prev_chunk[..., :provided_dim],
+ * x_t[..., :provided_dim])`) — the point the denoiser is evaluated and linearised at; a selection, bit-identical to torch.where:
+ *   out[r][c] = (row_mask[r % Hs] != 0 && c < provided) ? prev[r][c] : x[r][c];   row_mask f32 [Hs] (1 for rows below the inference
+ *   delay: data, not a launch constant);  out aliases neither input
  * kai0_rtc_error (:329-338, `x_1 = x_t - time * v_t; error = (prev_chunk - x_1) * weights[None, :, None] * dim_mask`):
  *   err_out[r][c] = ((prev[r][c] - (x[r][c] - t * v[r][c])) * w_row[r % Hs]) * (c < provided ? 1 : 0);   w_row f32 [Hs]
  * kai0_rtc_update (:335-349: the x_t half of the VJP of x_1, `v_t = v_local - guidance_weight * pinv_correction`, nan_to_num, the
  * Euler update), with jte = (dv/dx_t)^T err from the sweep:
  *   corr = err - t * jte;  v' = v - g * corr;  v' = 0 where it is not finite;  x = x + dt * v'   (in place)
  * With err = jte = 0 and a finite v that is kai0_euler_step, bit for bit. */
+int kai0_rtc_overwrite(const float* x, const float* prev, const float* row_mask, int provided, float* out, int64_t rows, int Hs, int A,
+                       kai0_stream_t stream);
 int kai0_rtc_error(const float* x, const float* v, const float* prev, const float* w_row, int provided, float t, float* err_out,
                    int64_t rows, int Hs, int A, kai0_stream_t stream);
 int kai0_rtc_update(float* x, const float* v, const float* err, const float* jte, float t, float g, float dt, int64_t rows, int A,

@@ -200,6 +200,7 @@ _PROTOS: dict[str, list] = {
     "kai0_denoise_glue": [c_p, c_p, c_i64, c_i, c_f, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_i64, c_i, c_i, c_p, c_p],
     "kai0_denoise_glue_rows": [c_p, c_p, c_i64, c_i, c_f, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_i64, c_i, c_i, c_p, c_i, c_i64, c_i64, c_p],
     "kai0_linear_f32_rows": [c_p, c_i64, c_p, c_i64, c_p, c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_i64, c_i, c_i64, c_i64, c_p, c_i64, c_p],
+    "kai0_rtc_overwrite": [c_p, c_p, c_p, c_i, c_p, c_i64, c_i, c_i, c_p],
     "kai0_rtc_error": [c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_i64, c_i, c_i, c_p],
     "kai0_rtc_update": [c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_i64, c_i, c_p],
     "kai0_sumsq": [c_p, c_i, c_i64, c_p, c_p, c_p],

@@ -1,6 +1,7 @@
-// rtc.hip — the two f32 seams around the denoiser's vector-Jacobian product in a guided (real-time chunking) Euler step
-// (pi0_rtc.py:329-349; kai0hip.h kai0_rtc_error / kai0_rtc_update).  Between them the engine runs the reverse sweep over the existing
-// backward entry points (infer.py `_denoiser_vjp`); these kernels hold the step's element-wise arithmetic:
+// rtc.hip — the f32 seams around the denoiser's vector-Jacobian product in a guided (real-time chunking) Euler step
+// (pi0_rtc.py:322-349; kai0hip.h kai0_rtc_overwrite / kai0_rtc_error / kai0_rtc_update).  Between them the engine runs the reverse sweep
+// over the existing backward entry points (infer.py `_denoiser_vjp`); these kernels hold the step's element-wise arithmetic:
+//     overwrite (mask_prefix_delay): x_den = (row_mask[row % Hs] != 0 && col < provided) ? prev : x
 //     error : x1 = x - t v;  e = ((prev - x1) * w[row % Hs]) * (col < provided ? 1 : 0)
 //     update: corr = e - t jte;  v' = v - g corr;  v' = finite(v') ? v' : 0;  x = x + dt v'
 // Every product and sum is rounded to f32 on its own (the library is built with -ffp-contract=off), so both can be restated with
@@ -79,6 +80,43 @@ __global__ __launch_bounds__(256) void rtc_update_kernel(const RtcUpdArgs p) {
     for (int64_t i = p.head + 4 * n4 + tid; i < p.n; i += stride) p.x[i] = rtc_update_one(p, p.x[i], p.v[i], p.err[i], p.jte[i]);
 }
 
+struct RtcOvwArgs {
+    const float* x;
+    const float* prev;
+    const float* row_mask;
+    float* out;
+    int64_t n, head;
+    int Hs, A, provided;
+};
+
+// a selection, no arithmetic: torch.where(mask, prev, x) bit for bit (NaN payloads and signed zeros included)
+__device__ __forceinline__ float rtc_overwrite_one(const RtcOvwArgs& p, int64_t i, float x, float prev) {
+    const int64_t row = i / p.A;
+    const int col = (int)(i - row * p.A);
+    // on the bit patterns: sel = all ones where prev is taken (a row of the mask is taken when it is not +-0).  Branch-free on purpose:
+    // with `(col < provided && mask != 0.0f) ? prev : x` here, the 4-wide body of rtc_overwrite_kernel (not its scalar loops) came out
+    // of hipcc -O3 for gfx950 with the move that puts x back dropped, so every row was overwritten — the listing and how to make it
+    // again: profiles/rtc_overwrite_short_circuit_isa.txt; the d = 0 and d = 1 cases of tests/test_rtc_pi0_gpu.py are what showed it
+    const uint32_t m = __builtin_bit_cast(uint32_t, p.row_mask[row % p.Hs]) & 0x7fffffffu;
+    const uint32_t sel = (col < p.provided && m != 0u) ? 0xffffffffu : 0u;
+    return __builtin_bit_cast(float, (__builtin_bit_cast(uint32_t, prev) & sel) | (__builtin_bit_cast(uint32_t, x) & ~sel));
+}
+
+__global__ __launch_bounds__(256) void rtc_overwrite_kernel(const RtcOvwArgs p) {
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    const int64_t n4 = (p.n - p.head) >> 2;
+    for (int64_t j = tid; j < n4; j += stride) {
+        const int64_t i = p.head + 4 * j;
+        const f32x4 x = *reinterpret_cast<const f32x4*>(p.x + i), pr = *reinterpret_cast<const f32x4*>(p.prev + i);
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = rtc_overwrite_one(p, i + k, x[k], pr[k]);
+        *reinterpret_cast<f32x4*>(p.out + i) = o;
+    }
+    for (int64_t i = tid; i < p.head; i += stride) p.out[i] = rtc_overwrite_one(p, i, p.x[i], p.prev[i]);
+    for (int64_t i = p.head + 4 * n4 + tid; i < p.n; i += stride) p.out[i] = rtc_overwrite_one(p, i, p.x[i], p.prev[i]);
+}
+
 // elements in front of the first 16-byte boundary of `lead` if every other buffer reaches one at the same element, else n (all scalar)
 template <int N>
 int64_t common_head(const void* lead, const void* const (&others)[N], int64_t n) {
@@ -99,6 +137,23 @@ int rtc_grid(int64_t n, int64_t head) {
 }
 
 }  // namespace
+
+KAI0_API int kai0_rtc_overwrite(const float* x, const float* prev, const float* row_mask, int provided, float* out, int64_t rows, int Hs,
+                                int A, kai0_stream_t stream) {
+    KAI0_REQUIRE(rows >= 0 && Hs > 0 && A > 0 && provided >= 0, "kai0_rtc_overwrite: rows=%lld Hs=%d A=%d provided=%d", (long long)rows, Hs,
+                 A, provided);
+    if (rows == 0) return 0;
+    KAI0_REQUIRE(x && prev && row_mask && out, "kai0_rtc_overwrite: null buffer");
+    KAI0_REQUIRE(out != x && out != prev, "kai0_rtc_overwrite: out must not alias an input");
+    KAI0_REQUIRE((((uintptr_t)x | (uintptr_t)prev | (uintptr_t)row_mask | (uintptr_t)out) & 3) == 0,
+                 "kai0_rtc_overwrite: a buffer is not aligned to its element size");
+    const int64_t n = rows * A;
+    const void* const others[] = {prev, out};
+    const int64_t head = common_head(x, others, n);
+    const RtcOvwArgs a{x, prev, row_mask, out, n, head, Hs, A, provided};
+    hipLaunchKernelGGL(rtc_overwrite_kernel, dim3(rtc_grid(n, head)), dim3(256), 0, (hipStream_t)stream, a);
+    return kai0_check_launch("kai0_rtc_overwrite");
+}
 
 KAI0_API int kai0_rtc_error(const float* x, const float* v, const float* prev, const float* w_row, int provided, float t, float* err_out,
                             int64_t rows, int Hs, int A, kai0_stream_t stream) {

@@ -26,6 +26,9 @@ MI355X-first choices:
   * real-time chunking: a request with a previous chunk runs the guided loop `_run_guided` — per Euler step one
     forward of the generic per-layer step that keeps what its backward needs, an explicit reverse sweep over the training backward's
     entry points (`_denoiser_vjp`) and two f32 seam kernels — captured into a hipGraph of its own; the unguided graph is not touched.
+    Both variants: pi0's sweep carries all Hs + 1 suffix rows per sample, its plain norms as the constant modulation [w | 0 | 1], and ends
+    behind the first layer in the suffix embedding's f32 Linears and SiLU.  `mask_prefix_delay` evaluates and linearises the denoiser at
+    x_t with the delay rows overwritten by the previous chunk (kai0_rtc_overwrite) and updates the original x_t.
 """
 
 from __future__ import annotations
@@ -126,7 +129,7 @@ class InferenceEngine:
         self._cap = self._graph_steps = None  # the captured chunk (`_Capture`) and the step count baked into it
         # real-time chunking: the guided chunk's own capture, its key, and the previous chunk / prefix weights it reads
         self._g_cap = self._g_graph_key = None
-        self._g_prev = self._g_w = None
+        self._g_prev = self._g_w = self._g_delay = None
         self._content_init()
 
     # what tests, tools and the benchmark read of the captures
@@ -134,6 +137,14 @@ class InferenceEngine:
     _static_in = property(lambda self: self._cap.inputs if self._cap else None)
     _static_out = property(lambda self: self._cap.out if self._cap else None)
     _g_graph = property(lambda self: self._g_cap.graph if self._g_cap else None)
+
+    @staticmethod
+    def require_hip(device, what: str) -> None:
+        """The guided sampler exists as HIP launches only — the taped step, the reverse sweep and the seams have no CPU form, and nothing
+        falls back to eager torch: a model that is not on a HIP device is refused here, before any engine is built (the request's
+        arguments have been validated by then: a bad one is a ValueError on any device)."""
+        if torch.device(device).type != "cuda":
+            raise NotImplementedError(f"{what} runs on the HIP engine only; the model's parameters are on `{device}`")
 
     def compatible(self, batch, n_lang, n_cam):
         return self.shape_matches(batch, n_lang, n_cam) and self.weights_unchanged()
@@ -492,13 +503,25 @@ class InferenceEngine:
         return sch
 
     def _guided_schedule(self, times: list[float]):
-        """`mods` / `mf` of a schedule for the guided loop, which runs the generic per-layer step on every engine: contiguous
-        [steps B, 3 De] modulation rows per norm (the production stack keeps them as column slices of one table)."""
+        """`mods` / `mf` of a schedule for the guided loop, which runs the generic per-layer step on every engine.  pi0.5: contiguous
+        [steps B, 3 De] modulation rows per norm (the production stack keeps them as column slices of one table).  pi0: the schedule's
+        `tvec` / `w_act`, and per norm the constant modulation rows [scale = w | shift = 0 | gate = 1] as f32 [B, 3 De] — the plain
+        RMSNorm as adaRMS arithmetic (`_build_fast`), which hands the taped forward its rstd and the sweep its norm backward."""
         sch = self._schedule(times)
-        if not self.fast:
+        if self.pi05 and not self.fast:
             return sch
         if sch.guided is None:
-            sch.guided = SimpleNamespace(mods=[(a.contiguous(), b.contiguous()) for a, b in sch.mods], mf=sch.mf.contiguous())
+            if self.pi05:
+                sch.guided = SimpleNamespace(mods=[(a.contiguous(), b.contiguous()) for a, b in sch.mods], mf=sch.mf.contiguous())
+            else:
+                ex, De, dev = self.pe.gemma_expert.model, self.De, self.dev
+
+                def const_rows(ln):
+                    row = torch.cat([ln.weight.float(), torch.zeros(De, dtype=F32, device=dev), torch.ones(De, dtype=F32, device=dev)])
+                    return row.reshape(1, 3 * De).repeat(self.B, 1).contiguous()
+
+                sch.guided = SimpleNamespace(mods=[(const_rows(l.input_layernorm), const_rows(l.post_attention_layernorm)) for l in ex.layers],
+                                             mf=const_rows(ex.norm), tvec=sch.tvec, w_act=sch.w_act)  # fmt: skip
         return sch.guided
 
     def _modulations(self, tt, n: int):
@@ -613,13 +636,24 @@ class InferenceEngine:
 
     def _pi0_suffix_embed(self, x_t, step: int, sch, xs):
         """pi0 embed_suffix of one denoise step (pi0_pytorch.py:263-285) into the action rows 1 .. Hs of every sample's Hs + 1 suffix rows
-        `xs` (row 0, the state token, is constant for a request: `_run` writes it once): action_in_proj, the action half of
-        action_time_mlp_in + the step's hoisted time vector, SiLU, action_time_mlp_out — f32, one bf16 rounding at the store."""
+        `xs` (row 0, the state token, is constant for a request: `_pi0_state_rows` writes it once): action_in_proj, the action half of
+        action_time_mlp_in + the step's hoisted time vector, SiLU, action_time_mlp_out — f32, one bf16 rounding at the store.
+        Returns the SiLU's input f32 [B Hs, De] (what a guided step's reverse sweep keeps)."""
         model, B, Hs, De = self.model, self.B, self.Hs, self.De
         a = ops.linear_f32(x_t.view(B * Hs, self.A), model.action_in_proj.weight, model.action_in_proj.bias)
-        h = ops.silu_f32(ops.linear_f32(a, sch.w_act, sch.tvec[step].contiguous()))
-        y = ops.linear_f32(h, model.action_time_mlp_out.weight, model.action_time_mlp_out.bias)
+        pre = ops.linear_f32(a, sch.w_act, sch.tvec[step].contiguous())
+        y = ops.linear_f32(ops.silu_f32(pre), model.action_time_mlp_out.weight, model.action_time_mlp_out.bias)
         ops._copy_rows(ops.cast(y, BF16), xs, B, Hs, De, Hs * De, 0, De, self.Ss * De, 1, De)
+        return pre
+
+    def _pi0_state_rows(self, state):
+        """pi0's suffix rows bf16 [B (Hs + 1), De] of one request with row 0 of every sample, the state token bf16(state_proj(state)),
+        written: constant over the Euler steps (rows 1 .. Hs: `_pi0_suffix_embed`, every step)."""
+        model, B, De = self.model, self.B, self.De
+        xs = torch.empty((B * self.Ss, De), dtype=BF16, device=self.dev)
+        s = ops.linear_f32(state.to(F32).contiguous(), model.state_proj.weight, model.state_proj.bias)
+        ops._copy_rows(ops.cast(s, BF16), xs, B, 1, De, De, 0, De, self.Ss * De, 0, De)
+        return xs
 
     def _adarms(self, xs, mod, eps: float):
         """kai0_adarms_fwd -> (y, gate bf16 [B, De], rstd f32 [rows]); `rstd` is what the guided step's reverse sweep reads."""
@@ -639,29 +673,36 @@ class InferenceEngine:
           pi0:   Hs + 1 rows per sample in the request's `xs` (row 0, the state token, written once by `_run` and recomputed through the
                  layers every step, as the reference does; rows 1 .. Hs by `_pi0_suffix_embed`); plain RMSNorms, no gates;
                  action_out_proj reads the last Hs rows.
-        `tape` (a guided step, `_denoiser_vjp`; pi0.5 only): the same launches, and what the reverse sweep needs is kept and appended per
-        layer — the inputs of both norms with their rstd, the gates, g / u, the attention's rotated query rows, output rows and
-        probabilities; the final norm's input and rstd come last."""
+        `tape` (a guided step, `_denoiser_vjp`): the same launches, and what the reverse sweep needs is kept and appended per layer — the
+        inputs of both norms with their rstd, the gates, g / u, the attention's rotated query rows, output rows and probabilities (all
+        suffix rows of a sample); the final norm's input and rstd come last, with pi0's SiLU input `pre`.  pi0's plain norms then run
+        as kai0_adarms_fwd over the constant modulation rows of `_guided_schedule` (the same arithmetic — x_hat (1 + w) + 0.0 — and it
+        returns the rstd that kai0_rmsnorm's wrapper keeps to itself): `sch` must be that record."""
         model, ex = self.model, self.pe.gemma_expert.model
         B, P, Hs, Ss, De = self.B, self.P, self.Hs, self.Ss, self.De
         H, HD, S_ld = self.H, self.HD, self.S_ld
         NQ = H * HD
         ada = self.pi05
+        taped = tape is not None
         inv_freq = self._inv_freq
         rows = slice(step * B, (step + 1) * B)
+        pre = None
         if ada:
             a = ops.linear_f32(x_t.view(B * Hs, self.A), model.action_in_proj.weight, model.action_in_proj.bias)
             xs = ops.cast(a, BF16)
         else:
-            self._pi0_suffix_embed(x_t, step, sch, xs)
+            pre = self._pi0_suffix_embed(x_t, step, sch, xs)
 
         def norm(x, ln, mod):  # -> (y, gate | None, rstd | None)
             if ada:
                 return self._adarms(x, mod[rows], ln.eps)
+            if taped:
+                y, _, rstd = self._adarms(x, mod, ln.eps)
+                return y, None, rstd
             return ops.rmsnorm(x, ln.weight, ln.eps), None, None
 
         for l, layer in enumerate(ex.layers):
-            m1, m2 = sch.mods[l] if ada else (None, None)
+            m1, m2 = sch.mods[l] if ada or taped else (None, None)
             x_in = xs
             hs, gate1, rstd1 = norm(xs, layer.input_layernorm, m1)
             at = layer.self_attn
@@ -671,11 +712,11 @@ class InferenceEngine:
             ops.rope_(self.q_buf, self.pos_suffix, inv_freq, B, Ss, S_ld, P, H, HD)
             ops.rope_(self.k_cache[l], self.pos_suffix, inv_freq, B, Ss, S_ld, P, 1, HD)
             probs = self._attend(l, P, Ss, P + Ss, self.qcode, self.kcode, want_probs=tape is not None)
-            if tape is not None:  # q_buf / att_buf are shared by the layers: this layer's suffix rows, compact [B Hs, H HD]
-                q_rows = torch.empty((B * Hs, NQ), dtype=BF16, device=self.dev)
-                att_rows = torch.empty((B * Hs, NQ), dtype=BF16, device=self.dev)
-                ops._copy_rows(self.q_buf, q_rows, B, Hs, NQ, S_ld * NQ, P, NQ, Hs * NQ, 0, NQ)
-                ops._copy_rows(self.att_buf, att_rows, B, Hs, NQ, S_ld * NQ, P, NQ, Hs * NQ, 0, NQ)
+            if tape is not None:  # q_buf / att_buf are shared by the layers: this layer's suffix rows, compact [B Ss, H HD]
+                q_rows = torch.empty((B * Ss, NQ), dtype=BF16, device=self.dev)
+                att_rows = torch.empty((B * Ss, NQ), dtype=BF16, device=self.dev)
+                ops._copy_rows(self.q_buf, q_rows, B, Ss, NQ, S_ld * NQ, P, NQ, Ss * NQ, 0, NQ)
+                ops._copy_rows(self.att_buf, att_rows, B, Ss, NQ, S_ld * NQ, P, NQ, Ss * NQ, 0, NQ)
             xs = self._oproj(at.o_proj, Ss, P, residual=xs, gate=gate1)
             x_mid = xs
             hs, gate2, rstd2 = norm(xs, layer.post_attention_layernorm, m2)
@@ -686,9 +727,9 @@ class InferenceEngine:
             xs = ops.linear_fwd(h, layer.mlp.down_proj.weight, residual=xs, gate=gate2, gate_rpb=Hs if ada else 0)
             if tape is not None:
                 tape.append((x_in, rstd1, gate1, q_rows, att_rows, probs, x_mid, rstd2, gate2, g, u))
-        out, _, rstd_f = norm(xs, ex.norm, sch.mf)
+        out, _, rstd_f = norm(xs, ex.norm, sch.mf if ada or taped else None)
         if tape is not None:
-            tape.append((xs, rstd_f))
+            tape.append((xs, rstd_f, pre))
         if Ss != Hs:  # pi0: the action rows of every sample, compact
             act = torch.empty((B * Hs, De), dtype=BF16, device=self.dev)
             ops._copy_rows(out, act, B, Hs, De, Ss * De, Ss - Hs, De, Hs * De, 0, De)
@@ -702,7 +743,7 @@ class InferenceEngine:
         a_map: dy's rows addressed through kai0_gemm_desc's row remap."""
         # (not ops.dgrad: this is the NN form inside a captured graph, and must never start transposing weights at 4096 rows)
         N, K = w.shape
-        M = self.B * self.Hs
+        M = self.B * self.Ss
         if into is None:
             dx = torch.empty((M, K), dtype=BF16, device=self.dev)
             gemm(dy, w, dx, M=M, N=K, K=N, a_kc=True, b_kc=False, lda=N, ldb=K, ldc=K, a_map=a_map, split_k=pick_split_k(M, K, N))
@@ -730,57 +771,85 @@ class InferenceEngine:
                   D, ops._stream())  # fmt: skip
         return dy
 
-    def _denoiser_vjp(self, cot, tape, step: int, mods, mf):
-        """(dv / dx_t)^T cot for the step `_denoise_step(..., tape)` just ran: cot f32 [B Hs, A] -> f32 [B Hs, A].  An explicit reverse sweep
-        over the C entry points of the training backward (the arithmetic and rounding points of autograd over the bf16 model), called
-        directly: not through the autograd shims, which would write weight gradients into a trainer's buffers (ops._grad_dst).  Only the
-        path x_t -> v is differentiated; weights, modulations and the prefix K / V are constants.  Attention: dS and dQ for the Hs H
-        folded suffix rows against all P + Hs keys in one launch (kai0_attn_bwd_dq over the stored probabilities), dK / dV for the
-        suffix key rows only, as two TN GEMMs over the key columns [P, P + Hs) of dS and P (widened to 16-byte boundaries)."""
+    def _denoiser_vjp(self, cot, tape, step: int, sch):
+        """(dv / dx_t)^T cot for the step `_denoise_step(..., tape)` just ran: cot f32 [B Hs, A] -> f32 [B Hs, A]; sch: the record of
+        `_guided_schedule`.  An explicit reverse sweep over the C entry points of the training backward (the arithmetic and rounding
+        points of autograd over the bf16 model), called directly: not through the autograd shims, which would write weight gradients
+        into a trainer's buffers (ops._grad_dst).  Only the path x_t -> v is differentiated; weights, modulations, the time vectors and
+        the prefix K / V are constants.  Attention: dS and dQ for the Ss H folded suffix rows against all P + Ss keys in one launch
+        (kai0_attn_bwd_dq over the stored probabilities), dK / dV for the suffix key rows only, as two TN GEMMs over the key columns
+        [P, P + Ss) of dS and P (widened to 16-byte boundaries).
+        pi0: the sweep carries all Ss = Hs + 1 rows of a sample.  The state row's cotangent starts at zero (action_out_proj reads the
+        action rows), picks up the state KEY's dK / dV — column P of the window, which therefore starts where pi0.5's does — and is
+        never read: every launch but the attention is row-wise, and the state query (mask code 1) has probability exactly 0 on the
+        action keys [P + 1, P + Ss), so nothing of that row reaches an action row's dK / dV / dQ.  The norms' backward takes the
+        constant modulation rows, the ungated residuals hand their cotangent on unchanged, and behind the first layer the suffix
+        embedding is undone in exact f32: action_time_mlp_out^T, silu'(pre), the action half of action_time_mlp_in^T, action_in_proj^T
+        (the time half and the biases take no gradient)."""
         model = self.model
-        B, P, Hs, De, A = self.B, self.P, self.Hs, self.De, self.A
+        B, P, Hs, Ss, De, A = self.B, self.P, self.Hs, self.Ss, self.De, self.A
         H, HD, S_ld = self.H, self.HD, self.S_ld
-        NQ, M, R = H * HD, B * Hs, Hs * H
+        NQ, M, R = H * HD, B * Ss, Ss * H
         dev = self.dev
+        ada = self.pi05
         rows = slice(step * B, (step + 1) * B)
+        mods = [(a[rows], b[rows]) for a, b in sch.mods] if ada else sch.mods
+        mf = sch.mf[rows] if ada else sch.mf
         layers = self.pe.gemma_expert.model.layers
         # action_out_proj^T: d(out32)[m, k] = sum_a cot[m, a] w_out[a, k]; the f32 <- bf16 cast hands its gradient on rounded to bf16
-        d32 = torch.empty((M, De), dtype=F32, device=dev)
-        ops.gemm_f32(cot, A, 1, model.action_out_proj.weight, De, 1, d32, M, De, A)
-        x_last, rstd_f = tape[-1]
-        dxs = self._adarms_bwd(ops.cast(d32, BF16), x_last, mf[rows], rstd_f, None)
+        d32 = torch.empty((B * Hs, De), dtype=F32, device=dev)
+        ops.gemm_f32(cot, A, 1, model.action_out_proj.weight, De, 1, d32, B * Hs, De, A)
+        dout = ops.cast(d32, BF16)
+        if Ss != Hs:  # pi0: action_out_proj read the last Hs rows of every sample; the state row's output has no reader
+            act = dout
+            dout = torch.zeros((M, De), dtype=BF16, device=dev)
+            ops._copy_rows(act, dout, B, Hs, De, Hs * De, 0, De, Ss * De, Ss - Hs, De)
+        x_last, rstd_f, pre = tape[-1]
+        dxs = self._adarms_bwd(dout, x_last, mf, rstd_f, None)
         c0 = P // 8 * 8  # the suffix key columns, from a 16-byte boundary of the probability rows
-        kw, koff = round_up(P + Hs - c0, 8), P - c0
+        kw, koff = round_up(P + Ss - c0, 8), P - c0
         for l in range(len(layers) - 1, -1, -1):
             layer = layers[l]
             x_in, rstd1, gate1, q_rows, att_rows, probs, x_mid, rstd2, gate2, g, u = tape[l]
             at, mlp = layer.self_attn, layer.mlp
-            # xs = x_mid + down(geglu(gate(hs2), up(hs2))) * gate2,  hs2 = adaRMS(x_mid, m2)
-            dh = self._dgrad(self._gated_bwd(dxs, gate2), mlp.down_proj.weight)
+            # xs = x_mid + down(geglu(gate(hs2), up(hs2))) * gate2,  hs2 = adaRMS(x_mid, m2)   (pi0: no gate)
+            dh = self._dgrad(self._gated_bwd(dxs, gate2) if ada else dxs, mlp.down_proj.weight)
             dg, du = torch.empty_like(g), torch.empty_like(u)
             _lib.call("kai0_geglu_bwd", dh.data_ptr(), g.data_ptr(), u.data_ptr(), dg.data_ptr(), du.data_ptr(), g.numel(), ops._stream())
             dhs = self._dgrad(du, mlp.up_proj.weight, into=self._dgrad(dg, mlp.gate_proj.weight))
-            dxs = self._adarms_bwd(dhs, x_mid, mods[l][1][rows], rstd2, dxs)
+            dxs = self._adarms_bwd(dhs, x_mid, mods[l][1], rstd2, dxs)
             # x_mid = x_in + o_proj(attention(q, k, v)) * gate1,  q | k | v = rope(proj(adaRMS(x_in, m1)))
-            datt = self._dgrad(self._gated_bwd(dxs, gate1), at.o_proj.weight)
+            datt = self._dgrad(self._gated_bwd(dxs, gate1) if ada else dxs, at.o_proj.weight)
             dS = torch.empty_like(probs)
             dq = torch.empty((M, NQ), dtype=BF16, device=dev)
             _lib.call("kai0_attn_bwd_dq", datt.data_ptr(), att_rows.data_ptr(), probs.data_ptr(), self.k_cache[l].data_ptr(),
-                      self.v_cache[l].data_ptr(), dS.data_ptr(), dq.data_ptr(), B, R, P + Hs, HD, HD, HD, HD, S_ld, R * HD, S_ld * HD,
+                      self.v_cache[l].data_ptr(), dS.data_ptr(), dq.data_ptr(), B, R, P + Ss, HD, HD, HD, HD, S_ld, R * HD, S_ld * HD,
                       S_ld * HD, R * S_ld, HD**-0.5, ops._stream())  # fmt: skip
             dkv = torch.empty((2, B, kw, HD), dtype=BF16, device=dev)
             for dst, a_t, b_t in ((dkv[0], dS, q_rows), (dkv[1], probs, datt)):  # dK = dS^T Q, dV = P^T dO over the suffix key columns
                 gemm(a_t, b_t, dst, M=kw, N=HD, K=R, a_kc=False, b_kc=False, lda=S_ld, ldb=HD, ldc=HD, batch=B, sA=(R * S_ld, 0),
                      sB=(R * HD, 0), sC=(kw * HD, 0), a_off_elems=c0)
-            ops.rope_(dq, self.pos_suffix, self._inv_freq, B, Hs, Hs, 0, H, HD, inverse=True)
-            ops.rope_(dkv[0], self.pos_suffix, self._inv_freq, B, Hs, kw, koff, 1, HD, inverse=True)
+            ops.rope_(dq, self.pos_suffix, self._inv_freq, B, Ss, Ss, 0, H, HD, inverse=True)
+            ops.rope_(dkv[0], self.pos_suffix, self._inv_freq, B, Ss, kw, koff, 1, HD, inverse=True)
             dhs = self._dgrad(dq, at.q_proj.weight)
-            self._dgrad(dkv[0], at.k_proj.weight, a_map=(Hs, kw, koff), into=dhs)
-            self._dgrad(dkv[1], at.v_proj.weight, a_map=(Hs, kw, koff), into=dhs)
-            dxs = self._adarms_bwd(dhs, x_in, mods[l][0][rows], rstd1, dxs)
-        # xs = bf16(action_in_proj(x_t)): action_in_proj^T of the gradient as f32
-        jte = torch.empty((M, A), dtype=F32, device=dev)
-        ops.gemm_f32(ops.cast(dxs, F32), De, 1, model.action_in_proj.weight, A, 1, jte, M, A, De)
+            self._dgrad(dkv[0], at.k_proj.weight, a_map=(Ss, kw, koff), into=dhs)
+            self._dgrad(dkv[1], at.v_proj.weight, a_map=(Ss, kw, koff), into=dhs)
+            dxs = self._adarms_bwd(dhs, x_in, mods[l][0], rstd1, dxs)
+        jte = torch.empty((B * Hs, A), dtype=F32, device=dev)
+        if ada:  # xs = bf16(action_in_proj(x_t)): action_in_proj^T of the gradient as f32
+            ops.gemm_f32(ops.cast(dxs, F32), De, 1, model.action_in_proj.weight, A, 1, jte, M, A, De)
+            return jte
+        # pi0: rows 1 .. Hs of xs = bf16(y),  y = W_out silu(pre) + b_out,  pre = w_act a + tvec[step],  a = action_in_proj(x_t)
+        Ma = B * Hs
+        dy = torch.empty((Ma, De), dtype=BF16, device=dev)
+        ops._copy_rows(dxs, dy, B, Hs, De, Ss * De, Ss - Hs, De, Hs * De, 0, De)
+        dh = torch.empty((Ma, De), dtype=F32, device=dev)
+        ops.gemm_f32(ops.cast(dy, F32), De, 1, model.action_time_mlp_out.weight, De, 1, dh, Ma, De, De)
+        dpre = torch.empty_like(dh)
+        _lib.call("kai0_silu_bwd_f32", dh.data_ptr(), pre.data_ptr(), dpre.data_ptr(), dh.numel(), ops._stream())
+        da = torch.empty_like(dh)
+        ops.gemm_f32(dpre, De, 1, sch.w_act, De, 1, da, Ma, De, De)
+        ops.gemm_f32(da, De, 1, model.action_in_proj.weight, A, 1, jte, Ma, A, De)
         return jte
 
     def _seams_pi05(self, x2, sch, rope, n: int, dt: float):
@@ -839,7 +908,7 @@ class InferenceEngine:
         sch = self._schedule(times)
         x_t = noise.clone().contiguous()
         self._prefix_pass(images, img_masks, lang_tokens, lang_masks)
-        model, B, P, HD, S_ld, De = self.model, self.B, self.P, self.HD, self.S_ld, self.De
+        B, P, HD, S_ld = self.B, self.P, self.HD, self.S_ld
         if self.fast:
             rope = ops.rope_table(self.pos_suffix, self._inv_freq)
             # prefix value rows of every layer -> transposed cache, one launch
@@ -851,22 +920,22 @@ class InferenceEngine:
             else:
                 self._seams_pi0(x2, sch, rope, len(times), dt, state)
         else:
-            xs = None
-            if not self.pi05:  # the state token, row 0 of every sample's suffix rows: constant over the steps
-                xs = torch.empty((B * self.Ss, De), dtype=BF16, device=self.dev)
-                s = ops.linear_f32(state.to(F32).contiguous(), model.state_proj.weight, model.state_proj.bias)
-                ops._copy_rows(ops.cast(s, BF16), xs, B, 1, De, De, 0, De, self.Ss * De, 0, De)
+            xs = None if self.pi05 else self._pi0_state_rows(state)  # the state token, row 0 of every sample's suffix rows
             for step in range(len(times)):
                 v_t = self._denoise_step(x_t, step, sch, xs)
                 ops.euler_step_(x_t, v_t, dt)
         self._content_stamp()
         return x_t
 
-    def _run_guided(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, max_guidance_weight: float, provided: int):
-        """A real-time-chunking chunk (pi0_rtc.py:293-349; kai0_amd/rtc.py): the prefix pass and the modulation tables of `_run`, then per
+    def _run_guided(self, images, img_masks, lang_tokens, lang_masks, noise, num_steps: int, max_guidance_weight: float, provided: int,
+                    mask_delay: bool = False, state=None):  # fmt: skip
+        """A real-time-chunking chunk (pi0_rtc.py:293-349; kai0_amd/rtc.py): the prefix pass and the schedule record of `_run`, then per
         Euler step ONE forward of the generic per-layer step that keeps what its reverse sweep needs (the linearisation point),
         kai0_rtc_error, the sweep `_denoiser_vjp`, kai0_rtc_update.  One stream; t, the guidance weight and dt are launch constants;
-        the previous chunk and the prefix weights are read from the engine's static buffers `_g_prev` / `_g_w`."""
+        the previous chunk, the prefix weights and the delay rows are read from the engine's static buffers `_g_prev` / `_g_w` /
+        `_g_delay`.  mask_delay (`mask_prefix_delay`, :322-327): the denoiser is evaluated and linearised at x_t with the delay rows'
+        provided columns overwritten by the previous chunk (kai0_rtc_overwrite), the error is taken there, and the update goes to the
+        original x_t."""
         from . import rtc
 
         times = euler_times(num_steps)
@@ -875,57 +944,68 @@ class InferenceEngine:
         gws = rtc.guidance_weights(times, max_guidance_weight)
         x_t = noise.clone().contiguous()
         self._prefix_pass(images, img_masks, lang_tokens, lang_masks)
+        xs = None if self.pi05 else self._pi0_state_rows(state)
         M = self.B * self.Hs
         for step, (t, g) in enumerate(zip(times, gws, strict=True)):
             tape = []
-            v_t = self._denoise_step(x_t, step, sch, tape=tape)
-            err = ops.rtc_error(x_t, v_t, self._g_prev, self._g_w, provided, t)
-            jte = self._denoiser_vjp(err.view(M, self.A), tape, step, sch.mods, sch.mf)
+            x_den = ops.rtc_overwrite(x_t, self._g_prev, self._g_delay, provided) if mask_delay else x_t
+            v_t = self._denoise_step(x_den, step, sch, xs, tape=tape)
+            err = ops.rtc_error(x_den, v_t, self._g_prev, self._g_w, provided, t)
+            jte = self._denoiser_vjp(err.view(M, self.A), tape, step, sch)
             ops.rtc_update_(x_t, v_t, err, jte, t, g, dt)
         self._content_stamp()
         return x_t
 
     @torch.no_grad()
-    def denoiser_vjp(self, images, img_masks, lang_tokens, lang_masks, x_t, cotangent, num_steps: int, step: int):
+    def denoiser_vjp(self, images, img_masks, lang_tokens, lang_masks, x_t, cotangent, num_steps: int, step: int, state=None):
         """The guided loop's primitive on its own (tests, tools): the prefix pass, then at `x_t` and the time of Euler step `step` the
-        velocity v and (dv / dx_t)^T cotangent, both f32 [B, Hs, A].  Eager launches."""
+        velocity v and (dv / dx_t)^T cotangent, both f32 [B, Hs, A].  Eager launches.  `state`: as `sample_actions` takes it (pi0)."""
+        if not self.pi05 and state is None:
+            raise ValueError("a pi0 engine needs the request's `state`")
         sch = self._guided_schedule(euler_times(num_steps))
         self._prefix_pass(images, img_masks, lang_tokens, lang_masks)
+        xs = None if self.pi05 else self._pi0_state_rows(state)
         tape = []
         x_t = x_t.to(F32).contiguous()
-        v_t = self._denoise_step(x_t, step, sch, tape=tape)
-        jte = self._denoiser_vjp(cotangent.to(F32).contiguous().view(self.B * self.Hs, self.A), tape, step, sch.mods, sch.mf)
+        v_t = self._denoise_step(x_t, step, sch, xs, tape=tape)
+        jte = self._denoiser_vjp(cotangent.to(F32).contiguous().view(self.B * self.Hs, self.A), tape, step, sch)
         return v_t, jte.view(self.B, self.Hs, self.A)
 
     @torch.no_grad()
-    def sample_actions_guided(self, images, img_masks, lang_tokens, lang_masks, noise, guidance, num_steps: int = 10):
+    def sample_actions_guided(self, images, img_masks, lang_tokens, lang_masks, noise, guidance, num_steps: int = 10, state=None):
         """`sample_actions` steered towards the previous chunk (`guidance`: kai0_amd.rtc.Guidance, resolved on the host).  Captured into
-        a hipGraph of its own, keyed on what is baked into its launches (num_steps, max_guidance_weight, provided); the unguided graph
-        and its static buffers are not touched.  KAI0_INFER_GRAPH=0 (or a refused capture) runs the same launches eagerly."""
-        if not self.pi05:
-            raise NotImplementedError("guided sampling (real-time chunking) is built for pi0.5 only: pi0's Jacobian also runs through the "
-                                      "time MLP and the state token")  # fmt: skip
+        a hipGraph of its own, keyed on what is baked into its launches (num_steps, max_guidance_weight, provided, and whether
+        `mask_prefix_delay` overwrites — the delay itself is data: the rows of `_g_delay`); the unguided graph and its static buffers
+        are not touched.  KAI0_INFER_GRAPH=0 (or a refused capture) runs the same launches eagerly.  `state`: as `sample_actions`."""
+        if self.pi05:
+            state = None
+        elif state is None:
+            raise ValueError("a pi0 engine needs the request's `state`")
         B, Hs, A = self.B, self.Hs, self.A
         if guidance.prev.shape != (B, Hs, A) or guidance.weights.shape != (Hs,):
             raise ValueError(f"guidance for a [{B}, {Hs}, {A}] chunk expected, got prev {guidance.prev.shape}, weights {guidance.weights.shape}")
         if self._g_prev is None:
             self._g_prev = torch.zeros((B, Hs, A), dtype=F32, device=self.dev)
             self._g_w = torch.zeros((Hs,), dtype=F32, device=self.dev)
+            self._g_delay = torch.zeros((Hs,), dtype=F32, device=self.dev)
         self._g_prev.copy_(torch.from_numpy(guidance.prev))
         self._g_w.copy_(torch.from_numpy(guidance.weights))
-        key = (num_steps, float(guidance.max_guidance_weight), int(guidance.provided))
+        mask_delay = bool(guidance.mask_prefix_delay) and guidance.provided > 0  # (:323)
+        if mask_delay:
+            self._g_delay.copy_(torch.from_numpy(guidance.delay_rows))
+        key = (num_steps, float(guidance.max_guidance_weight), int(guidance.provided), mask_delay)
         args = (images, img_masks, lang_tokens, lang_masks, noise)
         if self.use_graph and self._g_graph_key != key:
-            cap = _Capture(*args)
+            cap = _Capture(*args, state)
             self._g_cap, self._g_graph_key = None, key  # (a refused capture is not tried again for this key)
             try:
-                cap.capture(lambda im, mk, tok, lm, nz, st: self._run_guided(im, mk, tok, lm, nz, *key))
+                cap.capture(lambda im, mk, tok, lm, nz, st: self._run_guided(im, mk, tok, lm, nz, *key, st))
                 self._g_cap = cap
             except Exception as e:  # noqa: BLE001 - capture problems must not take serving down
                 logger.warning("hipGraph capture of the guided chunk failed (%s); running eager HIP launches", e)
         if not self.use_graph or self._g_cap is None:
-            return self._run_guided(*args, *key)
-        self._g_cap.replay(*args)
+            return self._run_guided(*args, *key, state)
+        self._g_cap.replay(*args, state)
         return self._g_cap.out.clone()
 
     # -------------------------------------------------------------------------------------------------- API

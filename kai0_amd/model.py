@@ -792,21 +792,21 @@ class PI0Pytorch(nn.Module):
         normalised action space) and `enable_rtc`, every step is steered towards the part of the previous chunk that will still be
         executed — rows below `inference_delay` fully, rows up to `execute_horizon` by `prefix_attention_schedule` — through the
         denoiser's vector-Jacobian product (infer.InferenceEngine.sample_actions_guided).  Without one the call is the unguided one in
-        every respect.  pi0.5 only; `mask_prefix_delay` is not built."""
+        every respect.  Both model variants.  `mask_prefix_delay` (:322-327): the denoiser is evaluated and linearised with the rows
+        below `inference_delay` replaced by the previous chunk's; without a previous chunk, or with `enable_rtc=False`, it does nothing.
+        A guided call validates its arguments (ValueError) and then needs the model on a HIP device (NotImplementedError otherwise: the
+        guided sampler has no CPU form)."""
         from .infer import InferenceEngine
 
         guidance = None
-        if mask_prefix_delay:
-            raise NotImplementedError("sample_actions: mask_prefix_delay is not built (the reference's Policy never passes it)")
         if enable_rtc and prev_action_chunk is not None:
             from . import rtc
 
-            if not self.pi05:
-                raise NotImplementedError("sample_actions: real-time chunking is built for pi0.5 only (pi0's Jacobian also runs through "
-                                          "the time MLP and the state token)")  # fmt: skip
             guidance = rtc.resolve(prev_action_chunk, batch=observation.state.shape[0], action_horizon=self.config.action_horizon,
                                    action_dim=self.config.action_dim, inference_delay=inference_delay, execute_horizon=execute_horizon,
-                                   prefix_attention_schedule=prefix_attention_schedule, max_guidance_weight=max_guidance_weight)  # fmt: skip
+                                   prefix_attention_schedule=prefix_attention_schedule, max_guidance_weight=max_guidance_weight,
+                                   mask_prefix_delay=mask_prefix_delay)  # fmt: skip
+            InferenceEngine.require_hip(next(self.parameters()).device, "sample_actions: real-time chunking (a previous chunk was given)")
         bsize = observation.state.shape[0]
         if noise is None:
             noise = self.sample_noise((bsize, self.config.action_horizon, self.config.action_dim), device)
@@ -839,7 +839,7 @@ class PI0Pytorch(nn.Module):
                 lru.pop(next(iter(lru)))
             self.__dict__["_engine_cur"] = eng
         if guidance is not None:
-            return eng.sample_actions_guided(images, img_masks, lang_tokens, lang_masks, noise.to(F32), guidance, num_steps)
+            return eng.sample_actions_guided(images, img_masks, lang_tokens, lang_masks, noise.to(F32), guidance, num_steps, state=state)
         return eng.sample_actions(images, img_masks, lang_tokens, lang_masks, noise.to(F32), num_steps, state=state)
 
 

@@ -1828,6 +1828,20 @@ def _chk_f32_rows(name: str, rows: int, A: int, **ts) -> None:
             raise TypeError(f"{name}: `{k}` must be a contiguous f32 tensor of {rows} x {A} elements, got {t.dtype} {tuple(t.shape)}")
 
 
+def rtc_overwrite(x, prev, row_mask, provided: int, out=None):
+    """kai0_rtc_overwrite: out = where(row_mask[row % Hs] != 0 and col < provided, prev, x) for f32 [..., Hs, A] (contiguous, any element
+    offset); a fresh tensor unless `out` is given (which must not be x or prev)."""
+    A, Hs = x.shape[-1], row_mask.numel()
+    rows = x.numel() // A
+    if out is None:
+        out = torch.empty_like(x)
+    _chk_f32_rows("rtc_overwrite", rows, A, x=x, prev=prev, out=out)
+    if not row_mask.is_cuda or row_mask.dtype != F32 or not row_mask.is_contiguous() or rows % Hs != 0:
+        raise TypeError(f"rtc_overwrite: row_mask must be a contiguous f32 HIP vector whose length divides the {rows} rows")
+    _lib.call("kai0_rtc_overwrite", x.data_ptr(), prev.data_ptr(), row_mask.data_ptr(), int(provided), out.data_ptr(), rows, Hs, A, _stream())
+    return out
+
+
 def rtc_error(x, v, prev, w_row, provided: int, t: float, out=None):
     """kai0_rtc_error: e = ((prev - (x - t v)) * w_row[row % Hs]) * (col < provided) for f32 [..., Hs, A] (contiguous, any element offset)."""
     A, Hs = x.shape[-1], w_row.numel()

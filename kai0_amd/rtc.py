@@ -5,8 +5,10 @@ Every Euler step of a guided chunk is steered towards the not-yet-executed part 
     e    = (prev - x1) * w[row] * (col < provided)
     corr = (d x1 / d x_t)^T e = e - t (d v / d x_t)^T e
     v'   = nan_to_num(v - g corr);   x_t += dt v'
+With `mask_prefix_delay` (:322-327) v, x1, e and the Jacobian are taken at x_den = x_t with the rows below the inference delay
+overwritten by `prev` on the provided columns; the update still goes to x_t.
 This module holds what is host arithmetic: the prefix weights `w`, the guidance weight `g` per step, and the handling of the request's
-arguments.  The device side is `infer.InferenceEngine.sample_actions_guided` (the reverse sweep) and `csrc/rtc.hip` (the two seams).
+arguments.  The device side is `infer.InferenceEngine.sample_actions_guided` (the reverse sweep) and `csrc/rtc.hip` (the seams).
 All of it is numpy float32: the values are launch constants and small static buffers of the engine.
 
 The reference is JAX; these are restatements read off its source, not executed against it."""
@@ -60,17 +62,20 @@ def guidance_weights(times, max_guidance_weight: float) -> list[float]:
 
 @dataclasses.dataclass
 class Guidance:
-    """A guided call's arguments, resolved: prev f32 [B, H, A] (finite, padded / cut to A), w f32 [H], provided (columns steered)."""
+    """A guided call's arguments, resolved: prev f32 [B, H, A] (finite, padded / cut to A), w f32 [H], provided (columns steered);
+    mask_prefix_delay with delay_rows f32 [H] = (row < inference delay) ? 1 : 0, the rows it overwrites (:324)."""
 
     prev: np.ndarray
     weights: np.ndarray
     provided: int
     max_guidance_weight: float
+    mask_prefix_delay: bool = False
+    delay_rows: np.ndarray | None = None
 
 
 def resolve(prev_action_chunk, *, batch: int, action_horizon: int, action_dim: int, inference_delay=None, execute_horizon=None,
-            prefix_attention_schedule: str = "exp", max_guidance_weight: float = 0.5) -> Guidance:  # fmt: skip
-    """pi0_rtc.py:299-321, 337 for a previous chunk [H, A'] or [B, H, A'] (array, tensor or nested lists)."""
+            prefix_attention_schedule: str = "exp", max_guidance_weight: float = 0.5, mask_prefix_delay: bool = False) -> Guidance:  # fmt: skip
+    """pi0_rtc.py:299-324, 337 for a previous chunk [H, A'] or [B, H, A'] (array, tensor or nested lists)."""
     if prefix_attention_schedule not in SCHEDULES:
         raise ValueError(f"Invalid schedule: {prefix_attention_schedule}")
     if hasattr(prev_action_chunk, "detach"):
@@ -95,4 +100,5 @@ def resolve(prev_action_chunk, *, batch: int, action_horizon: int, action_dim: i
         prev = np.concatenate([prev, np.zeros((*prev.shape[:2], action_dim - a_given), dtype=np.float32)], axis=-1)
     prev = np.array(np.broadcast_to(prev, (batch, H, action_dim)), dtype=np.float32)  # (a writable copy)
     return Guidance(prev=prev, weights=get_prefix_weights(d, exec_h, H, prefix_attention_schedule),
-                    provided=min(MAX_PROVIDED_DIM, a_given, action_dim), max_guidance_weight=float(max_guidance_weight))  # fmt: skip
+                    provided=min(MAX_PROVIDED_DIM, a_given, action_dim), max_guidance_weight=float(max_guidance_weight),
+                    mask_prefix_delay=bool(mask_prefix_delay), delay_rows=(np.arange(H) < d).astype(np.float32))  # fmt: skip

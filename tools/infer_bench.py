@@ -1,8 +1,9 @@
 """p50 of one B = 1 action chunk + stage split, without the training bench (quick iteration on the inference path).
 usage: python tools/infer_bench.py [--pi0]      (--pi0: Pi0Config(pi05=False) — 48 prompt slots, a state token; adds the time of the
 ten steps' suffix-embedding launches, ops.pi0_suffix_embed, replayed from a graph of their own)
-       python tools/infer_bench.py --rtc        (pi0.5: adds the p50 of a GUIDED B = 1 chunk — real-time chunking, d = 3, exec_h = 8, "exp",
-the previous chunk as 14-dim rows — measured the same way as the unguided p50 beside it, and of the same chunk on eager launches)"""
+       python tools/infer_bench.py --rtc [--pi0]  (adds the p50 of a GUIDED B = 1 chunk — real-time chunking, d = 3, exec_h = 8, "exp",
+the previous chunk as 14-dim rows — measured the same way as the unguided p50 beside it, of the same chunk with `mask_prefix_delay`,
+and of the same chunk on eager launches; with --pi0 for the state-token model)"""
 import time
 import json
 import os
@@ -41,14 +42,15 @@ if pi0:
                                  model.action_time_mlp_out.weight, model.action_time_mlp_out.bias, xs, sq, Hs, Ss)
 
     res["suffix_embed_10_steps_ms"] = bench._graph_time_ms(ten)
-if "--rtc" in sys.argv[1:] and not pi0:
+if "--rtc" in sys.argv[1:]:
     model.trim_prompt_padding_infer = False
     obs, _ = bench.synthetic_batch(cfg, 1, seed=123, device=dev)
     noise = torch.randn(1, cfg.action_horizon, cfg.action_dim, device=dev)
     prev = torch.randn(cfg.action_horizon, 14).tolist()
-    kw = dict(prev_action_chunk=prev, inference_delay=3, execute_horizon=8)
+    kw0 = dict(prev_action_chunk=prev, inference_delay=3, execute_horizon=8)
 
-    def p50(iters=20):
+    def p50(iters=20, **more):
+        kw = {**kw0, **more}
         for _ in range(2):
             model.sample_actions(dev, obs, noise=noise, num_steps=10, **kw)
         torch.cuda.synchronize()
@@ -63,6 +65,7 @@ if "--rtc" in sys.argv[1:] and not pi0:
     rtc = {"captured": p50()}
     eng = model._engine
     rtc["graph"] = eng._g_graph is not None
+    rtc["captured_mask_prefix_delay"] = p50(mask_prefix_delay=True)
     eng.use_graph = False
     rtc["eager"] = p50(5)
     eng.use_graph = True
