@@ -811,6 +811,32 @@ int kai0_chunk_stats_hist(const float* state, int64_t ld_state, int ds, const fl
                           int clip_action, int mask_state, uint32_t delta_mask, const double* edges, int bins, uint32_t col_mask,
                           unsigned long long* hist, kai0_stream_t stream);
 
+/* Train-time image augmentation with its own parameters for every sample (models_pytorch/preprocessing_pytorch.py:52-142: the
+ * arithmetic; models/model.py:196-214, augmax under jax.vmap with one key per sample: the granularity).  The definition is
+ * kai0_amd.preprocessing.augment_apply_torch; kai0_amd.preprocessing.sample_augment_params draws the parameters on the host.
+ *   in, out f32 [B][C][H][W] contiguous, C == 3, H, W >= 8, B <= 65535; they must not overlap (the geometric pass reads neighbours).
+ *   params  f32 [B][8] on the device: sh, sw, cos, sin, rotate (0 / 1), brightness, contrast, saturation.  With geometric == 0 only the
+ *           last three are read.  sh and sw are clamped to [0, H - ch] and [0, W - cw] on the device (ch = (int)(H * 0.95) in double,
+ *           likewise cw), so no parameter value makes the kernel read outside `in`.
+ *   scratch kai0_augment_scratch_floats(B, C, H, W) floats (per-block partial sums; 0 for a shape outside the contract).
+ * With v(p) = p / 2 + 0.5 and, for geometric != 0,
+ *     R(y, x) = F.interpolate(bilinear, align_corners=False) of the crop rows [sh, sh + ch) x columns [sw, sw + cw) back to H x W:
+ *               src = max(fmaf(scale, dst + 0.5f, -0.5f), 0), scale = (float)ch / (float)H; i0 = min((int)src, ch - 1),
+ *               i1 = min(i0 + 1, ch - 1), l = src - i0 (likewise along x), the four taps weighted and added as kai0_frames_to_chw does;
+ *     G(y, x) = rotate ? F.grid_sample(bilinear, zeros, align_corners=False) of R at (gx cos - gy sin, gx sin + gy cos), gx / gy =
+ *               torch.linspace(-1, 1, W / H) in f32, unnormalised as ((g + 1) * size - 1) / 2; a tap outside R contributes 0 : R(y, x)
+ * (G = v(in) for geometric == 0), the result per sample b is
+ *     t = G * brightness;  m = mean of t over the sample;  u = (t - m) * contrast + m;  g = (u_0 + u_1 + u_2) / 3;
+ *     out = clamp(g + (u - g) * saturation, 0, 1) * 2 - 1,
+ * every product and sum rounded to f32 on its own.  Two launches: the first writes t to `out` and one partial sum per block to `scratch`;
+ * the second adds a sample's partials in a fixed order in f64 (no atomics: the same call gives the same bits) and finishes `out` in
+ * place.  16-byte accesses where W % 4 == 0 and in / out are 16-byte aligned, 4-byte ones otherwise (4-byte alignment is all that is
+ * required); the result does not depend on which.  Shapes outside the contract, null or overlapping buffers return an error before
+ * any launch. */
+int64_t kai0_augment_scratch_floats(int B, int C, int H, int W);
+int kai0_augment_f32(const float* in, float* out, const float* params, float* scratch, int B, int C, int H, int W, int geometric,
+                     kai0_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

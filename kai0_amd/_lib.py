@@ -220,10 +220,11 @@ _PROTOS: dict[str, list] = {
     "kai0_chunk_stats_moments": [c_p, c_i64, c_i, c_p, c_i64, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, C.c_uint32, c_p, c_p, c_i64, c_p],
     "kai0_chunk_stats_hist": [c_p, c_i64, c_i, c_p, c_i64, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, C.c_uint32, c_p, c_i, C.c_uint32,
                               c_p, c_p],
+    "kai0_augment_f32": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
 }  # fmt: skip
 
 EXPORTED_SYMBOLS = ("kai0_last_error", "kai0_skinny_workspace_bytes", "kai0_attn_decode_workspace_bytes", "kai0_gemm_f32_workspace_bytes",
-                    "kai0_lora_wgrad_workspace_bytes", "kai0_chunk_stats_workspace_bytes", *_PROTOS.keys())
+                    "kai0_lora_wgrad_workspace_bytes", "kai0_chunk_stats_workspace_bytes", "kai0_augment_scratch_floats", *_PROTOS.keys())
 
 _lib = None
 
@@ -272,6 +273,8 @@ def load() -> C.CDLL:
     lib.kai0_lora_wgrad_workspace_bytes.argtypes = [c_i, c_i, c_i]
     lib.kai0_chunk_stats_workspace_bytes.restype = c_i64
     lib.kai0_chunk_stats_workspace_bytes.argtypes = [c_i, c_i]
+    lib.kai0_augment_scratch_floats.restype = c_i64
+    lib.kai0_augment_scratch_floats.argtypes = [c_i, c_i, c_i, c_i]
     if lib.kai0_skinny_desc_size() != C.sizeof(SkinnyDesc):
         raise Kai0HipError(
             f"kai0_skinny_desc layout mismatch: C {lib.kai0_skinny_desc_size()} B vs ctypes {C.sizeof(SkinnyDesc)} B"

@@ -7,7 +7,7 @@ import subprocess
 import sys
 
 HERE = pathlib.Path(__file__).resolve().parent
-SRC = ["runtime.hip", "gemm_bf16.hip", "gemm_f32.hip", "attention.hip", "skinny.hip", "attn_decode.hip", "attn_siglip.hip", "attn_bwd.hip", "norm.hip", "elementwise.hip", "optim.hip", "suffix_embed.hip", "rtc.hip", "lora.hip", "frames.hip", "norm_stats.hip"]
+SRC = ["runtime.hip", "gemm_bf16.hip", "gemm_f32.hip", "attention.hip", "skinny.hip", "attn_decode.hip", "attn_siglip.hip", "attn_bwd.hip", "norm.hip", "elementwise.hip", "optim.hip", "suffix_embed.hip", "rtc.hip", "lora.hip", "frames.hip", "norm_stats.hip", "augment.hip"]
 OUT = HERE / "lib" / "libkai0hip.so"
 
 

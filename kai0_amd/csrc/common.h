@@ -105,6 +105,17 @@ __device__ __forceinline__ float gelu_tanh_grad_f(float x) {
 }
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 
+// ---- bilinear resize taps (frames.hip, augment.hip) ---------------------------------------------
+// torch's area_pixel_compute_source_index + guard_index_and_lambda (align_corners=False): tap indices and the weight of the second tap.
+// The source index is ONE fused multiply-add, as in torch's CPU build (which contracts `scale * (dst + 0.5) - 0.5`): with src up to H0 an
+// unfused product moves the weight by an ulp of H0 (up to 1.5e-5 in the pixel), which a bf16 SigLIP amplifies to its rounding noise.
+__device__ __forceinline__ void bilinear_tap(float scale, int dst, int size, int& i0, int& i1, float& lam) {
+    const float src = fmaxf(__builtin_fmaf(scale, (float)dst + 0.5f, -0.5f), 0.0f);
+    i0 = min((int)src, size - 1);
+    i1 = min(i0 + 1, size - 1);
+    lam = src - (float)i0;
+}
+
 // ---- wave64 reductions -----------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

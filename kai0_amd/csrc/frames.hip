@@ -20,16 +20,6 @@ struct FramesArgs {
     float scale_y, scale_x;
 };
 
-// torch's area_pixel_compute_source_index + guard_index_and_lambda (align_corners=False): tap indices and the weight of the second tap.
-// The source index is ONE fused multiply-add, as in torch's CPU build (which contracts `scale * (dst + 0.5) - 0.5`): with src up to H0 an
-// unfused product moves the weight by an ulp of H0 (up to 1.5e-5 in the pixel), which a bf16 SigLIP amplifies to its rounding noise.
-__device__ __forceinline__ void tap(float scale, int dst, int size, int& i0, int& i1, float& lam) {
-    const float src = fmaxf(__builtin_fmaf(scale, (float)dst + 0.5f, -0.5f), 0.0f);
-    i0 = min((int)src, size - 1);
-    i1 = min(i0 + 1, size - 1);
-    lam = src - (float)i0;
-}
-
 __device__ __forceinline__ float norm_u8(uint8_t u) { return (float)u / 255.0f * 2.0f - 1.0f; }
 
 __global__ __launch_bounds__(256) void frames_to_chw_kernel(const FramesArgs p) {
@@ -42,8 +32,8 @@ __global__ __launch_bounds__(256) void frames_to_chw_kernel(const FramesArgs p) 
     int y0 = 0, y1 = 0, x0 = 0, x1 = 0;
     float ly = 0.0f, lx = 0.0f;
     if (inside) {
-        tap(p.scale_y, ry, p.H0, y0, y1, ly);
-        tap(p.scale_x, rx, p.W0, x0, x1, lx);
+        bilinear_tap(p.scale_y, ry, p.H0, y0, y1, ly);
+        bilinear_tap(p.scale_x, rx, p.W0, x0, x1, lx);
     }
     // torch's CPU kernel where it does not split an image over threads (always so below its parallel grain): the four tap weights are
     // products of the axis weights, rounded to f32, and the taps are accumulated as w01 v01, then fma(w00, v00), fma(w10, v10),

@@ -553,7 +553,8 @@ class PI0Pytorch(nn.Module):
             self.action_time_mlp_out = Linear(exp.width, exp.width)
         self.gradient_checkpointing_enabled = False
         # the reference hard-codes train=True (random crop/rotate/colour) in forward (pi0_pytorch.py:318);
-        # parity tests switch it off and inject noise/time.
+        # parity tests switch it off and inject noise/time.  "per_sample": every sample its own draw, as the JAX trainer augments
+        # (models/model.py:196-214; preprocessing.sample_augment_params, csrc/augment.hip); True stays the torch port's draw per batch.
         self.train_augmentation = True
         self.trim_prompt_padding = False  # training forward: drop the prompt slots no sample of the batch uses (_trim_prompt)
         # sample_actions: the same for the request's prompt (the tokenizer pads every prompt to max_token_len; a task prompt fills
@@ -669,8 +670,11 @@ class PI0Pytorch(nn.Module):
         return (t * 0.999 + 0.001).to(dtype=F32, device=device)
 
     def _preprocess_observation(self, observation, *, train=True):
+        if train not in (True, False, "per_sample"):
+            raise ValueError(f"train_augmentation must be True, False or 'per_sample', got {train!r}")
         res = self.paligemma_with_expert.siglip_cfg.image_size
-        obs = preprocess_observation(observation, train=train, image_resolution=(res, res))
+        obs = preprocess_observation(observation, train=bool(train), image_resolution=(res, res),
+                                     augment="per_sample" if train == "per_sample" else "batch")  # fmt: skip
         return (list(obs.images.values()), list(obs.image_masks.values()), obs.tokenized_prompt,
                 obs.tokenized_prompt_mask, obs.state)  # fmt: skip
 

@@ -1894,6 +1894,39 @@ def frames_to_chw(frames: torch.Tensor, height: int, width: int, out: torch.Tens
     return out
 
 
+def augment_images(image: torch.Tensor, params: torch.Tensor, *, geometric: bool, out: torch.Tensor | None = None,
+                   scratch: torch.Tensor | None = None) -> torch.Tensor:  # fmt: skip
+    """kai0_augment_f32: the train-time augmentation with one parameter row per sample (preprocessing.augment_apply_torch is the
+    definition, preprocessing.pack_augment_params the rows): image f32 [B, 3, H, W] in [-1, 1], contiguous, H, W >= 8; params f32 [B, 8]
+    on the same device (sh, sw, cos, sin, rotate, brightness, contrast, saturation) -> a fresh f32 [B, 3, H, W] (or `out`, which must not
+    overlap `image`).  `scratch`: kai0_augment_scratch_floats(B, 3, H, W) f32 elements, allocated here unless given.  Two launches."""
+    for name, t in (("image", image), ("params", params), ("out", out), ("scratch", scratch)):
+        if t is None:
+            continue
+        if not t.is_cuda or t.device != image.device:
+            raise _lib.Kai0HipError(f"augment_images: `{name}` must be a CUDA (HIP) tensor on the image's device; the kernel has no CPU form "
+                                    "(preprocessing.augment_apply_torch is the host path)")  # fmt: skip
+        if t.dtype != F32 or not t.is_contiguous():
+            raise _lib.Kai0HipError(f"augment_images: `{name}` must be a contiguous f32 tensor, got {t.dtype} with strides {t.stride()}")
+    if image.dim() != 4:
+        raise _lib.Kai0HipError(f"augment_images: image must be [B, 3, H, W], got {tuple(image.shape)}")
+    B, C, H, W = image.shape
+    if tuple(params.shape) != (B, 8):
+        raise _lib.Kai0HipError(f"augment_images: params must be [{B}, 8], got {tuple(params.shape)}")
+    if out is None:
+        out = torch.empty_like(image)
+    elif tuple(out.shape) != (B, C, H, W):
+        raise _lib.Kai0HipError(f"augment_images: out must be [{B}, {C}, {H}, {W}], got {tuple(out.shape)}")
+    need = int(_lib.load().kai0_augment_scratch_floats(B, C, H, W))
+    if scratch is None:
+        scratch = torch.empty(max(need, 1), dtype=F32, device=image.device)
+    elif scratch.numel() < need:
+        raise _lib.Kai0HipError(f"augment_images: scratch holds {scratch.numel()} floats, {need} needed")
+    _lib.call("kai0_augment_f32", image.data_ptr(), out.data_ptr(), params.data_ptr(), scratch.data_ptr(), B, C, H, W, int(bool(geometric)),
+              _stream())  # fmt: skip
+    return out
+
+
 def prefix_gather(bank: torch.Tensor, slots, lang: torch.Tensor | None, out: torch.Tensor | None = None) -> torch.Tensor:
     """kai0_prefix_gather: out[b][s * n_img + r] = bank[slots[b][s]][r], out[b][nslot * n_img + t] = lang[b][t] (lang [T, D]: one prompt
     for the whole batch; [B, T, D]: per sample; None: no prompt rows) -> bf16 [B, nslot * n_img + T, D].

@@ -3,7 +3,9 @@
 Mirrors `openpi.models.model.Observation` (models/model.py:85-140) and
 `preprocess_observation_pytorch` (models_pytorch/preprocessing_pytorch.py:20-173) including the train-time
 augmentation the reference hard-enables in `PI0Pytorch.forward` (pi0_pytorch.py:318).  SURVEY.md §2.1 #3 marks
-this as boundary code that stays in torch: it is memory-bound image plumbing, not a kernel target.
+this as boundary code that stays in torch: it is memory-bound image plumbing, not a kernel target.  The one exception is the
+opt-in per-sample augmentation (`augment="per_sample"`): every sample its own draw, as the JAX trainer augments, which
+torch glue cannot do in a batch-independent number of launches and csrc/augment.hip does in two per camera.
 """
 
 from __future__ import annotations
@@ -147,6 +149,99 @@ def _augment(image: torch.Tensor, geometric: bool) -> torch.Tensor:
     return torch.clamp(image, 0, 1) * 2.0 - 1.0
 
 
+AUGMENT_MODES = ("batch", "per_sample")
+
+
+def sample_augment_params(batch: int, height: int, width: int, *, geometric: bool, generator: torch.Generator | None = None) -> dict:
+    """One draw of `_augment`'s parameters for EVERY sample, as the JAX trainer augments (models/model.py:196-214: the augmax chain under
+    `jax.vmap` with one key per sample), where the torch port (preprocessing_pytorch.py:52-142) draws once per camera and call.
+    CPU tensors of length `batch`, drawn in the fixed order sh, sw (int64), angle, brightness, contrast, saturation (f32, formed as
+    `_augment` forms them); `geometric=False` draws the three colour parameters only.  The draws come from torch's default CPU generator
+    unless one is given — the trainer's saved RNG state reproduces them on resume — and none touches a device."""
+    params = {}
+    if geometric:
+        max_h, max_w = height - int(height * 0.95), width - int(width * 0.95)
+        params["sh"] = torch.randint(0, max_h + 1, (batch,), generator=generator, device="cpu")
+        params["sw"] = torch.randint(0, max_w + 1, (batch,), generator=generator, device="cpu")
+        params["angle"] = torch.rand(batch, generator=generator) * 10 - 5
+    params["brightness"] = 0.7 + torch.rand(batch, generator=generator) * 0.6
+    params["contrast"] = 0.6 + torch.rand(batch, generator=generator) * 0.8
+    params["saturation"] = 0.5 + torch.rand(batch, generator=generator) * 1.0
+    return params
+
+
+def augment_apply_torch(image: torch.Tensor, params: dict, *, geometric: bool) -> torch.Tensor:
+    """The per-sample augmentation's definition: sample b of the result is what `_augment` computes on `image[b:b+1]` ([B, H, W, C] in
+    [-1, 1], f32 or f64) when its six draws are `params[...][b]` — the same torch ops in the same order, sample by sample, and the
+    rotation's |angle| > 0.1 gate decided per sample.  The reference of csrc/augment.hip (in float64) and the per-sample path of
+    tensors that are not on a HIP device."""
+    dev = image.device
+    height, width = image.shape[1:3]
+    ch, cw = int(height * 0.95), int(width * 0.95)
+    out = []
+    for b in range(image.shape[0]):
+        x = image[b : b + 1] / 2.0 + 0.5
+        if geometric:
+            if height - ch > 0 and width - cw > 0:
+                sh, sw = int(params["sh"][b]), int(params["sw"][b])
+                x = x[:, sh : sh + ch, sw : sw + cw, :]
+            x = F.interpolate(x.permute(0, 3, 1, 2), size=(height, width), mode="bilinear", align_corners=False)
+            angle = float(params["angle"][b])
+            if abs(angle) > 0.1:
+                rad = angle * torch.pi / 180.0
+                cos_a, sin_a = float(np.cos(rad)), float(np.sin(rad))
+                gx = torch.linspace(-1, 1, width, device=dev, dtype=x.dtype)
+                gy = torch.linspace(-1, 1, height, device=dev, dtype=x.dtype)
+                gy, gx = torch.meshgrid(gy, gx, indexing="ij")
+                gx, gy = gx.unsqueeze(0), gy.unsqueeze(0)
+                grid = torch.stack([gx * cos_a - gy * sin_a, gx * sin_a + gy * cos_a], dim=-1)
+                x = F.grid_sample(x, grid, mode="bilinear", padding_mode="zeros", align_corners=False)
+            x = x.permute(0, 2, 3, 1)
+        x = x * float(params["brightness"][b])
+        mean = x.mean(dim=[1, 2, 3], keepdim=True)
+        x = (x - mean) * float(params["contrast"][b]) + mean
+        gray = x.mean(dim=-1, keepdim=True)
+        x = gray + (x - gray) * float(params["saturation"][b])
+        out.append(torch.clamp(x, 0, 1) * 2.0 - 1.0)
+    return torch.cat(out, dim=0)
+
+
+def pack_augment_params(params: dict, *, geometric: bool) -> torch.Tensor:
+    """`sample_augment_params`' dict as the f32 [B, 8] rows kai0_augment_f32 reads (sh, sw, cos, sin, rotate, brightness, contrast,
+    saturation), on the host: cos / sin through `np.cos(angle * pi / 180)` in double as `_augment` forms them, rotate = |angle| > 0.1."""
+    rows = torch.zeros(params["brightness"].shape[0], 8, dtype=torch.float32)
+    if geometric:
+        angle = params["angle"].to(torch.float64).numpy()
+        rad = angle * torch.pi / 180.0
+        rows[:, 0], rows[:, 1] = params["sh"].to(torch.float32), params["sw"].to(torch.float32)
+        rows[:, 2], rows[:, 3] = torch.from_numpy(np.cos(rad)).to(torch.float32), torch.from_numpy(np.sin(rad)).to(torch.float32)
+        rows[:, 4] = torch.from_numpy(np.abs(angle) > 0.1).to(torch.float32)
+    rows[:, 5], rows[:, 6], rows[:, 7] = params["brightness"], params["contrast"], params["saturation"]
+    return rows
+
+
+def _augment_per_sample(images: dict, keys: Sequence[str]) -> dict:
+    """`augment="per_sample"`: every camera of `keys` (NHWC views, in this order) with its own draw per sample.  All cameras' parameters
+    travel to the device as ONE [ncam, B, 8] tensor: each small pageable copy is a synchronisation (device_resize.py)."""
+    from . import ops
+
+    geometric = {key: "wrist" not in key for key in keys}
+    drawn = {key: sample_augment_params(*images[key].shape[:3], geometric=geometric[key]) for key in keys}
+    hip = [key for key in keys if images[key].is_cuda]
+    rows = {}
+    if hip:
+        packed = [pack_augment_params(drawn[key], geometric=geometric[key]) for key in hip]
+        rows = dict(zip(hip, torch.stack(packed).to(images[hip[0]].device)))
+    out = {}
+    for key in keys:
+        if key in rows:
+            nchw = ops.augment_images(images[key].permute(0, 3, 1, 2).contiguous(), rows[key], geometric=geometric[key])
+            out[key] = nchw.permute(0, 2, 3, 1)
+        else:
+            out[key] = augment_apply_torch(images[key], drawn[key], geometric=geometric[key])
+    return out
+
+
 class ProcessedObservation:
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -154,26 +249,33 @@ class ProcessedObservation:
 
 
 def preprocess_observation(observation, *, train: bool = False, image_keys: Sequence[str] = IMAGE_KEYS,
-                           image_resolution: tuple[int, int] | None = None):  # fmt: skip
+                           image_resolution: tuple[int, int] | None = None, augment: str = "batch"):  # fmt: skip
     """preprocessing_pytorch.py:20-173. `image_resolution=None` keeps whatever square resolution the images
-    already have when it is not 224 (small test towers); the default model resizes to 224x224 with padding."""
+    already have when it is not 224 (small test towers); the default model resizes to 224x224 with padding.
+    `augment` (with `train`): "batch" is the torch port's one draw per camera and call (`_augment`); "per_sample" gives every sample
+    its own draw (`sample_augment_params`), applied by csrc/augment.hip on a HIP tensor and by `augment_apply_torch` anywhere else."""
     if not set(image_keys).issubset(observation.images):
         raise ValueError(f"images dict missing keys: expected {image_keys}, got {list(observation.images)}")
+    if augment not in AUGMENT_MODES:
+        raise ValueError(f"augment must be one of {AUGMENT_MODES}, got {augment!r}")
     batch_shape = observation.state.shape[:-1]
-    out_images = {}
+    out_images, channels_first = {}, {}
     for key in image_keys:
         image = observation.images[key]
-        channels_first = image.shape[1] == 3
-        if channels_first:
+        channels_first[key] = image.shape[1] == 3
+        if channels_first[key]:
             image = image.permute(0, 2, 3, 1)
         if image_resolution is not None and tuple(image.shape[1:3]) != tuple(image_resolution):
             logger.info(f"Resizing image {key} from {image.shape[1:3]} to {image_resolution}")
             image = resize_with_pad_torch(image, *image_resolution)
-        if train:
+        if train and augment == "batch":
             image = _augment(image, geometric="wrist" not in key)
-        if channels_first:
-            image = image.permute(0, 3, 1, 2)
         out_images[key] = image
+    if train and augment == "per_sample":
+        out_images = _augment_per_sample(out_images, list(image_keys))
+    for key in image_keys:
+        if channels_first[key]:
+            out_images[key] = out_images[key].permute(0, 3, 1, 2)
     out_masks = {}
     for key in out_images:
         if key not in observation.image_masks:

@@ -293,6 +293,15 @@ def _setup_distributed():
     return world, rank, device
 
 
+def augment_mode_from_env() -> str:
+    """KAI0_AUGMENT: `batch` (or unset: the torch port's one augmentation draw per camera and step, the default) or `per_sample`
+    (`PI0Pytorch.train_augmentation = "per_sample"`)."""
+    mode = os.environ.get("KAI0_AUGMENT", "batch")
+    if mode not in ("batch", "per_sample"):
+        raise ValueError(f"KAI0_AUGMENT={mode!r}: expected 'batch' or 'per_sample'")
+    return mode
+
+
 def build_model(config, device):
     """train_pytorch.py:399-458: `config.model` in `pytorch_training_precision`, on `device`, with `pytorch_weight_path`'s
     `model.safetensors` loaded (strict unless an AdvantageEstimator is initialised from a policy checkpoint)."""
@@ -308,6 +317,8 @@ def build_model(config, device):
         # invisible keys and unread rows: loss and gradients unchanged beyond summation order, tests/test_model_gpu.py).  bench.py
         # measures with it off — every one of the 200 slots computed, as the reference does — and reports the trimmed rate beside it.
         model.trim_prompt_padding = True
+    if augment_mode_from_env() == "per_sample" and hasattr(model, "train_augmentation"):
+        model.train_augmentation = "per_sample"  # one augmentation draw per sample (the JAX trainer's form) instead of one per batch
     if config.pytorch_weight_path is not None:
         load_model_safetensors(model, os.path.join(config.pytorch_weight_path, "model.safetensors"),
                                strict=not config.advantage_estimator)  # fmt: skip
