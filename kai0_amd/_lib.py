@@ -128,8 +128,34 @@ class SkinnyDesc(C.Structure):
     ]  # fmt: skip
 
 
-# name -> argtypes (every function returns int except where noted)
+# C struct of include/kai0hip.h -> its mirror above (kai0_gemm_desc's nested `seg` is GemmSeg).  kai0_ck_item has none: the engine builds
+# the items as an int64 [n, 2] tensor.
+MIRRORS = {"kai0_gemm_desc": GemmDesc, "kai0_gemm_plan_t": GemmPlan, "kai0_skinny_seg": SkinnySeg, "kai0_skinny_desc": SkinnyDesc,
+           "kai0_attn_desc": AttnDesc, "kai0_attn_bwd_desc": AttnBwdDesc, "kai0_reduce_item": ReduceItem, "kai0_pack_part": PackPart}
+
+
+class _Proto(list):
+    """The argtypes of one function, with its restype where that is not int."""
+
+    def __init__(self, restype, argtypes):
+        super().__init__(argtypes)
+        self.restype = restype
+
+
+def restype_of(name: str):
+    return getattr(_PROTOS[name], "restype", c_i)
+
+
+# name -> argtypes (and restype) of EVERY exported function: the one description of the prototypes on this side of the boundary.
+# tests/test_cabi_cpu.py holds it, and the mirrors, against include/kai0hip.h declaration by declaration.
 _PROTOS: dict[str, list] = {
+    "kai0_last_error": _Proto(C.c_char_p, []),
+    "kai0_skinny_workspace_bytes": _Proto(c_i64, [c_i, c_i, c_i]),
+    "kai0_attn_decode_workspace_bytes": _Proto(c_i64, [c_i, c_i]),
+    "kai0_gemm_f32_workspace_bytes": _Proto(c_i64, [c_i, c_i, c_i]),
+    "kai0_lora_wgrad_workspace_bytes": _Proto(c_i64, [c_i, c_i, c_i]),
+    "kai0_chunk_stats_workspace_bytes": _Proto(c_i64, [c_i, c_i]),
+    "kai0_augment_scratch_floats": _Proto(c_i64, [c_i, c_i, c_i, c_i]),
     "kai0_abi_version": [],
     "kai0_gemm_desc_size": [],
     "kai0_device_info": [c_i, C.POINTER(c_i), C.POINTER(c_i), C.c_char_p],
@@ -223,8 +249,7 @@ _PROTOS: dict[str, list] = {
     "kai0_augment_f32": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
 }  # fmt: skip
 
-EXPORTED_SYMBOLS = ("kai0_last_error", "kai0_skinny_workspace_bytes", "kai0_attn_decode_workspace_bytes", "kai0_gemm_f32_workspace_bytes",
-                    "kai0_lora_wgrad_workspace_bytes", "kai0_chunk_stats_workspace_bytes", "kai0_augment_scratch_floats", *_PROTOS.keys())
+EXPORTED_SYMBOLS = tuple(_PROTOS)
 
 _lib = None
 
@@ -250,35 +275,17 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
 
     lib = C.CDLL(str(path))
-    lib.kai0_last_error.restype = C.c_char_p
-    lib.kai0_last_error.argtypes = []
-    for name, args in _PROTOS.items():
+    for name, argtypes in _PROTOS.items():
         fn = getattr(lib, name)
-        fn.restype = c_i
-        fn.argtypes = args
+        fn.restype = restype_of(name)
+        fn.argtypes = list(argtypes)
     if lib.kai0_abi_version() != ABI_VERSION:
         raise Kai0HipError(f"{path}: C ABI version {lib.kai0_abi_version()}, this binding expects {ABI_VERSION} (rebuild the library)")
-    if lib.kai0_gemm_desc_size() != C.sizeof(GemmDesc):
-        raise Kai0HipError(
-            f"kai0_gemm_desc layout mismatch: C {lib.kai0_gemm_desc_size()} B vs ctypes {C.sizeof(GemmDesc)} B"
-        )
-    for fn, mirror in (("kai0_attn_desc_size", AttnDesc), ("kai0_attn_bwd_desc_size", AttnBwdDesc), ("kai0_gemm_plan_size", GemmPlan)):
-        if getattr(lib, fn)() != C.sizeof(mirror):
-            raise Kai0HipError(f"{fn[:-5]} layout mismatch: C {getattr(lib, fn)()} B vs ctypes {C.sizeof(mirror)} B")
-    lib.kai0_attn_decode_workspace_bytes.restype = c_i64
-    lib.kai0_attn_decode_workspace_bytes.argtypes = [c_i, c_i]
-    lib.kai0_skinny_workspace_bytes.restype = c_i64
-    lib.kai0_skinny_workspace_bytes.argtypes = [c_i, c_i, c_i]
-    lib.kai0_lora_wgrad_workspace_bytes.restype = c_i64
-    lib.kai0_lora_wgrad_workspace_bytes.argtypes = [c_i, c_i, c_i]
-    lib.kai0_chunk_stats_workspace_bytes.restype = c_i64
-    lib.kai0_chunk_stats_workspace_bytes.argtypes = [c_i, c_i]
-    lib.kai0_augment_scratch_floats.restype = c_i64
-    lib.kai0_augment_scratch_floats.argtypes = [c_i, c_i, c_i, c_i]
-    if lib.kai0_skinny_desc_size() != C.sizeof(SkinnyDesc):
-        raise Kai0HipError(
-            f"kai0_skinny_desc layout mismatch: C {lib.kai0_skinny_desc_size()} B vs ctypes {C.sizeof(SkinnyDesc)} B"
-        )
+    for name in _PROTOS:  # every kai0_X_size() the library exports against the mirror of struct kai0_X (kai0_X_t)
+        if name.endswith("_size"):
+            mirror = MIRRORS.get(name[:-5]) or MIRRORS[name[:-5] + "_t"]
+            if getattr(lib, name)() != C.sizeof(mirror):
+                raise Kai0HipError(f"{name[:-5]} layout mismatch: C {getattr(lib, name)()} B vs ctypes {C.sizeof(mirror)} B")
     _lib = lib
     return lib
 

@@ -697,13 +697,9 @@ KAI0_API int kai0_attn_fwd(const kai0_attn_desc* d, kai0_stream_t stream) {
     do {                                                                                                          \
         constexpr int LDS = (OP > 0 ? OP : (RB == 64 ? 1 : 2)) * (NKS * 8192 + 64 * VC * 2) + (RB / 32) * 4096 + KC_LDS_MAX * 4 + 512; \
         static_assert(LDS <= 160 * 1024, "attention LDS budget");                                                    \
-        static bool attr_set = false;                                                                             \
         auto kern = attn_fwd_kernel<NKS, VC, QT, OP, RB>;                                                             \
-        if (!attr_set) {                                                                                          \
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); \
-            KAI0_REQUIRE(e == hipSuccess, "kai0_attn_fwd: cannot reserve %d B of LDS: %s", LDS, hipGetErrorString(e)); \
-            attr_set = true;                                                                                      \
-        }                                                                                                         \
+        const hipError_t e = kai0_reserve_lds((const void*)kern, LDS);                                            \
+        KAI0_REQUIRE(e == hipSuccess, "kai0_attn_fwd: cannot reserve %d B of LDS: %s", LDS, hipGetErrorString(e)); \
         hipLaunchKernelGGL(kern, grid, dim3(RB / (16 * QT) * 64), LDS, s, p);                                    \
     } while (0)
     // (Measured and rejected, round 3: the two wave groups of pass 2 one barrier slot apart — 1.095 against 0.965 ms; four-wave

@@ -368,13 +368,9 @@ static int attn_bwd_dq_launch(const void* dO, const void* O, const void* P, cons
 #define KAI0_AB_LAUNCH(NKS, RC)                                                                                          \
     do {                                                                                                               \
         constexpr int LDS = 2 * (NKS * 8192 + 64 * NKS * 128) + (RC ? AB_KC_MAX * 4 + 512 : 0);                                \
-        static bool attr_set = false;                                                                                  \
         auto kern = attn_bwd_dq_kernel<NKS, RC>;                                                                       \
-        if (!attr_set) {                                                                                               \
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);      \
-            KAI0_REQUIRE(e == hipSuccess, "kai0_attn_bwd_dq: cannot reserve %d B of LDS: %s", LDS, hipGetErrorString(e)); \
-            attr_set = true;                                                                                           \
-        }                                                                                                              \
+        const hipError_t e = kai0_reserve_lds((const void*)kern, LDS);                                                 \
+        KAI0_REQUIRE(e == hipSuccess, "kai0_attn_bwd_dq: cannot reserve %d B of LDS: %s", LDS, hipGetErrorString(e));   \
         hipLaunchKernelGGL(kern, grid, dim3(512), LDS, s, a);                                                          \
     } while (0)
     if (rc) {

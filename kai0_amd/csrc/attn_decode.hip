@@ -251,15 +251,11 @@ KAI0_API int kai0_attn_decode(const void* Q, const void* K, const void* Vt, void
               q_bs, k_bs, k_ld, vt_bs, vt_ld, qcode_ld, kcode_ld, scale};
     const int qt = (rows + 15) / 16;
     const int64_t l_bs = (int64_t)qt * 16 * DEC_KEYS;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)dec_logits_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, DEC_LOGITS_LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_logits_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, DEC_LOGITS_LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_pv_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, DEC_PV_LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_pv_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, DEC_PV_LDS);
-        KAI0_REQUIRE(e == hipSuccess, "kai0_attn_decode: cannot reserve %d B of LDS: %s", DEC_PV_LDS, hipGetErrorString(e));
-        attr_set = true;
-    }
+    hipError_t e = kai0_reserve_lds((const void*)dec_logits_kernel<1>, DEC_LOGITS_LDS);
+    if (e == hipSuccess) e = kai0_reserve_lds((const void*)dec_logits_kernel<2>, DEC_LOGITS_LDS);
+    if (e == hipSuccess) e = kai0_reserve_lds((const void*)dec_pv_kernel<2>, DEC_PV_LDS);
+    if (e == hipSuccess) e = kai0_reserve_lds((const void*)dec_pv_kernel<4>, DEC_PV_LDS);
+    KAI0_REQUIRE(e == hipSuccess, "kai0_attn_decode: cannot reserve %d B of LDS: %s", DEC_PV_LDS, hipGetErrorString(e));
     // few query tiles (B = 1: 25): eight key ranges / eight head-dim slices per tile instead of four, so that 200 blocks share
     // the staging of the caches instead of 100
     const int fine = 1;

@@ -505,13 +505,9 @@ static int siglip_attn_bwd_launch(const void* q, const void* k, const void* v, c
     if (ld_grad == 0) ld_grad = (int64_t)NH * HD;
     KAI0_REQUIRE(ld_grad >= (int64_t)NH * HD && ld_grad % 4 == 0, "kai0_siglip_attn_bwd: ld_grad=%lld", (long long)ld_grad);
     if (n_img <= 0) return 0;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)siglip_attn_bwd_kernel<false, 104>, hipFuncAttributeMaxDynamicSharedMemorySize, sb_lds_bytes(false, 104));
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)siglip_attn_bwd_kernel<true, 72>, hipFuncAttributeMaxDynamicSharedMemorySize, sb_lds_bytes(true, 72));
-        KAI0_REQUIRE(e == hipSuccess, "kai0_siglip_attn_bwd: cannot reserve LDS: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    hipError_t e = kai0_reserve_lds((const void*)siglip_attn_bwd_kernel<false, 104>, sb_lds_bytes(false, 104));
+    if (e == hipSuccess) e = kai0_reserve_lds((const void*)siglip_attn_bwd_kernel<true, 72>, sb_lds_bytes(true, 72));
+    KAI0_REQUIRE(e == hipSuccess, "kai0_siglip_attn_bwd: cannot reserve LDS: %s", hipGetErrorString(e));
     SbArgs a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dO, (const bf16_t*)O, (const bf16_t*)P, lse,
              (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, NH, (int64_t)NH * HD, ld_grad, scale};
     // (the recompute form with padded 104-wide tiles — one block per CU — measured 0.376 against 0.301 ms per layer: removed)
@@ -547,13 +543,9 @@ KAI0_API int kai0_siglip_attn_fwd(const void* q, const void* k, const void* v, v
                  "kai0_siglip_attn_fwd: q / k / v rows must be 16-byte aligned (leading dims %% 8), o rows 8-byte aligned");
     if (n_img <= 0) return 0;
     constexpr int LDS = 2 * sb_tile_bytes(72) + 64;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)siglip_attn_fwd_kernel<8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)siglip_attn_fwd_kernel<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        KAI0_REQUIRE(e == hipSuccess, "kai0_siglip_attn_fwd: cannot reserve LDS: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    hipError_t e = kai0_reserve_lds((const void*)siglip_attn_fwd_kernel<8, 2>, LDS);
+    if (e == hipSuccess) e = kai0_reserve_lds((const void*)siglip_attn_fwd_kernel<4, 1>, LDS);
+    KAI0_REQUIRE(e == hipSuccess, "kai0_siglip_attn_fwd: cannot reserve LDS: %s", hipGetErrorString(e));
     SfArgs a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, NH, ldq, ldk, ldv, ldo, sq, sk, sv, so, scale};
     const int heads = n_img * NH;
     // few heads (B = 1 inference: 48): four 64-row blocks per head so that the launch covers the chip

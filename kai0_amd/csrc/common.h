@@ -37,6 +37,10 @@ __device__ __forceinline__ void lds_barrier() {
 // ---- error plumbing (host side) -------------------------------------------------------------
 void kai0_set_error(const char* fmt, ...);
 int kai0_check_launch(const char* what);
+// Makes sure `kernel` may be launched with `bytes` of dynamic LDS: hipFuncAttributeMaxDynamicSharedMemorySize is set the first time a
+// kernel ADDRESS is seen, once per process; later calls are a table look-up (no runtime call, no device query on the launch path).
+// Returns the runtime's error, for the entry point to report under its own name.
+hipError_t kai0_reserve_lds(const void* kernel, int bytes);
 
 #define KAI0_REQUIRE(cond, ...)            \
     do {                                   \

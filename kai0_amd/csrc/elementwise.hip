@@ -655,44 +655,47 @@ __global__ __launch_bounds__(256) void euler_kernel(float* __restrict__ x, const
 
 #define S_(st) ((hipStream_t)(st))
 
+// What rope_kernel can rotate: 8 elements per thread, whole rows per 256-thread block.
+static bool rope_hd_ok(int HD) { return HD % 8 == 0 && HD >= 8 && HD <= 2048 && 256 % (HD / 8) == 0; }
+// The one rope_kernel launch behind kai0_rope_inplace / kai0_rope_inplace2 / kai0_rope_copy (HD already checked by the entry point, under
+// its own message); strides in elements.  x2 (optional): a second tensor rotated in place with the same positions.
+static int rope_launch(const char* who, bf16_t* dst, const bf16_t* src, const int32_t* pos, const float* inv_freq, int B, int S, int64_t dst_bs,
+                       int64_t dst_ld, int64_t src_bs, int64_t src_ld, int64_t pos_bs, int H, int HD, int inverse, kai0_stream_t stream,
+                       bf16_t* x2 = nullptr, int64_t x2_bs = 0, int64_t x2_ld = 0, int H2 = 0) {
+    if (B * S <= 0) return 0;
+    const int rpb = 256 / (HD / 8);
+    hipLaunchKernelGGL(rope_kernel, dim3(ew_grid((int64_t)B * S, rpb)), dim3(256), 0, S_(stream), dst, src, pos, inv_freq, B, S, dst_bs, dst_ld,
+                       src_bs, src_ld, pos_bs, H, HD, inverse, x2, x2_bs, x2_ld, H2);
+    return kai0_check_launch(who);
+}
+
 KAI0_API int kai0_rope_inplace(void* x, const int32_t* pos, const float* inv_freq, int B, int S, int64_t s_ld_rows,
                                int64_t row0, int H, int HD, int inverse, kai0_stream_t stream) {
     KAI0_REQUIRE(HD % 8 == 0 && HD >= 8 && HD <= 2048, "kai0_rope_inplace: HD=%d unsupported", HD);
-    KAI0_REQUIRE(256 % (HD / 8) == 0, "kai0_rope_inplace: HD/8 must divide 256 (HD=%d)", HD);
-    if (B * S <= 0) return 0;
-    const int rpb = 256 / (HD / 8);
+    KAI0_REQUIRE(rope_hd_ok(HD), "kai0_rope_inplace: HD/8 must divide 256 (HD=%d)", HD);
     const int64_t row = (int64_t)H * HD;
-    hipLaunchKernelGGL(rope_kernel, dim3(ew_grid((int64_t)B * S, rpb)), dim3(256), 0, S_(stream), (bf16_t*)x + row0 * row,
-                       (const bf16_t*)x + row0 * row, pos, inv_freq, B, S, s_ld_rows * row, row, s_ld_rows * row, row, (int64_t)S, H,
-                       HD, inverse);
-    return kai0_check_launch("kai0_rope_inplace");
+    return rope_launch("kai0_rope_inplace", (bf16_t*)x + row0 * row, (const bf16_t*)x + row0 * row, pos, inv_freq, B, S, s_ld_rows * row, row,
+                       s_ld_rows * row, row, (int64_t)S, H, HD, inverse, stream);
 }
 
 KAI0_API int kai0_rope_inplace2(void* x, int H, void* x2, int H2, const int32_t* pos, const float* inv_freq, int B, int S,
                                 int64_t s_ld_rows, int64_t row0, int HD, kai0_stream_t stream) {
     KAI0_REQUIRE(x && x2 && pos && inv_freq, "kai0_rope_inplace2: null operand");
-    KAI0_REQUIRE(HD % 8 == 0 && HD >= 8 && HD <= 2048 && 256 % (HD / 8) == 0, "kai0_rope_inplace2: HD=%d unsupported", HD);
-    if (B * S <= 0) return 0;
-    const int rpb = 256 / (HD / 8);
+    KAI0_REQUIRE(rope_hd_ok(HD), "kai0_rope_inplace2: HD=%d unsupported", HD);
     const int64_t r1 = (int64_t)H * HD, r2 = (int64_t)H2 * HD;
-    hipLaunchKernelGGL(rope_kernel, dim3(ew_grid((int64_t)B * S, rpb)), dim3(256), 0, S_(stream), (bf16_t*)x + row0 * r1,
-                       (const bf16_t*)x + row0 * r1, pos, inv_freq, B, S, s_ld_rows * r1, r1, s_ld_rows * r1, r1, (int64_t)S, H, HD, 0,
-                       (bf16_t*)x2 + row0 * r2, s_ld_rows * r2, r2, H2);
-    return kai0_check_launch("kai0_rope_inplace2");
+    return rope_launch("kai0_rope_inplace2", (bf16_t*)x + row0 * r1, (const bf16_t*)x + row0 * r1, pos, inv_freq, B, S, s_ld_rows * r1, r1,
+                       s_ld_rows * r1, r1, (int64_t)S, H, HD, 0, stream, (bf16_t*)x2 + row0 * r2, s_ld_rows * r2, r2, H2);
 }
 
 KAI0_API int kai0_rope_copy(const void* src, void* dst, const int32_t* pos, const float* inv_freq, int B, int S, int H, int HD,
                             int64_t src_bs, int64_t src_ld, int64_t dst_bs, int64_t dst_ld, int64_t pos_bs, int inverse,
                             kai0_stream_t stream) {
     KAI0_REQUIRE(src && dst && pos && inv_freq, "kai0_rope_copy: null operand");
-    KAI0_REQUIRE(HD % 8 == 0 && HD >= 8 && HD <= 2048 && 256 % (HD / 8) == 0, "kai0_rope_copy: HD=%d unsupported", HD);
+    KAI0_REQUIRE(rope_hd_ok(HD), "kai0_rope_copy: HD=%d unsupported", HD);
     KAI0_REQUIRE(src_ld % 4 == 0 && dst_ld % 4 == 0 && src_bs % 4 == 0 && dst_bs % 4 == 0 && ((uintptr_t)src % 8) == 0 &&
                      ((uintptr_t)dst % 8) == 0, "kai0_rope_copy: strides / bases must keep 8-byte alignment");
-    if (B * S <= 0) return 0;
-    const int rpb = 256 / (HD / 8);
-    hipLaunchKernelGGL(rope_kernel, dim3(ew_grid((int64_t)B * S, rpb)), dim3(256), 0, S_(stream), (bf16_t*)dst, (const bf16_t*)src,
-                       pos, inv_freq, B, S, dst_bs, dst_ld, src_bs, src_ld, pos_bs, H, HD, inverse);
-    return kai0_check_launch("kai0_rope_copy");
+    return rope_launch("kai0_rope_copy", (bf16_t*)dst, (const bf16_t*)src, pos, inv_freq, B, S, dst_bs, dst_ld, src_bs, src_ld, pos_bs, H, HD,
+                       inverse, stream);
 }
 
 KAI0_API int kai0_softmax_mask_fwd(const void* scores, void* probs, const int32_t* qcode, const int32_t* kcode, int B,

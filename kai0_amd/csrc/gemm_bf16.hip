@@ -1956,15 +1956,11 @@ int launch_cfg(const kai0_gemm_desc* d, GemmArgs& p, int batch, hipStream_t s) {
 #define KAI0_LAUNCH(AK, BK_)                                                                                      \
     if constexpr ((LAYOUTS & layout_bit(AK, BK_)) != 0)                                                          \
         if ((d->a_kc != 0) == AK && (d->b_kc != 0) == BK_) {                                                      \
-            static bool attr_set = false;                                                                         \
             auto kern = gemm_bf16_kernel<AK, BK_, WM, WN, MT, NT, PP, NS, BKT, SCH, CT>;                             \
-            if (!attr_set) {                                                                                      \
-                hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); \
-                if (e != hipSuccess) {                                                                            \
-                    kai0_set_error("kai0_gemm_bf16: cannot reserve %d B of LDS: %s", LDS, hipGetErrorString(e));  \
-                    return -2;                                                                                    \
-                }                                                                                                 \
-                attr_set = true;                                                                                  \
+            const hipError_t e = kai0_reserve_lds((const void*)kern, LDS);                                        \
+            if (e != hipSuccess) {                                                                                \
+                kai0_set_error("kai0_gemm_bf16: cannot reserve %d B of LDS: %s", LDS, hipGetErrorString(e));      \
+                return -2;                                                                                        \
             }                                                                                                     \
             hipLaunchKernelGGL(kern, grid, block, LDS, s, p);                                                     \
             return 0;                                                                                             \

@@ -775,34 +775,37 @@ KAI0_API int kai0_adarms_fwd(const void* x, const float* mod, void* y, void* gat
     return kai0_check_launch("kai0_adarms_fwd");
 }
 
-KAI0_API int kai0_denoise_glue_rows(const void* xs, const float* mod, int64_t mod_ld, int rows_per_batch, float eps, const float* w_out,
-                                    const float* b_out, float* x_t, float dt, const float* w_in, const float* b_in, void* xs_next,
-                                    int64_t rows, int D, int A, float* rowsq_next, int map_rpb, int64_t map_bs, int64_t map_off,
-                                    kai0_stream_t stream) {
-    CHECK_D("kai0_denoise_glue_rows", D);
+// kai0_denoise_glue and kai0_denoise_glue_rows: `who` names the entry point in the messages; the kernel takes map_rpb = 0 as the identity
+// row map, which only the entry point without a map may pass (`mapped` = false)
+static int denoise_glue_launch(const char* who, bool mapped, const void* xs, const float* mod, int64_t mod_ld, int rows_per_batch, float eps,
+                               const float* w_out, const float* b_out, float* x_t, float dt, const float* w_in, const float* b_in,
+                               void* xs_next, int64_t rows, int D, int A, float* rowsq_next, int map_rpb, int64_t map_bs, int64_t map_off,
+                               kai0_stream_t stream) {
+    KAI0_REQUIRE(D % 8 == 0 && D > 0 && D <= 2048, "%s: D=%d must be a multiple of 8, <= 2048", who, D);
     KAI0_REQUIRE(x_t && A >= 1 && A <= 64 && (xs == nullptr || (mod && w_out && b_out && rows_per_batch > 0 && mod_ld >= 2 * (int64_t)D)) &&
                      (xs_next == nullptr || (w_in && b_in)) && (xs != nullptr || xs_next != nullptr),
-                 "kai0_denoise_glue_rows: bad arguments (A <= 64; closing a step needs xs, mod, w_out, b_out; opening one w_in, b_in, xs_next)");
-    KAI0_REQUIRE(map_rpb >= 1 && map_bs >= map_rpb && map_off >= 0, "kai0_denoise_glue_rows: row map needs 1 <= rpb <= bs, off >= 0 (rpb=%d)", map_rpb);
+                 "%s: bad arguments (A <= 64; closing a step needs xs, mod, w_out, b_out; opening one w_in, b_in, xs_next)", who);
+    KAI0_REQUIRE(!mapped || (map_rpb >= 1 && map_bs >= map_rpb && map_off >= 0), "%s: row map needs 1 <= rpb <= bs, off >= 0 (rpb=%d)", who, map_rpb);
     if (rows <= 0) return 0;
     hipLaunchKernelGGL(denoise_glue_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)xs, mod,
                        mod_ld, rows_per_batch, eps, w_out, b_out, x_t, dt, w_in, b_in, (bf16_t*)xs_next, rows, D, A,
                        xs_next != nullptr ? rowsq_next : nullptr, map_rpb, map_bs, map_off);
-    return kai0_check_launch("kai0_denoise_glue_rows");
+    return kai0_check_launch(who);
+}
+
+KAI0_API int kai0_denoise_glue_rows(const void* xs, const float* mod, int64_t mod_ld, int rows_per_batch, float eps, const float* w_out,
+                                    const float* b_out, float* x_t, float dt, const float* w_in, const float* b_in, void* xs_next,
+                                    int64_t rows, int D, int A, float* rowsq_next, int map_rpb, int64_t map_bs, int64_t map_off,
+                                    kai0_stream_t stream) {
+    return denoise_glue_launch("kai0_denoise_glue_rows", true, xs, mod, mod_ld, rows_per_batch, eps, w_out, b_out, x_t, dt, w_in, b_in, xs_next,
+                               rows, D, A, rowsq_next, map_rpb, map_bs, map_off, stream);
 }
 
 KAI0_API int kai0_denoise_glue(const void* xs, const float* mod, int64_t mod_ld, int rows_per_batch, float eps, const float* w_out,
                                const float* b_out, float* x_t, float dt, const float* w_in, const float* b_in, void* xs_next,
                                int64_t rows, int D, int A, float* rowsq_next, kai0_stream_t stream) {
-    CHECK_D("kai0_denoise_glue", D);
-    KAI0_REQUIRE(x_t && A >= 1 && A <= 64 && (xs == nullptr || (mod && w_out && b_out && rows_per_batch > 0 && mod_ld >= 2 * (int64_t)D)) &&
-                     (xs_next == nullptr || (w_in && b_in)) && (xs != nullptr || xs_next != nullptr),
-                 "kai0_denoise_glue: bad arguments (A <= 64; closing a step needs xs, mod, w_out, b_out; opening one w_in, b_in, xs_next)");
-    if (rows <= 0) return 0;
-    hipLaunchKernelGGL(denoise_glue_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)xs, mod,
-                       mod_ld, rows_per_batch, eps, w_out, b_out, x_t, dt, w_in, b_in, (bf16_t*)xs_next, rows, D, A,
-                       xs_next != nullptr ? rowsq_next : nullptr, 0, 0, 0);
-    return kai0_check_launch("kai0_denoise_glue");
+    return denoise_glue_launch("kai0_denoise_glue", false, xs, mod, mod_ld, rows_per_batch, eps, w_out, b_out, x_t, dt, w_in, b_in, xs_next, rows, D,
+                               A, rowsq_next, 0, 0, 0, stream);
 }
 
 KAI0_API int kai0_adarms_combine(const float* partials, int splits, int64_t split_stride, const void* gate_prev,
@@ -824,12 +827,8 @@ KAI0_API int kai0_adarms_bwd(const void* dy, const void* dgate, const void* x, c
     KAI0_REQUIRE(rows_per_batch > 0 && rows % rows_per_batch == 0, "kai0_adarms_bwd: rows %% rows_per_batch != 0");
     const int B = (int)(rows / rows_per_batch);
     if (B <= 0) return 0;
-    static bool attr_set = false;
-    if (!attr_set) {  // 8 waves x (dscale, dshift) x D f32 = 128 KiB at D = 2048
-        hipError_t e = hipFuncSetAttribute((const void*)adarms_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 2048 * 4);
-        KAI0_REQUIRE(e == hipSuccess, "kai0_adarms_bwd: cannot reserve LDS: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    const hipError_t e = kai0_reserve_lds((const void*)adarms_bwd_kernel, 16 * 2048 * 4);  // 8 waves x (dscale, dshift) x D f32 = 128 KiB at D = 2048
+    KAI0_REQUIRE(e == hipSuccess, "kai0_adarms_bwd: cannot reserve LDS: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(adarms_bwd_kernel, dim3(B), dim3(512), 16 * D * sizeof(float), (hipStream_t)stream, (const bf16_t*)dy,
                        (const bf16_t*)dgate, (const bf16_t*)x, mod, rstd, (bf16_t*)dx, dmod, (const bf16_t*)dres, rows_per_batch, D);
     return kai0_check_launch("kai0_adarms_bwd");

@@ -249,12 +249,8 @@ KAI0_API int kai0_chunk_stats_hist(const float* state, int64_t ld_state, int ds,
     KAI0_REQUIRE(((int64_t)M + blocks - 1) / blocks * horizon + (int64_t)HIST_FRAMES * horizon <= 0xffffffffLL,
                  "kai0_chunk_stats_hist: M=%d x horizon=%d overflows a block's 32-bit counters", M, horizon);
     const int lds = hc.n * bins * 4;
-    static int reserved = 0;
-    if (lds > reserved) {
-        hipError_t e = hipFuncSetAttribute((const void*)chunk_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, HIST_LDS_BYTES);
-        KAI0_REQUIRE(e == hipSuccess, "kai0_chunk_stats_hist: cannot reserve %d B of LDS: %s", HIST_LDS_BYTES, hipGetErrorString(e));
-        reserved = HIST_LDS_BYTES;
-    }
+    const hipError_t e = kai0_reserve_lds((const void*)chunk_hist_kernel, HIST_LDS_BYTES);
+    KAI0_REQUIRE(e == hipSuccess, "kai0_chunk_stats_hist: cannot reserve %d B of LDS: %s", HIST_LDS_BYTES, hipGetErrorString(e));
     const ChunkArgs a{state, action, ep_end, frame_idx, ld_state, ld_action, ds, da, N, M, horizon, width, clip_state, clip_action, mask_state,
                       delta_mask};
     hipLaunchKernelGGL(chunk_hist_kernel, dim3(blocks, groups), dim3(HIST_THREADS), lds, (hipStream_t)stream, a, hc, edges, bins, hist);

@@ -4,6 +4,8 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
+#include <atomic>
+#include <mutex>
 
 static thread_local char g_err[512] = "";
 
@@ -21,6 +23,27 @@ int kai0_check_launch(const char* what) {
         return -2;
     }
     return 0;
+}
+
+// Keyed on the kernel's ADDRESS: two instantiations of one kernel template have the same function type (a flag local to a function
+// template over that type would be shared between them), never the same address.  Readers scan the published entries without a lock;
+// a kernel they do not find takes the mutex, sets the attribute and publishes its entry (two threads racing on a first launch both set
+// it: harmless).  Were the table ever full the attribute would be set on every call: slow, not wrong.
+static struct { const void* kernel; int bytes; } g_lds[512];
+static std::atomic<int> g_lds_n{0};
+static std::mutex g_lds_mutex;
+
+hipError_t kai0_reserve_lds(const void* kernel, int bytes) {
+    for (int i = 0, n = g_lds_n.load(std::memory_order_acquire); i < n; ++i)
+        if (g_lds[i].kernel == kernel && g_lds[i].bytes >= bytes) return hipSuccess;
+    std::lock_guard<std::mutex> lock(g_lds_mutex);
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    const int n = g_lds_n.load(std::memory_order_relaxed);
+    if (e == hipSuccess && n < (int)(sizeof(g_lds) / sizeof(g_lds[0]))) {
+        g_lds[n] = {kernel, bytes};
+        g_lds_n.store(n + 1, std::memory_order_release);
+    }
+    return e;
 }
 
 KAI0_API const char* kai0_last_error(void) { return g_err; }

@@ -639,12 +639,8 @@ int launch_skinny2(const SkinnyArgs& a, hipStream_t s) {
     const dim3 grid(a.N / (PAIR ? 32 : 16), 1, mtiles);
     auto kern = skinny2_kernel<NW, MTL, PAIR, ADA, NC, WNT, ALDS, FOLD>;
     if constexpr (LDS > 48 * 1024) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            KAI0_REQUIRE(e == hipSuccess, "kai0_gemm_skinny_bf16: cannot reserve %d B of LDS: %s", LDS, hipGetErrorString(e));
-            attr_set = true;
-        }
+        const hipError_t e = kai0_reserve_lds((const void*)kern, LDS);
+        KAI0_REQUIRE(e == hipSuccess, "kai0_gemm_skinny_bf16: cannot reserve %d B of LDS: %s", LDS, hipGetErrorString(e));
     }
     hipLaunchKernelGGL(kern, grid, dim3(NW * 64), LDS, s, a);
     return kai0_check_launch("kai0_gemm_skinny_bf16 (in-block K)");

@@ -336,8 +336,7 @@ class InferenceEngine:
             raise ValueError(f"prefix assembly: projector width {feats.shape[2]} != PaliGemma width {D}")
         tok = lang_tokens.to(torch.int64).contiguous() if lang_tokens.dtype != torch.int64 else lang_tokens.contiguous()
         table = pe.paligemma.model.language_model.embed_tokens.weight
-        _lib.call("kai0_embed_gather", table.data_ptr(), tok.data_ptr(), embs.data_ptr(), B, T, D, ops.sqrt_scale(D), P * D, ncam * n_img, D,
-                  ops._stream())  # fmt: skip
+        ops.embed_gather(table, tok, embs, ops.sqrt_scale(D), P * D, ncam * n_img, D)
         if not direct:
             for c in range(ncam):
                 ops._copy_rows(feats.reshape(ncam * B * n_img, D)[c * B * n_img :], embs, B, n_img, D, n_img * D, 0, D, P * D, c * n_img, D)
@@ -495,7 +494,7 @@ class InferenceEngine:
                                                                   guided=None, tvec=None, w_act=None)  # fmt: skip
             if self.pi05:
                 sch.times_dev = torch.tensor(times, dtype=F32).repeat_interleave(self.B).to(self.dev)
-                sch.mods, sch.mf, sch.mod_ld, sch.gates = self._modulations(sch.times_dev, len(times))
+                sch.mods, sch.mf, sch.mod_ld, sch.gates = self._modulations(sch.times_dev)
                 if self.fast:
                     sch.folded = self._fold_modulations(sch.mods, len(times))
             else:
@@ -524,14 +523,13 @@ class InferenceEngine:
                                              mf=const_rows(ex.norm), tvec=sch.tvec, w_act=sch.w_act)  # fmt: skip
         return sch.guided
 
-    def _modulations(self, tt, n: int):
-        """time embedding -> time MLP -> adaRMS `dense` for every layer and step at once (rows = step*B + b; tt: the n steps' time
+    def _modulations(self, tt):
+        """time embedding -> time MLP -> adaRMS `dense` for every layer and step at once (rows = step*B + b; tt: the steps' time
         values, each B times).  -> (mods, mf, mod_ld, gates): per-layer (input norm, post-attention norm) modulations and the final
         norm's.  Production stack: one f32 GEMM over the 37 stacked `dense` weights, mods / mf its column views of row stride mod_ld,
         gates its bf16 cast (`_gate`); generic path: one GEMM per norm, no mod_ld / gates."""
-        model, B, De = self.model, self.B, self.De
-        te = torch.empty((n * B, De), dtype=F32, device=self.dev)
-        _lib.call("kai0_time_sincos", tt.data_ptr(), te.data_ptr(), n * B, De, 4e-3, 4.0, ops._stream())
+        model, De = self.model, self.De
+        te = ops.time_sincos(tt, De)
         x = ops.silu_f32(ops.linear_f32(te, model.time_mlp_in.weight, model.time_mlp_in.bias))
         cond = ops.silu_f32(ops.linear_f32(x, model.time_mlp_out.weight, model.time_mlp_out.bias))
         if not self.fast:
@@ -626,10 +624,9 @@ class InferenceEngine:
         """pi0: the time half of `action_time_mlp_in` for every step of the schedule, tvec[step] = W_in[:, De:2De] time_emb(t_step) + b_in
         (f32 [steps, De]) — a function of the weights and the schedule only, like pi0.5's modulation table: once per engine, through
         the library's exact-f32 GEMM.  The action half W_in[:, :De] is kept as a contiguous copy next to it."""
-        model, De, n = self.model, self.De, len(times)
+        model, De = self.model, self.De
         tt = torch.tensor(times, dtype=F32).to(self.dev)
-        te = torch.empty((n, De), dtype=F32, device=self.dev)
-        _lib.call("kai0_time_sincos", tt.data_ptr(), te.data_ptr(), n, De, 4e-3, 4.0, ops._stream())
+        te = ops.time_sincos(tt, De)
         w = model.action_time_mlp_in.weight
         tvec = ops.linear_f32(te, w[:, De:].contiguous(), model.action_time_mlp_in.bias)
         return tvec, w[:, :De].contiguous()
@@ -654,16 +651,6 @@ class InferenceEngine:
         s = ops.linear_f32(state.to(F32).contiguous(), model.state_proj.weight, model.state_proj.bias)
         ops._copy_rows(ops.cast(s, BF16), xs, B, 1, De, De, 0, De, self.Ss * De, 0, De)
         return xs
-
-    def _adarms(self, xs, mod, eps: float):
-        """kai0_adarms_fwd -> (y, gate bf16 [B, De], rstd f32 [rows]); `rstd` is what the guided step's reverse sweep reads."""
-        rows, D = xs.shape
-        y = torch.empty_like(xs)
-        gate = torch.empty((self.B, D), dtype=BF16, device=self.dev)
-        rstd = torch.empty((rows,), dtype=F32, device=self.dev)
-        _lib.call("kai0_adarms_fwd", xs.data_ptr(), mod.data_ptr(), y.data_ptr(), gate.data_ptr(), rstd.data_ptr(), rows, rows // self.B, D,
-                  eps, ops._stream())  # fmt: skip
-        return y, gate, rstd
 
     def _denoise_step(self, x_t, step: int, sch, xs=None, tape: list | None = None):
         """One Euler step on the generic path (shapes the production stack was not built for) -> the velocity f32 [B, Hs, A].  Per layer:
@@ -695,9 +682,9 @@ class InferenceEngine:
 
         def norm(x, ln, mod):  # -> (y, gate | None, rstd | None)
             if ada:
-                return self._adarms(x, mod[rows], ln.eps)
+                return ops.adarms_fwd(x, mod[rows], x.shape[0] // B, ln.eps)  # (`rstd` is what the guided step's reverse sweep reads)
             if taped:
-                y, _, rstd = self._adarms(x, mod, ln.eps)
+                y, _, rstd = ops.adarms_fwd(x, mod, x.shape[0] // B, ln.eps)
                 return y, None, rstd
             return ops.rmsnorm(x, ln.weight, ln.eps), None, None
 
@@ -722,8 +709,7 @@ class InferenceEngine:
             hs, gate2, rstd2 = norm(xs, layer.post_attention_layernorm, m2)
             g = ops.linear_fwd(hs, layer.mlp.gate_proj.weight)
             u = ops.linear_fwd(hs, layer.mlp.up_proj.weight)
-            h = g if tape is None else torch.empty_like(g)  # in place, unless the sweep's kai0_geglu_bwd reads g
-            _lib.call("kai0_geglu_fwd", g.data_ptr(), u.data_ptr(), h.data_ptr(), g.numel(), ops._stream())
+            h = ops.geglu_fwd(g, u, out=g if tape is None else None)  # in place, unless the sweep's kai0_geglu_bwd reads g
             xs = ops.linear_fwd(h, layer.mlp.down_proj.weight, residual=xs, gate=gate2, gate_rpb=Hs if ada else 0)
             if tape is not None:
                 tape.append((x_in, rstd1, gate1, q_rows, att_rows, probs, x_mid, rstd2, gate2, g, u))
@@ -752,24 +738,12 @@ class InferenceEngine:
         return into
 
     def _adarms_bwd(self, dy, x, mod, rstd, dres):
-        """dx of y = adaRMS(x, mod) (+ dres, the residual branch's gradient, added inside the kernel).  The modulation's gradient is
-        not needed: it lands in a scratch buffer."""
-        rows, D = x.shape
-        dx = torch.empty_like(x)
-        dmod = torch.empty((self.B, 3 * D), dtype=F32, device=self.dev)
-        _lib.call("kai0_adarms_bwd", dy.data_ptr(), None, x.data_ptr(), mod.data_ptr(), rstd.data_ptr(), dx.data_ptr(), dmod.data_ptr(),
-                  ops._p(dres), rows, rows // self.B, D, ops._stream())  # fmt: skip
-        return dx
+        """dx of y = adaRMS(x, mod) (+ dres, the residual branch's gradient, added inside the kernel); the modulation's gradient is dropped."""
+        return ops.adarms_bwd(dy, x, mod, rstd, x.shape[0] // self.B, dres=dres)[0]
 
     def _gated_bwd(self, dout, gate):
-        """d(y) of out = x + y * gate[b]: bf16(dout * gate[b]).  kai0_gated_bwd's gate gradient (the only reader of y) is scratch: `dout`
-        stands in for y."""
-        rows, D = dout.shape
-        dy = torch.empty_like(dout)
-        dgate = torch.empty((self.B, D), dtype=BF16, device=self.dev)
-        _lib.call("kai0_gated_bwd", dout.data_ptr(), dout.data_ptr(), gate.data_ptr(), dy.data_ptr(), dgate.data_ptr(), rows, rows // self.B,
-                  D, ops._stream())  # fmt: skip
-        return dy
+        """d(y) of out = x + y * gate[b]: bf16(dout * gate[b]).  The gate's gradient (the only reader of y) is dropped: `dout` stands in for y."""
+        return ops.gated_bwd(dout, dout, gate, dout.shape[0] // self.B)[0]
 
     def _denoiser_vjp(self, cot, tape, step: int, sch):
         """(dv / dx_t)^T cot for the step `_denoise_step(..., tape)` just ran: cot f32 [B Hs, A] -> f32 [B Hs, A]; sch: the record of
@@ -814,17 +788,13 @@ class InferenceEngine:
             at, mlp = layer.self_attn, layer.mlp
             # xs = x_mid + down(geglu(gate(hs2), up(hs2))) * gate2,  hs2 = adaRMS(x_mid, m2)   (pi0: no gate)
             dh = self._dgrad(self._gated_bwd(dxs, gate2) if ada else dxs, mlp.down_proj.weight)
-            dg, du = torch.empty_like(g), torch.empty_like(u)
-            _lib.call("kai0_geglu_bwd", dh.data_ptr(), g.data_ptr(), u.data_ptr(), dg.data_ptr(), du.data_ptr(), g.numel(), ops._stream())
+            dg, du = ops.geglu_bwd(dh, g, u)
             dhs = self._dgrad(du, mlp.up_proj.weight, into=self._dgrad(dg, mlp.gate_proj.weight))
             dxs = self._adarms_bwd(dhs, x_mid, mods[l][1], rstd2, dxs)
             # x_mid = x_in + o_proj(attention(q, k, v)) * gate1,  q | k | v = rope(proj(adaRMS(x_in, m1)))
             datt = self._dgrad(self._gated_bwd(dxs, gate1) if ada else dxs, at.o_proj.weight)
-            dS = torch.empty_like(probs)
-            dq = torch.empty((M, NQ), dtype=BF16, device=dev)
-            _lib.call("kai0_attn_bwd_dq", datt.data_ptr(), att_rows.data_ptr(), probs.data_ptr(), self.k_cache[l].data_ptr(),
-                      self.v_cache[l].data_ptr(), dS.data_ptr(), dq.data_ptr(), B, R, P + Ss, HD, HD, HD, HD, S_ld, R * HD, S_ld * HD,
-                      S_ld * HD, R * S_ld, HD**-0.5, ops._stream())  # fmt: skip
+            dS, dq = ops.attn_bwd_dq_stored(datt, att_rows, probs, self.k_cache[l], self.v_cache[l], batch=B, rows=R, Sk=P + Ss, HD=HD, ldo=HD,
+                                            ldk=HD, ldv=HD, ldp=S_ld, sO=R * HD, sK=S_ld * HD, sV=S_ld * HD, sP=R * S_ld, scale=HD**-0.5)
             dkv = torch.empty((2, B, kw, HD), dtype=BF16, device=dev)
             for dst, a_t, b_t in ((dkv[0], dS, q_rows), (dkv[1], probs, datt)):  # dK = dS^T Q, dV = P^T dO over the suffix key columns
                 gemm(a_t, b_t, dst, M=kw, N=HD, K=R, a_kc=False, b_kc=False, lda=S_ld, ldb=HD, ldc=HD, batch=B, sA=(R * S_ld, 0),
@@ -845,8 +815,7 @@ class InferenceEngine:
         ops._copy_rows(dxs, dy, B, Hs, De, Ss * De, Ss - Hs, De, Hs * De, 0, De)
         dh = torch.empty((Ma, De), dtype=F32, device=dev)
         ops.gemm_f32(ops.cast(dy, F32), De, 1, model.action_time_mlp_out.weight, De, 1, dh, Ma, De, De)
-        dpre = torch.empty_like(dh)
-        _lib.call("kai0_silu_bwd_f32", dh.data_ptr(), pre.data_ptr(), dpre.data_ptr(), dh.numel(), ops._stream())
+        dpre = ops.silu_bwd_f32(dh, pre)
         da = torch.empty_like(dh)
         ops.gemm_f32(dpre, De, 1, sch.w_act, De, 1, da, Ma, De, De)
         ops.gemm_f32(da, De, 1, model.action_in_proj.weight, A, 1, jte, Ma, A, De)

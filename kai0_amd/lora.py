@@ -361,8 +361,7 @@ class LoraGegluMlpFn(torch.autograd.Function):
         lora_down(x, agu, Tgu, M=M, K=D, R=2 * r, ldx=D, lda=D, ldt=2 * r)
         _up_acc(Tgu, Ag, g, t_off=0, ldt=2 * r)
         _up_acc(Tgu, Au, u, t_off=r, ldt=2 * r)
-        h = torch.empty_like(g)
-        _lib.call("kai0_geglu_fwd", g.data_ptr(), u.data_ptr(), h.data_ptr(), g.numel(), _stream())
+        h = ops.geglu_fwd(g, u)
         y = ops.linear_fwd(h, wd)
         Td = _down(h, Ad)
         _up_acc(Td, Ad, y)

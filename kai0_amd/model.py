@@ -33,7 +33,7 @@ import math
 import torch
 from torch import nn
 
-from . import _lib, ops
+from . import ops
 from . import lora as lora_ops
 from .config import Pi0Config, SiglipConfig, get_config
 from .preprocessing import IMAGE_KEYS, preprocess_observation
@@ -720,8 +720,7 @@ class PI0Pytorch(nn.Module):
         cond f32 [B, De].  pi0: [B, 1 + H, De] = state token | action-time tokens, att [1, 1, 0, ...], cond None."""
         B, Hs, A = noisy_actions.shape
         De = self.action_in_proj.out_features
-        te = torch.empty((B, De), dtype=F32, device=noisy_actions.device)
-        _lib.call("kai0_time_sincos", timestep.contiguous().data_ptr(), te.data_ptr(), B, De, 4e-3, 4.0, ops._stream())
+        te = ops.time_sincos(timestep.contiguous(), De)
         if not self.pi05:
             a = ops.linear_f32(noisy_actions.reshape(B * Hs, A).contiguous(), self.action_in_proj.weight, self.action_in_proj.bias)
             # cat([action_emb, time_emb]) -> action_time_mlp_in -> SiLU -> action_time_mlp_out, all f32 (:275-285); cat is host glue

@@ -907,6 +907,26 @@ def rmsnorm(x, w, eps=1e-6):
     return RMSNormFn.apply(x, w, eps)[1]
 
 
+def adarms_fwd(x, mod, rows_per_batch: int, eps: float):
+    """kai0_adarms_fwd -> (y, gate bf16 [rows / rows_per_batch, D], rstd f32 [rows]); mod f32 [rows / rows_per_batch, 3 D]."""
+    rows, D = x.shape
+    y = torch.empty_like(x)
+    gate = torch.empty((rows // rows_per_batch, D), dtype=BF16, device=x.device)
+    rstd = torch.empty((rows,), dtype=F32, device=x.device)
+    _lib.call("kai0_adarms_fwd", x.data_ptr(), mod.data_ptr(), y.data_ptr(), gate.data_ptr(), rstd.data_ptr(), rows, rows_per_batch, D, eps, _stream())
+    return y, gate, rstd
+
+
+def adarms_bwd(dy, x, mod, rstd, rows_per_batch: int, dgate=None, dres=None):
+    """kai0_adarms_bwd -> (dx, dmod f32 [rows / rows_per_batch, 3 D]); dres: the residual branch's gradient, added into dx by the kernel."""
+    rows, D = x.shape
+    dx = torch.empty_like(x)
+    dmod = torch.empty((rows // rows_per_batch, 3 * D), dtype=F32, device=x.device)
+    _lib.call("kai0_adarms_bwd", dy.data_ptr(), _p(dgate), x.data_ptr(), mod.data_ptr(), rstd.data_ptr(), dx.data_ptr(), dmod.data_ptr(), _p(dres), rows,
+              rows_per_batch, D, _stream())  # fmt: skip
+    return dx, dmod
+
+
 class AdaRMSFn(torch.autograd.Function):
     """adaRMSNorm given the precomputed modulation `mod` = dense(cond) [B, 3D] f32.  Returns (x, y, gate); x is passed
     through for the residual branch (see RMSNormFn)."""
@@ -915,13 +935,7 @@ class AdaRMSFn(torch.autograd.Function):
     def forward(ctx, x, mod, rows_per_batch: int, eps: float):
         _chk(x, BF16, "adarms.x")
         _chk(mod, F32, "adarms.mod")
-        rows, D = x.shape
-        Bn = rows // rows_per_batch
-        y = torch.empty_like(x)
-        gate = torch.empty((Bn, D), dtype=BF16, device=x.device)
-        rstd = torch.empty((rows,), dtype=F32, device=x.device)
-        _lib.call("kai0_adarms_fwd", x.data_ptr(), mod.data_ptr(), y.data_ptr(), gate.data_ptr(), rstd.data_ptr(), rows,
-                  rows_per_batch, D, eps, _stream())  # fmt: skip
+        y, gate, rstd = adarms_fwd(x, mod, rows_per_batch, eps)
         ctx.save_for_backward(x, mod, rstd)
         ctx.rpb = rows_per_batch
         return x.view_as(x), y, gate
@@ -929,16 +943,12 @@ class AdaRMSFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dres, dy, dgate):
         x, mod, rstd = ctx.saved_tensors
-        rows, D = x.shape
         if dy is None:
             dy = torch.zeros_like(x)
         dy = dy.contiguous()
         dgate = dgate.contiguous() if dgate is not None else None
         dres = dres.contiguous() if dres is not None else None
-        dx = torch.empty_like(x)
-        dmod = torch.empty_like(mod)
-        _lib.call("kai0_adarms_bwd", dy.data_ptr(), _p(dgate), x.data_ptr(), mod.data_ptr(), rstd.data_ptr(),
-                  dx.data_ptr(), dmod.data_ptr(), _p(dres), rows, ctx.rpb, D, _stream())  # fmt: skip
+        dx, dmod = adarms_bwd(dy, x, mod, rstd, ctx.rpb, dgate, dres)
         return dx, dmod, None, None
 
 
@@ -994,25 +1004,33 @@ def layernorm(x, w, b, eps=1e-6):
     return LayerNormFn.apply(x, w, b, eps)[1]
 
 
+def geglu_fwd(g, u, out=None):
+    """kai0_geglu_fwd: h = bf16(bf16(gelu_tanh(g)) * u) into `out` (which may be g: in place), a new tensor by default."""
+    h = torch.empty_like(g) if out is None else out
+    _lib.call("kai0_geglu_fwd", g.data_ptr(), u.data_ptr(), h.data_ptr(), g.numel(), _stream())
+    return h
+
+
+def geglu_bwd(dh, g, u):
+    """kai0_geglu_bwd -> (dg, du)."""
+    dg, du = torch.empty_like(g), torch.empty_like(u)
+    _lib.call("kai0_geglu_bwd", dh.data_ptr(), g.data_ptr(), u.data_ptr(), dg.data_ptr(), du.data_ptr(), g.numel(), _stream())
+    return dg, du
+
+
 class GegluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, g, u):
         _chk(g, BF16, "geglu.g")
         _chk(u, BF16, "geglu.u")
-        h = torch.empty_like(g)
-        _lib.call("kai0_geglu_fwd", g.data_ptr(), u.data_ptr(), h.data_ptr(), g.numel(), _stream())
+        h = geglu_fwd(g, u)
         ctx.save_for_backward(g, u)
         return h
 
     @staticmethod
     def backward(ctx, dh):
         g, u = ctx.saved_tensors
-        dh = dh.contiguous()
-        dg = torch.empty_like(g)
-        du = torch.empty_like(u)
-        _lib.call("kai0_geglu_bwd", dh.data_ptr(), g.data_ptr(), u.data_ptr(), dg.data_ptr(), du.data_ptr(), g.numel(),
-                  _stream())  # fmt: skip
-        return dg, du
+        return geglu_bwd(dh.contiguous(), g, u)
 
 
 def geglu(g, u):
@@ -1188,6 +1206,14 @@ def geglu_mlp(x, wg, wu, wd, residual=None):
     return GegluMlpFn.apply(x, wg, wu, wd, residual)
 
 
+def gated_bwd(dout, y, gate, rows_per_batch: int):
+    """kai0_gated_bwd, the backward of out = x + y * gate[b] -> (dy = bf16(dout * gate[b]), dgate like gate); y is read for dgate only."""
+    rows, D = y.shape
+    dy, dgate = torch.empty_like(y), torch.empty_like(gate)
+    _lib.call("kai0_gated_bwd", dout.data_ptr(), y.data_ptr(), gate.data_ptr(), dy.data_ptr(), dgate.data_ptr(), rows, rows_per_batch, D, _stream())
+    return dy, dgate
+
+
 class GatedResidualFn(torch.autograd.Function):
     """out = x + y * gate[b]  (modeling_gemma.py:209-227), gate [B, D] broadcast over the rows of batch b."""
 
@@ -1205,16 +1231,19 @@ class GatedResidualFn(torch.autograd.Function):
     def backward(ctx, dout):
         y, gate = ctx.saved_tensors
         dout = dout.contiguous()
-        rows, D = y.shape
-        dy = torch.empty_like(y)
-        dgate = torch.empty_like(gate)
-        _lib.call("kai0_gated_bwd", dout.data_ptr(), y.data_ptr(), gate.data_ptr(), dy.data_ptr(), dgate.data_ptr(), rows,
-                  ctx.rpb, D, _stream())  # fmt: skip
+        dy, dgate = gated_bwd(dout, y, gate, ctx.rpb)
         return dout, dy, dgate, None
 
 
 def gated_residual(x, y, gate, rows_per_batch):
     return GatedResidualFn.apply(x, y, gate, rows_per_batch)
+
+
+def silu_bwd_f32(dy, x):
+    """kai0_silu_bwd_f32 -> dx = dy * silu'(x), f32."""
+    dx = torch.empty_like(x)
+    _lib.call("kai0_silu_bwd_f32", dy.data_ptr(), x.data_ptr(), dx.data_ptr(), x.numel(), _stream())
+    return dx
 
 
 class SiluF32Fn(torch.autograd.Function):
@@ -1229,10 +1258,7 @@ class SiluF32Fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        _lib.call("kai0_silu_bwd_f32", dy.data_ptr(), x.data_ptr(), dx.data_ptr(), x.numel(), _stream())
-        return dx
+        return silu_bwd_f32(dy.contiguous(), x)
 
 
 def silu_f32(x):
@@ -1271,6 +1297,19 @@ def cast_ag(x, dtype):
     return CastFn.apply(x, dtype == BF16)
 
 
+def embed_gather(table, tokens, out, scale: float, out_bs: int, out_row0: int, out_ld: int):
+    """kai0_embed_gather: out[b][out_row0 + t] = bf16(table[tokens[b][t]] * scale), int64 tokens [B, T]; out_bs / out_ld in elements."""
+    Bn, T = tokens.shape
+    _lib.call("kai0_embed_gather", table.data_ptr(), tokens.data_ptr(), out.data_ptr(), Bn, T, table.shape[1], scale, out_bs, out_row0, out_ld, _stream())
+
+
+def time_sincos(t, De: int):
+    """kai0_time_sincos: the sinusoidal time embedding f32 [t.numel(), De] of the contiguous f32 time values `t` (periods 4e-3 .. 4)."""
+    te = torch.empty((t.numel(), De), dtype=F32, device=t.device)
+    _lib.call("kai0_time_sincos", t.data_ptr(), te.data_ptr(), t.numel(), De, 4e-3, 4.0, _stream())
+    return te
+
+
 class EmbedFn(torch.autograd.Function):
     """embed_tokens(tokens) * sqrt(D)  (gemma_pytorch.py:88-89; pi0_pytorch.py:213-216) -> [B*T, D] bf16."""
 
@@ -1282,8 +1321,7 @@ class EmbedFn(torch.autograd.Function):
         Bn, T = tokens.shape
         D = table.shape[1]
         out = torch.empty((Bn * T, D), dtype=BF16, device=table.device)
-        _lib.call("kai0_embed_gather", table.data_ptr(), tokens.data_ptr(), out.data_ptr(), Bn, T, D, scale, T * D, 0, D,
-                  _stream())  # fmt: skip
+        embed_gather(table, tokens, out, scale, T * D, 0, D)
         ctx.save_for_backward(tokens)
         ctx.table = table
         ctx.shape = table.shape
@@ -1410,34 +1448,11 @@ def round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
-def attn_fwd_keysplit(Q, K, V, O, *, rows, Sk, HD, H, q0, ldk, ldv, qcode, kcode, scale, q_off, o_off, parts: int = 4):
-    """One batch entry's masked attention with the keys cut into `parts` equal ranges (kai0_attn_fwd over the ranges as batch
-    entries + kai0_attn_combine): for grids whose row blocks alone cannot fill the chip (the B = 1 prefix pass).  Q rows are the folded
-    (position, head) rows at Q + q_off, contiguous [rows, HD]; O likewise at O + o_off; qcode / kcode 1-D views of this entry's codes."""
-    if Sk % parts != 0:
-        raise ValueError("attn_fwd_keysplit: Sk must be a multiple of the number of key ranges")
-    rng = Sk // parts
-    dev = Q.device
-    o_parts = torch.empty((parts, rows, HD), dtype=BF16, device=dev)
-    lse = torch.empty((parts, rows), dtype=torch.float32, device=dev)
-    d = AttnDesc()
-    d.Q, d.K, d.V, d.O = Q.data_ptr() + 2 * q_off, K.data_ptr(), V.data_ptr(), o_parts.data_ptr()
-    d.qcode, d.kcode = _p(qcode), _p(kcode)
-    d.rows, d.Sk, d.HD, d.H, d.q0, d.batch, d.batch_inner = rows, rng, HD, H, q0, parts, 1
-    d.ldq, d.ldk, d.ldv, d.ldo = HD, ldk, ldv, HD
-    d.sQ1, d.sK1, d.sV1, d.sO1 = 0, rng * ldk, rng * ldv, rows * HD
-    d.qcode_ld, d.kcode_ld = 0, rng
-    d.scale = scale
-    d.online = 1
-    d.lse, d.s_lse = lse.data_ptr(), rows
-    _lib.call("kai0_attn_fwd", C.byref(d), _stream())
-    _lib.call("kai0_attn_combine", o_parts.data_ptr(), lse.data_ptr(), O.data_ptr() + 2 * o_off, parts, rows, HD, HD, rows * HD, rows, _stream())
-
-
-def attn_fwd(Q, K, V, O, P, *, rows, Sk, HD, H=1, q0=0, batch=1, batch_inner=1, ldq, ldk, ldv, ldo, ldp=0, sQ=(0, 0),
-             sK=(0, 0), sV=(0, 0), sO=(0, 0), sP=0, qcode=None, kcode=None, scale, q_off=0, o_off=0, lse=None, online=0):
-    """kai0_attn_fwd (fused logits + mask + softmax + P V).  P: optional probabilities output (the exact two-pass form);
-    lse: optional f32 [batch, >= rows] log-sum-exp output — what the recompute backward needs instead of P."""
+def _attn_desc(Q, K, V, O, P, *, rows, Sk, HD, H=1, q0=0, batch=1, batch_inner=1, ldq, ldk, ldv, ldo, ldp=0, sQ=(0, 0),
+               sK=(0, 0), sV=(0, 0), sO=(0, 0), sP=0, qcode=None, kcode=None, code_ld=None, scale, q_off=0, o_off=0, lse=None, online=0) -> AttnDesc:
+    """The ONE place that fills a kai0_attn_desc.  P: optional probabilities output (the exact two-pass form); lse: optional f32
+    [batch, >= rows] log-sum-exp output — what the recompute backward needs instead of P.  q_off / o_off: element offsets into Q / O;
+    code_ld: the batch strides of (qcode, kcode) where they are not the tensors' own."""
     d = AttnDesc()
     d.Q, d.K, d.V, d.O = Q.data_ptr() + 2 * q_off, K.data_ptr(), V.data_ptr(), O.data_ptr() + 2 * o_off
     d.P = _p(P)
@@ -1449,14 +1464,38 @@ def attn_fwd(Q, K, V, O, P, *, rows, Sk, HD, H=1, q0=0, batch=1, batch_inner=1, 
     d.sV1, d.sV2 = sV
     d.sO1, d.sO2 = sO
     d.sP = sP
-    if qcode is not None:
-        d.qcode_ld, d.kcode_ld = qcode.stride(0), kcode.stride(0)
+    if code_ld is None and qcode is not None:
+        code_ld = qcode.stride(0), kcode.stride(0)
+    d.qcode_ld, d.kcode_ld = code_ld or (0, 0)
     d.scale = scale
     d.online = online
     if lse is not None:
         _chk(lse, torch.float32, "lse")
         d.lse, d.s_lse = lse.data_ptr(), lse.stride(0)
+    return d
+
+
+def attn_fwd_keysplit(Q, K, V, O, *, rows, Sk, HD, H, q0, ldk, ldv, qcode, kcode, scale, q_off, o_off, parts: int = 4):
+    """One batch entry's masked attention with the keys cut into `parts` equal ranges (kai0_attn_fwd over the ranges as batch
+    entries + kai0_attn_combine): for grids whose row blocks alone cannot fill the chip (the B = 1 prefix pass).  Q rows are the folded
+    (position, head) rows at Q + q_off, contiguous [rows, HD]; O likewise at O + o_off; qcode / kcode 1-D views of this entry's codes."""
+    if Sk % parts != 0:
+        raise ValueError("attn_fwd_keysplit: Sk must be a multiple of the number of key ranges")
+    rng = Sk // parts
+    dev = Q.device
+    o_parts = torch.empty((parts, rows, HD), dtype=BF16, device=dev)
+    lse = torch.empty((parts, rows), dtype=torch.float32, device=dev)
+    # the ranges as batch entries: they share the queries and their codes (stride 0) and step K / V / the key codes by a range
+    d = _attn_desc(Q, K, V, o_parts, None, rows=rows, Sk=rng, HD=HD, H=H, q0=q0, batch=parts, ldq=HD, ldk=ldk, ldv=ldv, ldo=HD,
+                   sK=(rng * ldk, 0), sV=(rng * ldv, 0), sO=(rows * HD, 0), qcode=qcode, kcode=kcode, code_ld=(0, rng), scale=scale,
+                   q_off=q_off, lse=lse, online=1)
     _lib.call("kai0_attn_fwd", C.byref(d), _stream())
+    _lib.call("kai0_attn_combine", o_parts.data_ptr(), lse.data_ptr(), O.data_ptr() + 2 * o_off, parts, rows, HD, HD, rows * HD, rows, _stream())
+
+
+def attn_fwd(Q, K, V, O, P, **kw):
+    """kai0_attn_fwd (fused logits + mask + softmax + P V); the keywords are `_attn_desc`'s."""
+    _lib.call("kai0_attn_fwd", C.byref(_attn_desc(Q, K, V, O, P, **kw)), _stream())
 
 
 # KAI0_ATTN_STORE_P=1: the round-3 training attention (exact two-pass forward that stores P, backward reads it) for A/B runs
@@ -1472,19 +1511,13 @@ def mqa_attention_fwd(q_all, k_all, v_all, qcode, kcode, Bn, Sq, q0, Sk, S_ld, H
     no probabilities) the second value is lse f32 [B, Sq*H] instead."""
     dev = q_all.device
     M = Sq * H
-    if want_lse:
-        lse = torch.empty((Bn, M), dtype=torch.float32, device=dev)
-        att = torch.empty((Bn, S_ld, H * HD), dtype=BF16, device=dev)
-        attn_fwd(q_all, k_all, v_all, att, None, rows=M, Sk=Sk, HD=HD, H=H, q0=q0, batch=Bn, ldq=HD, ldk=HD, ldv=HD, ldo=HD,
-                 sQ=(S_ld * H * HD, 0), sK=(S_ld * HD, 0), sV=(S_ld * HD, 0), sO=(S_ld * H * HD, 0), qcode=qcode, kcode=kcode,
-                 scale=scale, q_off=q0 * H * HD, o_off=q0 * H * HD, lse=lse)
-        return att, lse
-    probs = torch.empty((Bn, M, S_ld), dtype=BF16, device=dev) if want_probs else None
+    lse = torch.empty((Bn, M), dtype=torch.float32, device=dev) if want_lse else None
+    probs = torch.empty((Bn, M, S_ld), dtype=BF16, device=dev) if want_probs and not want_lse else None
     att = torch.empty((Bn, S_ld, H * HD), dtype=BF16, device=dev)
     attn_fwd(q_all, k_all, v_all, att, probs, rows=M, Sk=Sk, HD=HD, H=H, q0=q0, batch=Bn, ldq=HD, ldk=HD, ldv=HD, ldo=HD,
-             ldp=S_ld, sQ=(S_ld * H * HD, 0), sK=(S_ld * HD, 0), sV=(S_ld * HD, 0), sO=(S_ld * H * HD, 0), sP=M * S_ld,
-             qcode=qcode, kcode=kcode, scale=scale, q_off=q0 * H * HD, o_off=q0 * H * HD)
-    return att, probs
+             ldp=0 if want_lse else S_ld, sQ=(S_ld * H * HD, 0), sK=(S_ld * HD, 0), sV=(S_ld * HD, 0), sO=(S_ld * H * HD, 0),
+             sP=0 if want_lse else M * S_ld, qcode=qcode, kcode=kcode, scale=scale, q_off=q0 * H * HD, o_off=q0 * H * HD, lse=lse)
+    return att, lse if want_lse else probs
 
 
 def _attn_bwd_split(Bn: int, S_ld: int, HD: int, M: int) -> int:
@@ -1493,6 +1526,16 @@ def _attn_bwd_split(Bn: int, S_ld: int, HD: int, M: int) -> int:
     if t256 >= 160 or M < 4096:
         return 1
     return max(1, min(8, -(-256 // t256), M // 2048))
+
+
+def attn_bwd_dq_stored(datt, att, probs, k, v, *, batch, rows, Sk, HD, ldo, ldk, ldv, ldp, sO, sK, sV, sP, scale):
+    """kai0_attn_bwd_dq, the query side of the attention backward over STORED probabilities -> (dS like probs, dQ like datt).  datt, att and
+    dQ: folded rows of HD elements (row stride ldo, batch stride sO); probs: [batch][rows][ldp]; strides in elements (kai0hip.h)."""
+    dS = torch.empty_like(probs)
+    dQ = torch.empty_like(datt)
+    _lib.call("kai0_attn_bwd_dq", datt.data_ptr(), att.data_ptr(), probs.data_ptr(), k.data_ptr(), v.data_ptr(), dS.data_ptr(),
+              dQ.data_ptr(), batch, rows, Sk, HD, ldo, ldk, ldv, ldp, sO, sK, sV, sP, scale, _stream())  # fmt: skip
+    return dS, dQ
 
 
 def _joint_attention_grads(cfg, pos, inv_freq, dq_all, dk_all, dv_all):
@@ -1571,8 +1614,8 @@ class JointAttentionFn(torch.autograd.Function):
         Bn, S, S_ld, H, HD, seg_lens, scale, recompute = ctx.cfg
         dev = q_all.device
         M = S * H
-        dq_all = torch.empty((Bn, S_ld, H * HD), dtype=BF16, device=dev)
         if recompute:
+            dq_all = torch.empty((Bn, S_ld, H * HD), dtype=BF16, device=dev)
             # P and dS side by side, dV and dK likewise: the two TN GEMMs that consume them run as ONE batched launch below
             pd = torch.empty((2, Bn, M, S_ld), dtype=BF16, device=dev)
             lse, probs, dscores = probs, pd[0], pd[1]
@@ -1616,11 +1659,9 @@ class JointAttentionFn(torch.autograd.Function):
         gemm(probs, datt, dv_all, M=S_ld, N=HD, K=M, a_kc=False, b_kc=False, lda=S_ld, ldb=HD, ldc=HD, batch=Bn,
              sA=(M * S_ld, 0), sB=(S_ld * H * HD, 0), sC=(S_ld * HD, 0), split_k=kv_split)  # fmt: skip
         if not recompute:
-            dscores = torch.empty_like(probs)
             # stored-P form (KAI0_ATTN_STORE_P=1): one launch — D = rowsum(dO * O), dP = dO V^T in f32, dS written once, dQ = dS K on chip
-            _lib.call("kai0_attn_bwd_dq", datt.data_ptr(), att.data_ptr(), probs.data_ptr(), k_all.data_ptr(), v_all.data_ptr(),
-                      dscores.data_ptr(), dq_all.data_ptr(), Bn, M, S, HD, HD, HD, HD, S_ld, S_ld * H * HD, S_ld * HD, S_ld * HD,
-                      M * S_ld, scale, _stream())  # fmt: skip
+            dscores, dq_all = attn_bwd_dq_stored(datt, att, probs, k_all, v_all, batch=Bn, rows=M, Sk=S, HD=HD, ldo=HD, ldk=HD, ldv=HD,
+                                                 ldp=S_ld, sO=S_ld * H * HD, sK=S_ld * HD, sV=S_ld * HD, sP=M * S_ld, scale=scale)
         # dK[b] [S_ld, HD] = dS[b]^T [S_ld, M] @ Q[b] [M, HD]
         dk_all = torch.empty((Bn, S_ld, HD), dtype=BF16, device=dev)
         gemm(dscores, q_all, dk_all, M=S_ld, N=HD, K=M, a_kc=False, b_kc=False, lda=S_ld, ldb=HD, ldc=HD, batch=Bn,
