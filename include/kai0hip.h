@@ -25,7 +25,7 @@ extern "C" {
 typedef void* kai0_stream_t; /* hipStream_t */
 
 const char* kai0_last_error(void);
-/* returns 2; what changed since version 1: INTEGRATION.md section 2.  Bindings check it at load time. */
+/* returns 3; what changed since versions 1 and 2: INTEGRATION.md section 2.  Bindings check it at load time. */
 int kai0_abi_version(void);
 /* device properties probe: writes CU count, LDS bytes/CU, gcnArchName (<=63 chars) */
 int kai0_device_info(int device, int* n_cu, int* lds_bytes, char* arch_name64);
@@ -458,17 +458,18 @@ int kai0_softmax_mask_fwd(const void* scores, void* probs, const int32_t* qcode,
                           int64_t qcode_ld, int64_t kcode_ld, kai0_stream_t stream);
 /* Backward of SigLIP's unmasked multi-head attention for one layer, one block per (image, head)
  * (modeling_siglip.py:325-345 through autograd; S = 256 tokens, head_dim = 72 — the so400m/14 @ 224 tower):
- *   q, k, v, dO, O : bf16 [n_img*S][NH*HD] (head h at column h*HD);  P : bf16 [n_img*NH][S][ldp] from kai0_attn_fwd
+ *   q, k, v, dO, O : bf16 [n_img*S][NH*HD] (head h at column h*HD)
+ *   lse : f32 [n_img * NH][S], the log-sum-exp of every row's logits from kai0_siglip_attn_fwd or kai0_attn_fwd (kai0_attn_desc.lse):
+ *         no probabilities are stored, P = bf16(exp(bf16(bf16(q k^T) * scale) - lse[row])) is recomputed inside the block from the
+ *         q / k tiles that are in LDS anyway
  *   dq, dk, dv : bf16 rows of stride ld_grad (0 = NH*HD; 3*NH*HD when the three are the column slices of one [rows][3*NH*HD]
  *                buffer, which lets the fused q|k|v projection backward read them as a single operand)
  *   D = rowsum(dO * O);  dS = bf16((P * (dO V^T - D)) * scale)  (dP in f32, never stored);
  *   dQ = bf16(dS K), dK = bf16(dS^T Q), dV = bf16(P^T dO).  Same rounding points as the GEMM formulation
- *   (kai0_gemm_bf16 act 4 + three batched GEMMs) it replaces. */
-int kai0_siglip_attn_bwd(const void* q, const void* k, const void* v, const void* dO, const void* O, const void* P,
-                         void* dq, void* dk, void* dv, int n_img, int S, int NH, int HD, int64_t ldp, int64_t ld_grad,
-                         float scale, kai0_stream_t stream);
-/* The same without stored probabilities (round 4): P = bf16(exp(bf16(bf16(q k^T) * scale) - lse[row])) is recomputed inside the
- * block from the q / k tiles that are in LDS anyway; lse: f32 [n_img * NH][S] from kai0_attn_fwd (kai0_attn_desc.lse). */
+ *   (kai0_gemm_bf16 act 4 + three batched GEMMs) it replaces.  (Version 2's kai0_siglip_attn_bwd read stored probabilities.) */
+int kai0_siglip_attn_bwd2(const void* q, const void* k, const void* v, const void* dO, const void* O, const float* lse,
+                          void* dq, void* dk, void* dv, int n_img, int S, int NH, int HD, int64_t ld_grad, float scale,
+                          kai0_stream_t stream);
 /* SigLIP's attention forward at the real tower's shape (S = 256 tokens, head_dim = 72; modeling_siglip.py:325-345), one block per
  * (image, head) with the head's K and V unpadded in LDS: logits = bf16(bf16(q k^T) * scale), EXACT softmax in f32 (the whole row is
  * on chip), P = bf16(softmax), O = bf16(P V) — the reference's rounding order, in one pass, no P written.
@@ -477,9 +478,6 @@ int kai0_siglip_attn_bwd(const void* q, const void* k, const void* v, const void
 int kai0_siglip_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int n_img, int S, int NH, int HD,
                          int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t sq, int64_t sk, int64_t sv, int64_t so,
                          float scale, kai0_stream_t stream);
-int kai0_siglip_attn_bwd2(const void* q, const void* k, const void* v, const void* dO, const void* O, const float* lse,
-                          void* dq, void* dk, void* dv, int n_img, int S, int NH, int HD, int64_t ld_grad, float scale,
-                          kai0_stream_t stream);
 /* out[r] = sum_d a[r][d] * b[r][d] in f32 (rows of D contiguous bf16 elements, D % 8 == 0): the softmax-backward row term */
 int kai0_rowdot_bf16(const void* a, const void* b, float* out, int64_t rows, int D, kai0_stream_t stream);
 /* dscores = bf16( (probs * (dprobs - sum_j dprobs*probs)) * scale ).  dprobs is bf16 or (dprobs_f32) f32:

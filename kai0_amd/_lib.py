@@ -12,7 +12,7 @@ import pathlib
 
 _HERE = pathlib.Path(__file__).resolve().parent
 LIB_PATH = _HERE / "lib" / "libkai0hip.so"
-ABI_VERSION = 2  # what kai0_abi_version() must return: the version these mirrors and prototypes describe
+ABI_VERSION = 3  # what kai0_abi_version() must return: the version these mirrors and prototypes describe
 
 c_p = C.c_void_p
 c_i = C.c_int
@@ -198,7 +198,6 @@ _PROTOS: dict[str, list] = {
     "kai0_rope_inplace2": [c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_i64, c_i64, c_i, c_p],
     "kai0_rope_copy": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_i64, c_i64, c_i64, c_i64, c_i, c_p],
     "kai0_softmax_mask_fwd": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_i64, c_i, c_i64, c_i64, c_p],
-    "kai0_siglip_attn_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_i64, c_f, c_p],
     "kai0_rowdot_bf16": [c_p, c_p, c_p, c_i64, c_i, c_p],
     "kai0_softmax_bwd": [c_p, c_p, c_i, c_p, c_i64, c_i, c_i64, c_f, c_p],
     "kai0_geglu_fwd": [c_p, c_p, c_p, c_i64, c_p],

@@ -3,25 +3,28 @@
 // Replaces eager_attention_forward (modeling_gemma.py:230-253; modeling_siglip.py:325-345) with its exact rounding
 // points: logits = bf16(bf16(Q K^T) * scale), softmax in f32, P = bf16(softmax), O = bf16(P V).
 //
-// gfx950 design:
-//   * training (round 4): ONE pass with an online softmax (OP = -1): per key tile the logits are computed once, the running row
-//     max m and row sum l are updated, O is rescaled by exp(m_old - m_new) when a row's max moved, P~ = bf16(exp(s - m)) goes
-//     straight into P V; at the end O /= l and lse = m + log(l) is written per row.  NO probabilities leave the chip: the
-//     backward recomputes them from Q, K and lse (attn_bwd.hip, attn_siglip.hip).  The logits keep the reference's rounding
-//     (bf16(bf16(Q K^T) * scale)); the point where P is rounded to bf16 moves from "after the normalisation" to "before" —
-//     inside the stated floating-point tolerance, not bit-identical to eager_attention_forward.
-//   * the former "two-pass" form (OP = 0: pass 1 row max / row sum, pass 2 recomputes the logits, writes the FINAL normalised P
-//     and accumulates O with that bf16 P — bitwise the reference's rounding order) is kept for callers that ask for P and as the
-//     A/B alternative (ops.py: KAI0_ATTN_STORE_P=1).
+// gfx950 design — three forms of one kernel (OP), chosen by kai0_attn_fwd:
+//   * one pass with an online softmax (OP = -1), whenever the caller does not ask for P — training: per key tile the logits are
+//     computed once, the running row max m and row sum l are updated, O is rescaled by exp(m_old - m_new) when a row's max
+//     moved, P~ = bf16(exp(s - m)) goes straight into P V; at the end O /= l and lse = m + log(l) is written per row.  NO
+//     probabilities leave the chip: the backward recomputes them from Q, K and lse (attn_bwd.hip, attn_siglip.hip).  The logits
+//     keep the reference's rounding (bf16(bf16(Q K^T) * scale)); the point where P is rounded to bf16 moves from "after the
+//     normalisation" to "before" — inside the stated floating-point tolerance, not bit-identical to
+//     eager_attention_forward.
+//   * two passes (OP = 0), when the caller asks for P (sequences too long for the recompute backward, the guided inference step):
+//     pass 1 row max / row sum, pass 2 recomputes the logits, writes the FINAL normalised P and accumulates O with that bf16 P —
+//     bitwise the reference's rounding order.
+//   * resident (OP = 4), for <= 256 keys at HD <= 128 on small grids: all key tiles staged at once, the whole row of logits in
+//     registers — exact like the two-pass form, and one pass.
 //   * transposed orientation: S^T = K Q^T and O^T = V^T P^T.  The C-layout of S^T (lane = query column, registers =
 //     4 consecutive keys) IS the B-operand layout of the second MFMA, so P never leaves registers; softmax statistics
 //     are per lane (no cross-lane traffic in the key loop); V^T comes from a row-major V tile through
 //     ds_read_b64_tr_b16.
 //   * multi-query folding: the caller presents the H query heads of a position as extra rows (rows = Sq*H), so one
 //     K/V tile in LDS serves all heads.
-//   * block = 4 waves, one per SIMD (512-register budget): each wave owns 32 query rows, Q fragments stay in VGPRs;
-//     K (K-contiguous sub-tiles) and V (contraction-strided tile) arrive by LDS-DMA, double-buffered, zero-filled at
-//     the edges by the buffer descriptor.
+//   * block = 128 query rows on 8 waves, two per SIMD, so that one wave's MFMAs overlap the other's softmax VALU work and LDS
+//     reads: each wave owns 16 query rows, Q fragments stay in VGPRs; K (K-contiguous sub-tiles) and V (contraction-strided
+//     tile) arrive by LDS-DMA, double-buffered, zero-filled at the edges by the buffer descriptor.
 #include "common.h"
 #include "../../include/kai0hip.h"
 #include <limits.h>
@@ -63,18 +66,16 @@ struct AttnArgs {
 };
 
 // NKS = number of 64-wide K sub-tiles (HD <= 64*NKS); VC = V tile columns (128 or 256); OMT = VC/16 output d-tiles
-// QT = 16-row query tiles per wave.  2: four waves per 128-row block (one per SIMD); 1: eight waves (two per SIMD), so that one
-// wave's MFMAs overlap the other's softmax VALU work and LDS reads — the block, its K / V tiles and LDS footprint are the same.
 // OP > 0: single pass for Sk <= 64 * OP keys — all OP key tiles (K and V) are staged into LDS at once, the logits of the whole
-// row stay in registers (OP x 4 x QT accumulators), so Q K^T is computed once and there is no per-tile barrier; OP = 0: the
+// row stay in registers (OP x 4 accumulators), so Q K^T is computed once and there is no per-tile barrier; OP = 0: the
 // general two-pass form (pass 1: row max / sum, pass 2: recompute the logits, P, P V); OP = -1: one pass, online softmax (no P).
-// RB = query rows per block (128; 64: four waves, ONE staging buffer, 80 KiB of LDS -> two independent blocks per CU that cover each
-// other's DMA waits and softmax chains instead of eight lockstep waves).
-template <int NKS, int VC, int QT, int OP = 0, int RB = 128>
-__global__ __launch_bounds__(RB / (16 * QT) * 64, RB == 64 ? 2 : 1) void attn_fwd_kernel(const AttnArgs p) {
-    constexpr int WAVES = RB / (16 * QT);
-    constexpr int NST = RB == 64 ? 1 : 2;  // staging buffers of the two-pass form
-    static_assert(RB == 128 && QT == 1, "128-row blocks of eight waves (the 64-row / four-wave forms were measured slower and removed)");
+// A block is 128 query rows on eight waves of 16 rows; the tile loops of OP <= 0 alternate between two staging buffers.
+template <int NKS, int VC, int OP>
+__global__ __launch_bounds__(512, 1) void attn_fwd_kernel(const AttnArgs p) {
+    // 16-row query tiles per wave.  One, and not a parameter (two tiles on four waves measured slower, see the record above the
+    // dispatch); the [QT] arrays and one-trip nt loops stay only because hipcc optimises a loop of one trip at another point of its
+    // pipeline than straight-line code: without even one of them all five kernels come out as different instruction streams.
+    constexpr int QT = 1;
     constexpr int OMT = VC / 16;
     constexpr int KSTEPS = NKS * 2;                 // 32-wide contraction steps over the head dim
     constexpr int K_BYTES = NKS * 8192;             // NKS x [64 keys][64 d] bf16
@@ -83,12 +84,11 @@ __global__ __launch_bounds__(RB / (16 * QT) * 64, RB == 64 ? 2 : 1) void attn_fw
     constexpr int STAGE = K_BYTES + V_BYTES;
     constexpr int V_LPR = V_ROWB / 16;              // lanes per V row (16 or 32)
     constexpr int V_RPP = 64 / V_LPR;               // key rows per DMA piece (4 or 2)
-    constexpr int NKP = NKS * 8 / WAVES;            // K DMA pieces per wave per tile
-    constexpr int NVP = (64 / V_RPP) / WAVES;       // V DMA pieces per wave per tile
-    static_assert(NKP >= 1 && NVP >= 1, "too many waves for this tile");
+    constexpr int NKP = NKS;                        // K DMA pieces (8 key rows) per wave per tile
+    constexpr int NVP = (64 / V_RPP) / 8;           // V DMA pieces per wave per tile
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* pbuf_all = smem + (OP > 0 ? OP : NST) * STAGE;  // WAVES x [16 QT rows][64 keys] bf16 (P transposition scratch)
-    int* kc_lds = reinterpret_cast<int*>(pbuf_all + WAVES * QT * 2048);  // key codes of all keys (see load_kcodes)
+    char* pbuf_all = smem + (OP > 0 ? OP : 2) * STAGE;  // 8 waves x [16 QT rows][64 keys] bf16 (P transposition scratch)
+    int* kc_lds = reinterpret_cast<int*>(pbuf_all + 8 * QT * 2048);  // key codes of all keys (see load_kcodes)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(RB / (16 * QT) * 64, RB == 64 ? 2 : 1) void attn_fw
     const __amdgpu_buffer_rsrc_t k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Kb, 0, (int)OOB, 0x00020000);
     const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Vb, 0, (int)OOB, 0x00020000);
     const __amdgpu_buffer_rsrc_t p_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Pb, 0, (int)OOB, 0x00020000);
-    const int row0 = blockIdx.x * RB + wave * (16 * QT);   // first query row of this wave
+    const int row0 = blockIdx.x * 128 + wave * (16 * QT);  // first query row of this wave
     const int ntiles = (p.Sk + 63) / 64;
     const uint32_t ldk2 = (uint32_t)p.ldk * 2, ldv2 = (uint32_t)p.ldv * 2;
 
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(RB / (16 * QT) * 64, RB == 64 ? 2 : 1) void attn_fw
     // whose latency the tile's 32 MFMAs do not cover (the forward's phases are latency-bound: KAI0_ATTN_ABLATE shows their costs
     // simply adding up).
     if (p.kc_lds_keys > 0) {
-        for (int i = tid; i < p.kc_lds_keys; i += WAVES * 64)
+        for (int i = tid; i < p.kc_lds_keys; i += 512)
             kc_lds[i] = p.kcode == nullptr ? 0 : (i < p.Sk ? p.kcode[z1 * p.kcode_ld + i] : INT_MAX);
     }
     auto load_kcodes = [&](int kt, int (&kc)[4][4]) {
@@ -247,8 +247,6 @@ __global__ __launch_bounds__(RB / (16 * QT) * 64, RB == 64 ? 2 : 1) void attn_fw
 #pragma unroll
         for (int nt = 0; nt < QT; ++nt) o[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
     char* pbuf = pbuf_all + wave * (QT * 2048);
-    // one 64-key tile of the output side: final probabilities from the finished logits s (row max m, 1 / row sum inv_l),
-    // P written out, O^T += V^T P^T
     // final probabilities of a 64-key tile from the finished logits s (row max m, 1 / row sum inv_l), rounded to bf16 exactly once
     // (what the reference multiplies V with), and written out
     auto make_p = [&](int kt, f32x4 (&s)[4][QT], const float (&m_run)[QT], const float (&inv_l)[QT], bf16x4 (&pb)[4][QT]) {
@@ -406,7 +404,7 @@ __global__ __launch_bounds__(RB / (16 * QT) * 64, RB == 64 ? 2 : 1) void attn_fw
         int nlive = ntiles;
         if (use_list) {
             __syncthreads();  // the codes are in LDS
-            for (int t = wave; t < ntiles; t += WAVES) {
+            for (int t = wave; t < ntiles; t += 8) {
                 const bool any = __any(kc_lds[t * 64 + lane] != INT_MAX);
                 if (lane == 0) lt[40 + t] = any ? 1 : 0;
             }
@@ -426,8 +424,8 @@ __global__ __launch_bounds__(RB / (16 * QT) * 64, RB == 64 ? 2 : 1) void attn_fw
         lds_barrier();
         for (int it = 0; it < nlive; ++it) {
             const int kt = tile_at(it);
-            const int buf = NST == 2 ? (it & 1) : 0;
-            if (NST == 2 && it + 1 < nlive && !(KAI0_ABL(p) & 8)) stage(tile_at(it + 1), buf ^ 1, true);
+            const int buf = it & 1;
+            if (it + 1 < nlive && !(KAI0_ABL(p) & 8)) stage(tile_at(it + 1), buf ^ 1, true);
             const char* tk = smem + buf * STAGE;
             int kc[4][4];
             load_kcodes(kt, kc);
@@ -471,10 +469,6 @@ __global__ __launch_bounds__(RB / (16 * QT) * 64, RB == 64 ? 2 : 1) void attn_fw
                 }
             }
             pv_tile(tk + K_BYTES, pb);
-            if (NST == 1) {
-                lds_barrier();
-                if (it + 1 < nlive) stage(tile_at(it + 1), 0, true);
-            }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             lds_barrier();
         }
@@ -498,8 +492,8 @@ __global__ __launch_bounds__(RB / (16 * QT) * 64, RB == 64 ? 2 : 1) void attn_fw
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
     for (int kt = 0; kt < ((KAI0_ABL(p) & 2) ? 0 : ntiles); ++kt) {
-        const int buf = NST == 2 ? (kt & 1) : 0;
-        if (NST == 2 && kt + 1 < ntiles && !(KAI0_ABL(p) & 8)) stage(kt + 1, buf ^ 1, false);
+        const int buf = kt & 1;
+        if (kt + 1 < ntiles && !(KAI0_ABL(p) & 8)) stage(kt + 1, buf ^ 1, false);
         int kc[4][4];
         load_kcodes(kt, kc);
         f32x4 s[4][QT];
@@ -522,10 +516,6 @@ __global__ __launch_bounds__(RB / (16 * QT) * 64, RB == 64 ? 2 : 1) void attn_fw
                 l_run[nt] = acc;
                 m_run[nt] = mn;
             }
-        }
-        if (NST == 1) {  // one buffer: every wave is done reading tile kt before tile kt + 1 overwrites it
-            lds_barrier();
-            if (kt + 1 < ntiles && !(KAI0_ABL(p) & 8)) stage(kt + 1, 0, false);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         lds_barrier();
@@ -553,8 +543,8 @@ __global__ __launch_bounds__(RB / (16 * QT) * 64, RB == 64 ? 2 : 1) void attn_fw
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
     for (int kt = 0; kt < ntiles; ++kt) {
-        const int buf = NST == 2 ? (kt & 1) : 0;
-        if (NST == 2 && kt + 1 < ntiles && !(KAI0_ABL(p) & 8)) stage(kt + 1, buf ^ 1, true);
+        const int buf = kt & 1;
+        if (kt + 1 < ntiles && !(KAI0_ABL(p) & 8)) stage(kt + 1, buf ^ 1, true);
         const char* tk = smem + buf * STAGE;
         int kc[4][4];
         load_kcodes(kt, kc);
@@ -568,20 +558,12 @@ __global__ __launch_bounds__(RB / (16 * QT) * 64, RB == 64 ? 2 : 1) void attn_fw
         logits(tk, s);
         finish_logits(kt, s, kc);
         emit_tile(kt, tk + K_BYTES, s, m_run, inv_l);
-        if (NST == 1) {
-            lds_barrier();
-            if (kt + 1 < ntiles && !(KAI0_ABL(p) & 8)) stage(kt + 1, 0, true);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the P stores are older than these pieces)
-        } else {
         // the DMA of tile kt+1 (issued at the top of this iteration) must have landed; the P stores issued after it may fly
         if (p.P != nullptr && !(KAI0_ABL(p) & 1)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * QT) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
         lds_barrier();
     }
     }
-    // zero the padding columns [64*ntiles, ldp) of P (none when ldp <= 64*ntiles) — the tiles above already wrote
-    // zeros for keys in [Sk, 64*ntiles)
     // ---- O: lane (q = l15, g) holds O^T rows d = 16 mt + 4g + r ----------------------------------------------------
 #pragma unroll
     for (int nt = 0; nt < QT; ++nt) {
@@ -693,14 +675,15 @@ KAI0_API int kai0_attn_fwd(const kai0_attn_desc* d, kai0_stream_t stream) {
     const int batch = d->batch > 0 ? d->batch : 1;
     dim3 grid((d->rows + 127) / 128, batch, 1);
     hipStream_t s = (hipStream_t)stream;
-#define KAI0_ATTN_LAUNCH(NKS, VC, QT, OP, RB)                                                                          \
+    // LDS: the staged tiles, 16 KiB of P transposition scratch, the key codes and the live-tile list
+#define KAI0_ATTN_LAUNCH(NKS, VC, OP)                                                                             \
     do {                                                                                                          \
-        constexpr int LDS = (OP > 0 ? OP : (RB == 64 ? 1 : 2)) * (NKS * 8192 + 64 * VC * 2) + (RB / 32) * 4096 + KC_LDS_MAX * 4 + 512; \
-        static_assert(LDS <= 160 * 1024, "attention LDS budget");                                                    \
-        auto kern = attn_fwd_kernel<NKS, VC, QT, OP, RB>;                                                             \
+        constexpr int LDS = (OP > 0 ? OP : 2) * (NKS * 8192 + 64 * VC * 2) + 8 * 2048 + KC_LDS_MAX * 4 + 512;     \
+        static_assert(LDS <= 160 * 1024, "attention LDS budget");                                                 \
+        auto kern = attn_fwd_kernel<NKS, VC, OP>;                                                                 \
         const hipError_t e = kai0_reserve_lds((const void*)kern, LDS);                                            \
         KAI0_REQUIRE(e == hipSuccess, "kai0_attn_fwd: cannot reserve %d B of LDS: %s", LDS, hipGetErrorString(e)); \
-        hipLaunchKernelGGL(kern, grid, dim3(RB / (16 * QT) * 64), LDS, s, p);                                    \
+        hipLaunchKernelGGL(kern, grid, dim3(512), LDS, s, p);                                                     \
     } while (0)
     // (Measured and rejected, round 3: the two wave groups of pass 2 one barrier slot apart — 1.095 against 0.965 ms; four-wave
     // blocks with two 16-row tiles per wave — 0.83 against 0.66 ms one-pass; 64-row blocks, two per CU — 0.915 against 0.930 ms two-pass.
@@ -714,12 +697,12 @@ KAI0_API int kai0_attn_fwd(const kai0_attn_desc* d, kai0_stream_t stream) {
     const bool online = d->P == nullptr && d->online != 2;
     if (d->HD <= 128) {
         // 256 keys = 4 resident tiles (144 KiB, one block per CU): wins when the grid is at most a round or two of the chip
-        if (d->Sk <= 256 && (int64_t)grid.x * grid.y <= 512) KAI0_ATTN_LAUNCH(2, 128, 1, 4, 128);
-        else if (online) KAI0_ATTN_LAUNCH(2, 128, 1, -1, 128);
-        else KAI0_ATTN_LAUNCH(2, 128, 1, 0, 128);
+        if (d->Sk <= 256 && (int64_t)grid.x * grid.y <= 512) KAI0_ATTN_LAUNCH(2, 128, 4);
+        else if (online) KAI0_ATTN_LAUNCH(2, 128, -1);
+        else KAI0_ATTN_LAUNCH(2, 128, 0);
     } else {
-        if (online) KAI0_ATTN_LAUNCH(4, 256, 1, -1, 128);
-        else KAI0_ATTN_LAUNCH(4, 256, 1, 0, 128);
+        if (online) KAI0_ATTN_LAUNCH(4, 256, -1);
+        else KAI0_ATTN_LAUNCH(4, 256, 0);
     }
 #undef KAI0_ATTN_LAUNCH
     return kai0_check_launch("kai0_attn_fwd");

@@ -4,17 +4,19 @@
 //     dP   = dO V^T                 (f32, never rounded, never written)
 //     dS   = bf16((P * (dP - D)) * scale)                     (written once: dK = dS^T Q still needs it)
 //     dQ   = dS K                                              (f32 accumulate, bf16 out)
-// in ONE launch.  Round 4 (RC = true, kai0_attn_bwd_dq2): P is not read but RECOMPUTED per key tile — S^T = K Q^T from the K tile
-// that is in LDS anyway (the row-major image serves both the b128 row reads of this product and the transpose reads of
-// dQ^T += K^T dS^T: with the key swizzle below the 16 lanes of every ds_read_b128 group fall on 16 distinct 16-byte slots), the
-// logits rounded and masked exactly as the forward does, P = bf16(exp(s - lse[row])) with the forward's per-row log-sum-exp —
-// and WRITTEN once (bf16) next to dS for the two batched GEMMs dV = P^T dO, dK = dS^T Q that follow.  The forward therefore
-// stores no probabilities (attention.hip, OP = -1); one extra product here against one fewer pass and one fewer S x S store
-// there, and P never sits in HBM between forward and backward (9.6 GB per step at B = 32).
-// It replaces kai0_rowdot_bf16 + the K = 256 GEMM with the softmax-backward epilogue (all epilogue: 4 K-tiles
-// per 256x256 tile, 277 TFLOP/s) + the dQ GEMM that re-read dS: P is read once, dS written once, dO / V / K stay on chip.
-// P is the forward's stored bf16 probabilities — recomputing them (a "flash" backward) would cost 7 GEMM-units of MFMA work
-// instead of 4 at HD = 256 and the forward keeps P for dV = P^T dO anyway.
+// in ONE launch; dV = P^T dO and dK = dS^T Q stay GEMMs.  It replaces kai0_rowdot_bf16 + the K = 256 GEMM with the
+// softmax-backward epilogue (all epilogue: 4 K-tiles per 256x256 tile, 277 TFLOP/s) + the dQ GEMM that re-read dS: dS is written
+// once, dO / V / K stay on chip.  One kernel, two forms (RC):
+//   * recompute (RC = true, kai0_attn_bwd_dq2, round 4) — training, up to AB_KC_MAX keys: P is not read but RECOMPUTED per key
+//     tile — S^T = K Q^T from the K tile that is in LDS anyway (the row-major image serves both the b128 row reads of this
+//     product and the transpose reads of dQ^T += K^T dS^T: with the key swizzle below the 16 lanes of every ds_read_b128 group
+//     fall on 16 distinct 16-byte slots), the logits rounded and masked exactly as the forward does, P = bf16(exp(s - lse[row]))
+//     with the forward's per-row log-sum-exp — and WRITTEN once (bf16) next to dS for the two batched GEMMs that follow.  The
+//     forward therefore stores no probabilities (attention.hip, OP = -1): one extra product here (7 GEMM-units of MFMA work
+//     instead of 4 at HD = 256) against one fewer pass and one fewer S x S store there, and P never sits in HBM between forward
+//     and backward (9.6 GB per step at B = 32).
+//   * stored P (RC = false, kai0_attn_bwd_dq, round 3) — longer sequences and the guided inference step, whose forward is the
+//     two-pass form that writes P: the lane's 16-byte slices of P are read once, a tile ahead of their use.
 //
 // gfx950 mapping (mirrors attention.hip): block = 128 rows on 8 waves (16 rows each, two waves per SIMD); the wave keeps its dO
 // rows as MFMA B fragments and its dQ^T accumulators [256 d x 16 rows] in registers; V tiles ([64 keys][64 d] sub-tiles, read
@@ -345,25 +347,24 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(const AbArgs p) {
 
 }  // namespace
 
-static int attn_bwd_dq_launch(const void* dO, const void* O, const void* P, const void* K, const void* V, void* dS, void* dQ,
-                              int batch, int rows, int Sk, int HD, int64_t ldo, int64_t ldk, int64_t ldv, int64_t ldp,
-                              int64_t sO, int64_t sK, int64_t sV, int64_t sP, float scale, kai0_stream_t stream,
-                              const void* Q, const float* lse, int64_t s_lse, const int32_t* qcode, int64_t qcode_ld,
-                              const int32_t* kcode, int64_t kcode_ld, int H, bool rc) {
-    KAI0_REQUIRE(dO && O && P && K && V && dS && dQ, "kai0_attn_bwd_dq: null operand");
-    KAI0_REQUIRE(!rc || (Q && lse && s_lse >= rows && H >= 1 && ((qcode == nullptr) == (kcode == nullptr)) && Sk <= AB_KC_MAX),
+// One launch of either form.  d->P is the stored probabilities (read) without rc, the recomputed ones (written) with it; the
+// descriptor fields that only the recompute form has (Q, lse, the mask codes, H) are not looked at without rc.
+static int attn_bwd_dq_launch(const kai0_attn_bwd_desc& d, bool rc, kai0_stream_t stream) {
+    KAI0_REQUIRE(d.dO && d.O && d.P && d.K && d.V && d.dS && d.dQ, "kai0_attn_bwd_dq: null operand");
+    KAI0_REQUIRE(!rc || (d.Q && d.lse && d.s_lse >= d.rows && d.H >= 1 && ((d.qcode == nullptr) == (d.kcode == nullptr)) && d.Sk <= AB_KC_MAX),
                  "kai0_attn_bwd_dq2: needs Q, lse (s_lse >= rows), H >= 1, both or neither mask code, Sk <= %d", AB_KC_MAX);
-    KAI0_REQUIRE(HD % 8 == 0 && HD > 0 && HD <= 256, "kai0_attn_bwd_dq: HD=%d unsupported", HD);
-    KAI0_REQUIRE(ldo % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldp % 8 == 0 && ldp >= Sk,
+    KAI0_REQUIRE(d.HD % 8 == 0 && d.HD > 0 && d.HD <= 256, "kai0_attn_bwd_dq: HD=%d unsupported", d.HD);
+    KAI0_REQUIRE(d.ldo % 8 == 0 && d.ldk % 8 == 0 && d.ldv % 8 == 0 && d.ldp % 8 == 0 && d.ldp >= d.Sk,
                  "kai0_attn_bwd_dq: leading dims must be multiples of 8 and ldp >= Sk");
-    KAI0_REQUIRE((int64_t)Sk * ldk * 2 < (int64_t)0x7FFF0000 && (int64_t)Sk * ldv * 2 < (int64_t)0x7FFF0000 &&
-                     (int64_t)rows * ldp * 2 < (int64_t)0x7FFF0000,
+    KAI0_REQUIRE((int64_t)d.Sk * d.ldk * 2 < (int64_t)0x7FFF0000 && (int64_t)d.Sk * d.ldv * 2 < (int64_t)0x7FFF0000 &&
+                     (int64_t)d.rows * d.ldp * 2 < (int64_t)0x7FFF0000,
                  "kai0_attn_bwd_dq: an operand spans more than 2 GiB per batch entry");
-    if (rows <= 0 || Sk <= 0 || batch <= 0) return 0;
-    AbArgs a{(const bf16_t*)dO, (const bf16_t*)O, rc ? nullptr : (const bf16_t*)P, rc ? (bf16_t*)P : nullptr, (const bf16_t*)Q, lse,
-             qcode, kcode, s_lse, qcode_ld, kcode_ld, H,
-             (const bf16_t*)K, (const bf16_t*)V, (bf16_t*)dS, (bf16_t*)dQ, rows, Sk, HD, ldo, ldk, ldv, ldp, sO, sK, sV, sP, scale};
-    const dim3 grid((rows + 127) / 128, batch, 1);
+    if (d.rows <= 0 || d.Sk <= 0 || d.batch <= 0) return 0;
+    AbArgs a{(const bf16_t*)d.dO, (const bf16_t*)d.O, rc ? nullptr : (const bf16_t*)d.P, rc ? (bf16_t*)d.P : nullptr, (const bf16_t*)d.Q,
+             d.lse, d.qcode, d.kcode, d.s_lse, d.qcode_ld, d.kcode_ld, d.H,
+             (const bf16_t*)d.K, (const bf16_t*)d.V, (bf16_t*)d.dS, (bf16_t*)d.dQ, d.rows, d.Sk, d.HD, d.ldo, d.ldk, d.ldv, d.ldp,
+             d.sO, d.sK, d.sV, d.sP, d.scale};
+    const dim3 grid((d.rows + 127) / 128, d.batch, 1);
     hipStream_t s = (hipStream_t)stream;
 #define KAI0_AB_LAUNCH(NKS, RC)                                                                                          \
     do {                                                                                                               \
@@ -374,10 +375,10 @@ static int attn_bwd_dq_launch(const void* dO, const void* O, const void* P, cons
         hipLaunchKernelGGL(kern, grid, dim3(512), LDS, s, a);                                                          \
     } while (0)
     if (rc) {
-        if (HD <= 128) KAI0_AB_LAUNCH(2, true);
+        if (d.HD <= 128) KAI0_AB_LAUNCH(2, true);
         else KAI0_AB_LAUNCH(4, true);
     } else {
-        if (HD <= 128) KAI0_AB_LAUNCH(2, false);
+        if (d.HD <= 128) KAI0_AB_LAUNCH(2, false);
         else KAI0_AB_LAUNCH(4, false);
     }
 #undef KAI0_AB_LAUNCH
@@ -387,15 +388,17 @@ static int attn_bwd_dq_launch(const void* dO, const void* O, const void* P, cons
 KAI0_API int kai0_attn_bwd_dq(const void* dO, const void* O, const void* P, const void* K, const void* V, void* dS, void* dQ,
                               int batch, int rows, int Sk, int HD, int64_t ldo, int64_t ldk, int64_t ldv, int64_t ldp,
                               int64_t sO, int64_t sK, int64_t sV, int64_t sP, float scale, kai0_stream_t stream) {
-    return attn_bwd_dq_launch(dO, O, P, K, V, dS, dQ, batch, rows, Sk, HD, ldo, ldk, ldv, ldp, sO, sK, sV, sP, scale, stream, nullptr,
-                              nullptr, 0, nullptr, 0, nullptr, 0, 1, false);
+    kai0_attn_bwd_desc d = {};
+    d.dO = dO; d.O = O; d.P = const_cast<void*>(P); d.K = K; d.V = V; d.dS = dS; d.dQ = dQ;
+    d.batch = batch; d.rows = rows; d.Sk = Sk; d.HD = HD; d.H = 1;
+    d.ldo = ldo; d.ldk = ldk; d.ldv = ldv; d.ldp = ldp; d.sO = sO; d.sK = sK; d.sV = sV; d.sP = sP;
+    d.scale = scale;
+    return attn_bwd_dq_launch(d, false, stream);
 }
 
 KAI0_API int kai0_attn_bwd_desc_size(void) { return (int)sizeof(kai0_attn_bwd_desc); }
 
 KAI0_API int kai0_attn_bwd_dq2(const kai0_attn_bwd_desc* d, kai0_stream_t stream) {
     KAI0_REQUIRE(d != nullptr, "kai0_attn_bwd_dq2: null descriptor");
-    return attn_bwd_dq_launch(d->dO, d->O, d->P, d->K, d->V, d->dS, d->dQ, d->batch, d->rows, d->Sk, d->HD, d->ldo, d->ldk, d->ldv,
-                              d->ldp, d->sO, d->sK, d->sV, d->sP, d->scale, stream, d->Q, d->lse, d->s_lse, d->qcode, d->qcode_ld,
-                              d->kcode, d->kcode_ld, d->H, true);
+    return attn_bwd_dq_launch(*d, true, stream);
 }

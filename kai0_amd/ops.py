@@ -1498,10 +1498,6 @@ def attn_fwd(Q, K, V, O, P, **kw):
     _lib.call("kai0_attn_fwd", C.byref(_attn_desc(Q, K, V, O, P, **kw)), _stream())
 
 
-# KAI0_ATTN_STORE_P=1: the round-3 training attention (exact two-pass forward that stores P, backward reads it) for A/B runs
-_ATTN_STORE_P = os.environ.get("KAI0_ATTN_STORE_P", "0") == "1"
-
-
 def mqa_attention_fwd(q_all, k_all, v_all, qcode, kcode, Bn, Sq, q0, Sk, S_ld, H, HD, scale, want_probs=True, want_lse=False):
     """Prefix-LM masked multi-query attention over padded buffers (modeling_gemma.py:230-253), one fused kernel.
 
@@ -1592,8 +1588,10 @@ class JointAttentionFn(torch.autograd.Function):
             parts.append((None, 0, v_all, S * HD, (0, 0), (S_ld * HD, HD), Bn, S_ld - S, HD, 3, 0))
         pack_rows(parts, HD, pos, S, inv_freq)
         scale = HD**-0.5
-        # one pass, no stored probabilities: the backward recomputes them from lse (kai0_attn_bwd_dq2)
-        recompute = not _ATTN_STORE_P and S <= 2048
+        # one pass, no stored probabilities: the backward recomputes them from lse (kai0_attn_bwd_dq2), which stages the key codes of
+        # up to 2048 keys in LDS (AB_KC_MAX in attn_bwd.hip).  Longer sequences take the two-pass forward that stores P and the
+        # backward that reads it (kai0_attn_bwd_dq): a selection from the input size alone
+        recompute = S <= 2048
         att, probs = mqa_attention_fwd(q_all, k_all, v_all, qcode, kcode, Bn, S, 0, S, S_ld, H, HD, scale, want_lse=recompute)
         outs, parts = [], []
         r0 = 0
@@ -1659,7 +1657,7 @@ class JointAttentionFn(torch.autograd.Function):
         gemm(probs, datt, dv_all, M=S_ld, N=HD, K=M, a_kc=False, b_kc=False, lda=S_ld, ldb=HD, ldc=HD, batch=Bn,
              sA=(M * S_ld, 0), sB=(S_ld * H * HD, 0), sC=(S_ld * HD, 0), split_k=kv_split)  # fmt: skip
         if not recompute:
-            # stored-P form (KAI0_ATTN_STORE_P=1): one launch — D = rowsum(dO * O), dP = dO V^T in f32, dS written once, dQ = dS K on chip
+            # stored-P form (S > 2048): one launch — D = rowsum(dO * O), dP = dO V^T in f32, dS written once, dQ = dS K on chip
             dscores, dq_all = attn_bwd_dq_stored(datt, att, probs, k_all, v_all, batch=Bn, rows=M, Sk=S, HD=HD, ldo=HD, ldk=HD, ldv=HD,
                                                  ldp=S_ld, sO=S_ld * H * HD, sK=S_ld * HD, sV=S_ld * HD, sP=M * S_ld, scale=scale)
         # dK[b] [S_ld, HD] = dS[b]^T [S_ld, M] @ Q[b] [M, HD]
@@ -1695,7 +1693,7 @@ class SiglipAttentionFn(torch.autograd.Function):
         scale = HD**-0.5
         out = torch.empty((n_img * S, E), dtype=BF16, device=dev)
         # the real tower: no stored probabilities, the fused backward recomputes them from lse (kai0_siglip_attn_bwd2)
-        recompute = S == 256 and HD == 72 and S_ld == 256 and _SIGLIP_BWD_FUSED and not _ATTN_STORE_P
+        recompute = S == 256 and HD == 72 and S_ld == 256 and _SIGLIP_BWD_FUSED
         if recompute and _SIGLIP_FWD_DEDICATED and q.stride(0) == k.stride(0) == v.stride(0):
             probs = torch.empty((n_img * NH, S), dtype=torch.float32, device=dev)  # lse
             siglip_attn_fwd(q, k, v, out, n_img=n_img, S=S, NH=NH, HD=HD, ld_qkv=q.stride(0), ld_out=E, lse=probs)
@@ -1719,17 +1717,11 @@ class SiglipAttentionFn(torch.autograd.Function):
         E = NH * HD
         dout = dout.contiguous()
         if recompute:
-            dq, dk, dv = fused_columns(q.shape[0], (E, E, E), dev)
-            _lib.call("kai0_siglip_attn_bwd2", q.data_ptr(), k.data_ptr(), v.data_ptr(), dout.data_ptr(), out.data_ptr(),
-                      probs.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), n_img, S, NH, HD, 3 * E, scale, _stream())  # fmt: skip
-            return dq, dk, dv, None, None, None, None
-        if S == 256 and HD == 72 and S_ld == 256 and _SIGLIP_BWD_FUSED:
             # the real tower (so400m/14 @ 224): one block per (image, head) runs the whole backward out of LDS
             # dq | dk | dv are the column slices of one buffer: the fused q|k|v projection backward reads it whole
             dq, dk, dv = fused_columns(q.shape[0], (E, E, E), dev)
-            _lib.call("kai0_siglip_attn_bwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), dout.data_ptr(), out.data_ptr(),
-                      probs.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), n_img, S, NH, HD, S_ld, 3 * E, scale,
-                      _stream())  # fmt: skip
+            _lib.call("kai0_siglip_attn_bwd2", q.data_ptr(), k.data_ptr(), v.data_ptr(), dout.data_ptr(), out.data_ptr(),
+                      probs.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), n_img, S, NH, HD, 3 * E, scale, _stream())  # fmt: skip
             return dq, dk, dv, None, None, None, None
         nb = n_img * NH
         sP = (NH * S * S_ld, S * S_ld)

@@ -231,7 +231,7 @@ def test_product_never_imports_oracle():
 
 # ------------------------------------------------------------------------------------------------ C-ABI
 def test_cabi_v2_exports_every_declared_symbol():
-    """libkai0hip.so loads, reports C ABI version 2 and exports exactly what include/kai0hip.h declares (no compute call here)."""
+    """libkai0hip.so loads, reports C ABI version 3 and exports exactly what include/kai0hip.h declares (no compute call here)."""
     import ctypes
 
     from kai0_amd import _lib
@@ -242,7 +242,7 @@ def test_cabi_v2_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in kai0hip.h but not exported"
     assert declared == set(_lib.EXPORTED_SYMBOLS), declared ^ set(_lib.EXPORTED_SYMBOLS)
-    assert lib.kai0_abi_version() == 2
+    assert lib.kai0_abi_version() == 3
     assert ctypes.sizeof(_lib.GemmDesc) == lib.kai0_gemm_desc_size()
 
 

@@ -650,14 +650,13 @@ def _mqa_ref(q, k, v, pos, inv, qcode, kcode, H, HD):
     return (p @ vh).permute(0, 2, 1, 3).reshape(B, S, H * HD)
 
 
-@pytest.mark.parametrize("H,HD,P,Hs", [(8, 16, 20, 6), (8, 256, 40, 10)])
-def test_joint_attention_fwd_bwd(ops, H, HD, P, Hs):
+def _joint_attention_case(ops, B, H, HD, P, Hs):
     from kai0_amd.model import build_mask_codes
 
-    B, S = 2, P + Hs
+    S = P + Hs
     pad = torch.ones((B, S), dtype=torch.bool, device=dev())
     pad[0, 3:6] = False
-    pad[1, P - 4 : P] = False
+    pad[B - 1, P - 4 : P] = False
     att = torch.zeros((B, S), dtype=torch.bool, device=dev())
     att[:, P] = True
     qcode, kcode, pos = build_mask_codes(pad, att)
@@ -687,6 +686,18 @@ def test_joint_attention_fwd_bwd(ops, H, HD, P, Hs):
     for n, t, r in zip(names, flat, refs):
         e = rel_err(t.grad, r.grad)
         assert e < 2e-2, f"{n}: rel-L2 {e:.3e}"
+
+
+@pytest.mark.parametrize("H,HD,P,Hs", [(8, 16, 20, 6), (8, 256, 40, 10)])
+def test_joint_attention_fwd_bwd(ops, H, HD, P, Hs):
+    _joint_attention_case(ops, 2, H, HD, P, Hs)
+
+
+def test_joint_attention_fwd_bwd_past_recompute_limit(ops):
+    """S = 2056 is the smallest padded sequence past the 2048 keys the recompute backward stages in LDS: the two-pass forward stores P
+    (key codes read from global memory), kai0_attn_bwd_dq reads it, and the dV / dK GEMMs (M = 4112) take a two-way split.  One batch
+    entry, so both padding gaps sit in it; same reference and bounds as the short sequences above."""
+    _joint_attention_case(ops, 1, 2, 16, 2050, 6)
 
 
 def test_siglip_attention_fwd_bwd(ops):

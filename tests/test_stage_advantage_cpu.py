@@ -282,7 +282,7 @@ def test_video_decoding_unavailable_is_a_clear_error(tmp_path, monkeypatch):
 
 
 def test_prototypes_and_bindings():
-    """The two prototypes are in include/kai0hip.h, cite the reference op they replace, and _lib.py binds them; the C ABI stays 2."""
+    """The two prototypes are in include/kai0hip.h, cite the reference op they replace, and _lib.py binds them; the C ABI version is 3."""
     import ctypes as C
 
     from kai0_amd import _lib
@@ -295,4 +295,4 @@ def test_prototypes_and_bindings():
     p, i, i64 = C.c_void_p, C.c_int, C.c_int64
     assert _lib._PROTOS["kai0_frames_to_chw"] == [p, p, i, i, i, i, i, i, i, i, i, p]
     assert _lib._PROTOS["kai0_prefix_gather"] == [p, p, p, p, i, i, i, i, i, i64, p]
-    assert "frames.hip" in SRC and _lib.ABI_VERSION == 2
+    assert "frames.hip" in SRC and _lib.ABI_VERSION == 3
