@@ -300,7 +300,8 @@ int64_t kai0_skinny_workspace_bytes(int M, int N, int split_k);
  *   K    : bf16 [batch][k_rows][k_ld] row-major keys (one KV head);  Vt : bf16 [batch][HD][vt_ld] TRANSPOSED values
  *   allowed(b, token s, key j) = j < Sk && kcode[b][j] <= qcode[b][s]   (codes as in kai0_softmax_mask_fwd)
  *   logits bf16(bf16(q.k) * scale) -> f32 softmax -> P bf16 -> O = bf16(P V) : the rounding points of
- *   kai0_gemm_bf16 + kai0_softmax_mask_fwd + kai0_gemm_bf16.  HD = 256, Sk <= 1024, vt_ld >= round_up(Sk, 32). */
+ *   kai0_gemm_bf16 + kai0_softmax_mask_fwd + kai0_gemm_bf16.  HD = 256, Sk <= 1024, vt_ld >= round_up(Sk, 32).
+ *   K rows Sk .. k_rows and Vt columns Sk .. vt_ld are read but may hold anything (NaN included): nothing of them reaches O. */
 int kai0_attn_decode(const void* Q, const void* K, const void* Vt, void* O, const int32_t* qcode, const int32_t* kcode,
                      int batch, int rows, int H, int HD, int Sk, int q0, int64_t q_bs, int64_t k_bs, int64_t k_ld,
                      int k_rows, int64_t vt_bs, int64_t vt_ld, int64_t qcode_ld, int64_t kcode_ld, float scale,

@@ -155,13 +155,19 @@ __global__ __launch_bounds__(256) void dec_pv_kernel(const DecArgs p, const bf16
     char* my = dec_smem + wave * DEC_STAGE;
     {
         const int sub = lane >> 5, c16 = lane & 31;
-        const int kcol = min(wave * 256 + c16 * 8, (int)p.vt_ld - 8);  // (keys past the padded row end: never multiplied, P = 0)
+        const int k0 = wave * 256 + c16 * 8;
+        const int kcol = min(k0, (int)p.vt_ld - 8);  // (keys past the padded row end: a clamped address, masked below)
         const bf16_t* Vb = p.Vt + (int64_t)b * p.vt_bs + (int64_t)h0 * p.vt_ld + kcol;
-        bf16x8 ch[8 * HT];
+        // keys >= Sk have P = 0, but the MFMA still multiplies: whatever the cache holds past Sk (its padding need not be finite, and
+        // 0 * NaN is NaN) is cleared on the way into LDS.  One mask per lane: dword w of a chunk holds keys k0 + 2 w, k0 + 2 w + 1.
+        u32x4 keep;
 #pragma unroll
-        for (int q = 0; q < 8 * HT; ++q) ch[q] = *reinterpret_cast<const bf16x8*>(Vb + (int64_t)(2 * q + sub) * p.vt_ld);
+        for (int w = 0; w < 4; ++w) keep[w] = (k0 + 2 * w < p.Sk ? 0x0000FFFFu : 0u) | (k0 + 2 * w + 1 < p.Sk ? 0xFFFF0000u : 0u);
+        u32x4 ch[8 * HT];
 #pragma unroll
-        for (int q = 0; q < 8 * HT; ++q) *reinterpret_cast<bf16x8*>(my + (2 * q + sub) * DEC_ROWB + (c16 << 4)) = ch[q];
+        for (int q = 0; q < 8 * HT; ++q) ch[q] = *reinterpret_cast<const u32x4*>(Vb + (int64_t)(2 * q + sub) * p.vt_ld);
+#pragma unroll
+        for (int q = 0; q < 8 * HT; ++q) *reinterpret_cast<u32x4*>(my + (2 * q + sub) * DEC_ROWB + (c16 << 4)) = ch[q] & keep;
     }
     float s[8][8];
     float m = -INFINITY;
