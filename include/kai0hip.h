@@ -226,8 +226,7 @@ int kai0_gemm_plan_size(void); /* sizeof the plan struct as compiled, as kai0_ge
  * GeGLU pair (gate_j, up_j) is combined in registers: pair_stride = HD/2 (mode 1), N/2 (mode 2), 16 (mode 0).
  * K / split_k must be 512 or 1024.  split_k > 1 (mode 0 only, no gate / residual) cuts K over blocks so that the
  * whole chip streams the weight: the kernel then writes the raw f32 partial products, `workspace` = f32
- * [split_k][M][N] (kai0_skinny_workspace_bytes), and kai0_adarms_combine — the gated residual + adaRMS that follows
- * o_proj / down_proj anyway — adds the splits in a fixed order (deterministic, no atomics).
+ * [split_k][M][N] (kai0_skinny_workspace_bytes), for the caller to add in a fixed order (deterministic, no atomics).
  * rope_cos / rope_sin: f32 [M][rope_half] tables from kai0_rope_table (bf16-rounded cos/sin of pos * inv_freq,
  * exactly the values kai0_rope_inplace computes), indexed by the A row. */
 typedef struct kai0_skinny_seg {
@@ -397,12 +396,6 @@ int kai0_adarms_fwd(const void* x, const float* mod, void* y, void* gate_out, fl
 int kai0_adarms_bwd(const void* dy, const void* dgate, const void* x, const float* mod, const float* rstd,
                     void* dx, float* dmod, const void* dres, int64_t rows, int rows_per_batch, int D,
                     kai0_stream_t stream);
-/* Denoise-loop companion of kai0_gemm_skinny_bf16: finishes a split-K o_proj / down_proj and runs the next adaRMS.
- *   x = bf16( sum_s partials[s][row] ); x = bf16(x * gate_prev[b]) (if gate_prev); x = bf16(x + residual[row]) (if residual)
- *   x_out = x;  y, gate_out = adaRMS(x, mod) exactly as kai0_adarms_fwd.   (gemma_pytorch.py:150-279 `_gated_residual`) */
-int kai0_adarms_combine(const float* partials, int splits, int64_t split_stride, const void* gate_prev,
-                        const void* residual, void* x_out, const float* mod, void* y, void* gate_out, int64_t rows,
-                        int rows_per_batch, int D, float eps, kai0_stream_t stream);
 /* LayerNorm over the last dim (modeling_siglip.py:439-441,756): bf16 x, bf16 w/b, f32 statistics. */
 int kai0_layernorm_fwd(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd,
                        int64_t rows, int D, float eps, kai0_stream_t stream);

@@ -12,7 +12,7 @@ import pathlib
 
 _HERE = pathlib.Path(__file__).resolve().parent
 LIB_PATH = _HERE / "lib" / "libkai0hip.so"
-ABI_VERSION = 3  # what kai0_abi_version() must return: the version these mirrors and prototypes describe
+ABI_VERSION = 4  # what kai0_abi_version() must return: the version these mirrors and prototypes describe
 
 c_p = C.c_void_p
 c_i = C.c_int
@@ -184,7 +184,6 @@ _PROTOS: dict[str, list] = {
     "kai0_rmsnorm_fwd": [c_p, c_p, c_p, c_p, c_i64, c_i, c_f, c_p],
     "kai0_rmsnorm_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i64, c_i, c_p],
     "kai0_adarms_fwd": [c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_f, c_p],
-    "kai0_adarms_combine": [c_p, c_i, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_f, c_p],
     "kai0_adarms_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_p],
     "kai0_layernorm_fwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_f, c_p],
     "kai0_layernorm_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i64, c_i, c_p],

@@ -282,77 +282,78 @@ __global__ __launch_bounds__(256) void denoise_glue_kernel(const bf16_t* __restr
     }
 }
 
-// split-K combine + gated residual + adaRMS (inference denoise loop): one wave per row
-__global__ __launch_bounds__(256) void adarms_combine_kernel(const float* __restrict__ partials, int splits,
-                                                             int64_t split_stride, const bf16_t* __restrict__ gate_prev,
-                                                             const bf16_t* __restrict__ residual, bf16_t* __restrict__ x_out,
-                                                             const float* __restrict__ mod, bf16_t* __restrict__ y,
-                                                             bf16_t* __restrict__ gate_out, int64_t rows, int rpb, int D,
-                                                             float eps) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
+// ------------------------------------------------------------------------------------ norm backward
+// One row of the three backward kernels, a wave per row: xh = (x - mean) * rstd, dxh = dy * cw, the row sums s1 and s2,
+// dx = rstd * (dxh - s1 - xh * s2) + dres (the gradient of the residual branch of x, if any).  The RMS forms (LN = false) pass
+// mean = 0 and keep s1 = 0: `- 0.f` is exact and costs no instruction.  acc(c, e, dy, xh) adds element e of chunk c to the caller's
+// column sums (taken by reference: with the lambda by value hipcc gives layernorm_bwd_kernel 269 registers instead of 228, one wave
+// per SIMD instead of two).
+template <bool LN, class Acc>
+__device__ __forceinline__ void norm_bwd_row(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const bf16_t* __restrict__ dres,
+                                             bf16_t* __restrict__ dx, int64_t row, int D, int lane, float mean, float rstd,
+                                             const float (&cw)[MAXC][8], Acc&& acc) {
     const int nchunk = D >> 3;
-    const int64_t b = row / rpb;
-    float xv[MAXC][8];
-    float ss = 0.f;
+    float xh[MAXC][8], dxh[MAXC][8];
+    float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
         const int ci = c * 64 + lane;
         if (ci < nchunk) {
-            float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            const float* pp = partials + row * D + ci * 8;
-            for (int s = 0; s < splits; ++s) {
-                float t[8];
-                loadf8(pp + (int64_t)s * split_stride, t);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) acc[e] += t[e];
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] = rbf(acc[e]);
-            if (gate_prev != nullptr) {
-                float g[8];
-                load8(gate_prev + b * D + ci * 8, g);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) acc[e] = rbf(acc[e] * g[e]);
-            }
-            if (residual != nullptr) {
-                float r[8];
-                load8(residual + row * D + ci * 8, r);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) acc[e] = rbf(acc[e] + r[e]);
-            }
-            store8(x_out + row * D + ci * 8, acc);
+            float dyv[8];
+            load8(dy + row * D + ci * 8, dyv);
+            load8(x + row * D + ci * 8, xh[c]);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                xv[c][e] = acc[e];
-                ss += acc[e] * acc[e];
+                xh[c][e] = (xh[c][e] - mean) * rstd;
+                dxh[c][e] = dyv[e] * cw[c][e];
+                if constexpr (LN) s1 += dxh[c][e];
+                s2 += dxh[c][e] * xh[c][e];
+                acc(c, e, dyv[e], xh[c][e]);
             }
         }
     }
-    ss = wave_sum(ss);
-    const float rstd = rsqrtf(ss / (float)D + eps);
-    const float* mrow = mod + b * (int64_t)(3 * D);
+    if constexpr (LN) s1 = wave_sum(s1) / (float)D;
+    s2 = wave_sum(s2) / (float)D;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
         const int ci = c * 64 + lane;
         if (ci < nchunk) {
-            float o[8], sc[8], sh[8];
-            loadf8(mrow + ci * 8, sc);
-            loadf8(mrow + D + ci * 8, sh);
+            float o[8], rs[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (xv[c][e] * rstd) * (1.0f + sc[e]) + sh[e];
-            store8(y + row * D + ci * 8, o);
-            if (gate_out != nullptr && (row % rpb) == 0) {
-                float gt[8];
-                loadf8(mrow + 2 * D + ci * 8, gt);
-                store8(gate_out + b * (int64_t)D + ci * 8, gt);
-            }
+            for (int e = 0; e < 8; ++e) rs[e] = 0.f;
+            if (dres != nullptr) load8(dres + row * D + ci * 8, rs);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = rstd * (dxh[c][e] - s1 - xh[c][e] * s2) + rs[e];
+            store8(dx + row * D + ci * 8, o);
         }
     }
 }
 
-// plain RMSNorm backward: dx and per-wave dw partials [gridDim.x*4][D]
+// The tail of rmsnorm_bwd (NS = 1: dw) and layernorm_bwd (NS = 2: dw | db): the block's 4 wave partials meet in LDS and leave as one
+// partial row of NS * D columns per block (a quarter of the bytes the column reduction reads).
+template <int NS>
+__device__ __forceinline__ void block_partial_row(const float (&sums)[NS][MAXC][8], int D, int lane, float* __restrict__ partial) {
+    extern __shared__ float nred[];  // [4][NS * D]
+    const int W = NS * D, nchunk = D >> 3;
+    float* pr = nred + (threadIdx.x >> 6) * W;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        const int ci = c * 64 + lane;
+        if (ci < nchunk) {
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                const float(&v)[8] = sums[k][c];
+                *reinterpret_cast<f32x4*>(pr + k * D + ci * 8) = f32x4{v[0], v[1], v[2], v[3]};
+                *reinterpret_cast<f32x4*>(pr + k * D + ci * 8 + 4) = f32x4{v[4], v[5], v[6], v[7]};
+            }
+        }
+    }
+    __syncthreads();
+    for (int col = threadIdx.x; col < W; col += 256)
+        partial[(int64_t)blockIdx.x * W + col] = (nred[col] + nred[W + col]) + (nred[2 * W + col] + nred[3 * W + col]);
+}
+
+// plain RMSNorm backward: dx and one dw partial row per block, dw_partial [gridDim.x][D]
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                           const float* __restrict__ w, const float* __restrict__ rstd_in,
                                                           bf16_t* __restrict__ dx, float* __restrict__ dw_partial,
@@ -361,68 +362,23 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
     const int64_t wg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t nw = (int64_t)gridDim.x * 4;
     const int nchunk = D >> 3;
-    float dwa[MAXC][8];
+    float dwa[1][MAXC][8];
     float cw[MAXC][8];
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
         const int ci = c * 64 + lane;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { dwa[c][e] = 0.f; cw[c][e] = 0.f; }
+        for (int e = 0; e < 8; ++e) { dwa[0][c][e] = 0.f; cw[c][e] = 0.f; }
         if (ci < nchunk) {
             loadf8(w + ci * 8, cw[c]);
 #pragma unroll
             for (int e = 0; e < 8; ++e) cw[c][e] += 1.0f;
         }
     }
-    for (int64_t row = wg; row < rows; row += nw) {
-        const float rstd = rstd_in[row];
-        float xh[MAXC][8], dxh[MAXC][8];
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int ci = c * 64 + lane;
-            if (ci < nchunk) {
-                float dyv[8];
-                load8(dy + row * D + ci * 8, dyv);
-                load8(x + row * D + ci * 8, xh[c]);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    xh[c][e] *= rstd;
-                    dxh[c][e] = dyv[e] * cw[c][e];
-                    s += dxh[c][e] * xh[c][e];
-                    dwa[c][e] += dyv[e] * xh[c][e];
-                }
-            }
-        }
-        s = wave_sum(s) / (float)D;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int ci = c * 64 + lane;
-            if (ci < nchunk) {
-                float o[8], rs[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) rs[e] = 0.f;
-                if (dres != nullptr) load8(dres + row * D + ci * 8, rs);  // gradient of the residual branch of x
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = rstd * (dxh[c][e] - xh[c][e] * s) + rs[e];
-                store8(dx + row * D + ci * 8, o);
-            }
-        }
-    }
-    // the block's 4 wave partials meet in LDS: one partial row per block (a quarter of the bytes the column reduction reads)
-    extern __shared__ float nred[];  // [4][D]
-    float* pr = nred + (threadIdx.x >> 6) * D;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-        const int ci = c * 64 + lane;
-        if (ci < nchunk) {
-            *reinterpret_cast<f32x4*>(pr + ci * 8) = f32x4{dwa[c][0], dwa[c][1], dwa[c][2], dwa[c][3]};
-            *reinterpret_cast<f32x4*>(pr + ci * 8 + 4) = f32x4{dwa[c][4], dwa[c][5], dwa[c][6], dwa[c][7]};
-        }
-    }
-    __syncthreads();
-    for (int col = threadIdx.x; col < D; col += 256)
-        dw_partial[(int64_t)blockIdx.x * D + col] = (nred[col] + nred[D + col]) + (nred[2 * D + col] + nred[3 * D + col]);
+    for (int64_t row = wg; row < rows; row += nw)
+        norm_bwd_row<false>(dy, x, dres, dx, row, D, lane, 0.f, rstd_in[row], cw,
+                            [&](int c, int e, float dyv, float xh) { dwa[0][c][e] += dyv * xh; });
+    block_partial_row<1>(dwa, D, lane, dw_partial);
 }
 
 // adaRMS backward: one block of 8 waves per batch entry b (rows b*rpb .. b*rpb+rpb-1); a wave owns whole rows (lane -> chunks
@@ -453,40 +409,10 @@ __global__ __launch_bounds__(512) void adarms_bwd_kernel(const bf16_t* __restric
     }
     for (int i = wave; i < rpb; i += 8) {
         const int64_t row = (int64_t)b * rpb + i;
-        const float rstd = rstd_in[row];
-        float xh[MAXC][8], dxh[MAXC][8];
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int ci = c * 64 + lane;
-            if (ci < nchunk) {
-                float dyv[8];
-                load8(dy + row * D + ci * 8, dyv);
-                load8(x + row * D + ci * 8, xh[c]);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    xh[c][e] *= rstd;
-                    dxh[c][e] = dyv[e] * c1[c][e];
-                    s += dxh[c][e] * xh[c][e];
-                    dsc[c][e] += dyv[e] * xh[c][e];
-                    dsh[c][e] += dyv[e];
-                }
-            }
-        }
-        s = wave_sum(s) / (float)D;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int ci = c * 64 + lane;
-            if (ci < nchunk) {
-                float o[8], rs[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) rs[e] = 0.f;
-                if (dres != nullptr) load8(dres + row * D + ci * 8, rs);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = rstd * (dxh[c][e] - xh[c][e] * s) + rs[e];
-                store8(dx + row * D + ci * 8, o);
-            }
-        }
+        norm_bwd_row<false>(dy, x, dres, dx, row, D, lane, 0.f, rstd_in[row], c1, [&](int c, int e, float dyv, float xh) {
+            dsc[c][e] += dyv * xh;
+            dsh[c][e] += dyv;
+        });
     }
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
@@ -569,7 +495,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const bf16_t* __rest
     }
 }
 
-// dx and per-wave partials [gridDim.x*4][2*D] = [dw | db]
+// dx and one partial row per block, partial [gridDim.x][2 D] = [dw | db]
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                             const bf16_t* __restrict__ w, const float* __restrict__ mean_in,
                                                             const float* __restrict__ rstd_in, bf16_t* __restrict__ dx,
@@ -579,78 +505,30 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
     const int64_t wg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t nw = (int64_t)gridDim.x * 4;
     const int nchunk = D >> 3;
-    float dwa[MAXC][8], dba[MAXC][8], wv[MAXC][8];
+    float dwb[2][MAXC][8], wv[MAXC][8];  // dwb: [dw | db]
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
         const int ci = c * 64 + lane;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { dwa[c][e] = 0.f; dba[c][e] = 0.f; wv[c][e] = 0.f; }
+        for (int e = 0; e < 8; ++e) { dwb[0][c][e] = 0.f; dwb[1][c][e] = 0.f; wv[c][e] = 0.f; }
         if (ci < nchunk) load8(w + ci * 8, wv[c]);
     }
-    for (int64_t row = wg; row < rows; row += nw) {
-        const float mean = mean_in[row], rstd = rstd_in[row];
-        float xh[MAXC][8], dxh[MAXC][8];
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int ci = c * 64 + lane;
-            if (ci < nchunk) {
-                float dyv[8];
-                load8(dy + row * D + ci * 8, dyv);
-                load8(x + row * D + ci * 8, xh[c]);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    xh[c][e] = (xh[c][e] - mean) * rstd;
-                    dxh[c][e] = dyv[e] * wv[c][e];
-                    s1 += dxh[c][e];
-                    s2 += dxh[c][e] * xh[c][e];
-                    dwa[c][e] += dyv[e] * xh[c][e];
-                    dba[c][e] += dyv[e];
-                }
-            }
-        }
-        s1 = wave_sum(s1) / (float)D;
-        s2 = wave_sum(s2) / (float)D;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int ci = c * 64 + lane;
-            if (ci < nchunk) {
-                float o[8], rs[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) rs[e] = 0.f;
-                if (dres != nullptr) load8(dres + row * D + ci * 8, rs);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = rstd * (dxh[c][e] - s1 - xh[c][e] * s2) + rs[e];
-                store8(dx + row * D + ci * 8, o);
-            }
-        }
-    }
-    extern __shared__ float nred[];  // [4][2 D]: the block's wave partials -> one partial row per block
-    float* pr = nred + (threadIdx.x >> 6) * (2 * D);
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-        const int ci = c * 64 + lane;
-        if (ci < nchunk) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                pr[ci * 8 + e] = dwa[c][e];
-                pr[D + ci * 8 + e] = dba[c][e];
-            }
-        }
-    }
-    __syncthreads();
-    const int W = 2 * D;
-    for (int col = threadIdx.x; col < W; col += 256)
-        partial[(int64_t)blockIdx.x * W + col] = (nred[col] + nred[W + col]) + (nred[2 * W + col] + nred[3 * W + col]);
+    for (int64_t row = wg; row < rows; row += nw)
+        norm_bwd_row<true>(dy, x, dres, dx, row, D, lane, mean_in[row], rstd_in[row], wv, [&](int c, int e, float dyv, float xh) {
+            dwb[0][c][e] += dyv * xh;
+            dwb[1][c][e] += dyv;
+        });
+    block_partial_row<2>(dwb, D, lane, partial);
 }
 
 // ------------------------------------------------------------------------------------ column reductions
-__global__ __launch_bounds__(1024) void reduce_partials_kernel(const float* __restrict__ partial, int blocks, int ncols,
-                                                               int64_t ld, void* __restrict__ out, int out_f32) {
-    // 64 columns x 16 row-groups per block; fixed summation order (deterministic)
+// out[col] = sum_b partial[b][col] for the 64 columns of column block `cblock`: 64 columns x 16 row-groups per block; fixed
+// summation order (deterministic)
+__device__ __forceinline__ void reduce_partials_block(const float* __restrict__ partial, int blocks, int ncols, int64_t ld,
+                                                      void* __restrict__ out, int out_f32, int cblock) {
     __shared__ float red[16][64];
     const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int col = blockIdx.x * 64 + cl;
+    const int col = cblock * 64 + cl;
     float s = 0.f;
     if (col < ncols)
         for (int b = rg; b < blocks; b += 16) s += partial[(int64_t)b * ld + col];
@@ -665,6 +543,11 @@ __global__ __launch_bounds__(1024) void reduce_partials_kernel(const float* __re
     }
 }
 
+__global__ __launch_bounds__(1024) void reduce_partials_kernel(const float* __restrict__ partial, int blocks, int ncols,
+                                                               int64_t ld, void* __restrict__ out, int out_f32) {
+    reduce_partials_block(partial, blocks, ncols, ld, out, out_f32, blockIdx.x);
+}
+
 // The same reduction for up to 32 (partials, destination) pairs in one launch: the final sums of the norm-weight and bias
 // gradients are ~9 us launches of 2-4 MB each (254 per training step); ops.py queues them during backward and flushes the
 // queue before anything reads the gradients.  Block b belongs to the item whose block range [first[i], first[i+1]) holds it.
@@ -673,24 +556,10 @@ struct ReduceBatch {
     int first[33];
 };
 __global__ __launch_bounds__(1024) void reduce_partials_batch_kernel(ReduceBatch rb, int n) {
-    __shared__ float red[16][64];
     int i = 0;
     while (i + 1 < n && (int)blockIdx.x >= rb.first[i + 1]) ++i;
     const kai0_reduce_item it = rb.it[i];
-    const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int col = ((int)blockIdx.x - rb.first[i]) * 64 + cl;
-    float s = 0.f;
-    if (col < it.ncols)
-        for (int b = rg; b < it.blocks; b += 16) s += it.partial[(int64_t)b * it.ld + col];
-    red[rg][cl] = s;
-    __syncthreads();
-    if (rg == 0 && col < it.ncols) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += red[k][cl];
-        if (it.out_f32) reinterpret_cast<float*>(it.out)[col] = t;
-        else reinterpret_cast<bf16_t*>(it.out)[col] = f2bf(t);
-    }
+    reduce_partials_block(it.partial, it.blocks, it.ncols, it.ld, it.out, it.out_f32, (int)blockIdx.x - rb.first[i]);
 }
 
 // Column sums of a [M][N] bf16 matrix (bias gradients): block (x, y) covers the 512 columns [512 x, 512 x + 512) — one wave
@@ -806,18 +675,6 @@ KAI0_API int kai0_denoise_glue(const void* xs, const float* mod, int64_t mod_ld,
                                int64_t rows, int D, int A, float* rowsq_next, kai0_stream_t stream) {
     return denoise_glue_launch("kai0_denoise_glue", false, xs, mod, mod_ld, rows_per_batch, eps, w_out, b_out, x_t, dt, w_in, b_in, xs_next, rows, D,
                                A, rowsq_next, 0, 0, 0, stream);
-}
-
-KAI0_API int kai0_adarms_combine(const float* partials, int splits, int64_t split_stride, const void* gate_prev,
-                                 const void* residual, void* x_out, const float* mod, void* y, void* gate_out,
-                                 int64_t rows, int rows_per_batch, int D, float eps, kai0_stream_t stream) {
-    CHECK_D("kai0_adarms_combine", D);
-    KAI0_REQUIRE(partials && splits >= 1 && x_out && mod && y && rows_per_batch > 0, "kai0_adarms_combine: bad arguments");
-    if (rows <= 0) return 0;
-    hipLaunchKernelGGL(adarms_combine_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, partials,
-                       splits, split_stride, (const bf16_t*)gate_prev, (const bf16_t*)residual, (bf16_t*)x_out, mod,
-                       (bf16_t*)y, (bf16_t*)gate_out, rows, rows_per_batch, D, eps);
-    return kai0_check_launch("kai0_adarms_combine");
 }
 
 KAI0_API int kai0_adarms_bwd(const void* dy, const void* dgate, const void* x, const float* mod, const float* rstd,

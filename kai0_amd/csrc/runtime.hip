@@ -47,7 +47,7 @@ hipError_t kai0_reserve_lds(const void* kernel, int bytes) {
 }
 
 KAI0_API const char* kai0_last_error(void) { return g_err; }
-KAI0_API int kai0_abi_version(void) { return 3; }
+KAI0_API int kai0_abi_version(void) { return 4; }
 KAI0_API int kai0_gemm_desc_size(void) { return (int)sizeof(kai0_gemm_desc); }
 
 KAI0_API int kai0_device_info(int device, int* n_cu, int* lds_bytes, char* arch_name64) {

@@ -11,7 +11,7 @@
 //     bytes per row (the contraction index inside a 128-chunk is permuted identically for A and W, which a dot
 //     product does not care about), all loads of a chunk in flight before the first MFMA;
 //   * wave partials meet in LDS; with split_k > 1 the block writes its raw f32 partial product [split][M][N] and the
-//     consumer kernel (kai0_adarms_combine: gated residual + adaRMS, needed anyway) adds the splits in a fixed order.
+//     consumer adds the splits in a fixed order.
 //     (An in-kernel "last block reduces" scheme was measured at 24-41 us per launch: the agent-scope fences it needs
 //     write back / invalidate the whole L2.  The kernel boundary gives the same visibility for free.)
 //   * epilogues (rounding points identical to the separate kernels they replace, see kai0hip.h):
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(NW * 64, 1) void skinny_kernel(const SkinnyArgs p) 
         v1[e] = s1;
     }
 
-    // ---- split-K: raw f32 partial products [split][M][N]; the consumer (kai0_adarms_combine) adds them in order ----
+    // ---- split-K: raw f32 partial products [split][M][N]; the consumer adds them in order ----
     if (p.split_k > 1) {
         const int mrow_p = m0 + row;
         if (mrow_p < p.M) {
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(NW * 64, 1) void skinny_kernel(const SkinnyArgs p) 
 // mode 0) — a 1024-column o_proj / down_proj is 64 blocks of 64-128 KB of weights each: the launch is one memory latency long,
 // which is what matters for a 50-row GEMM; the former split-K version needed its partials finished by a separate launch.
 //   ADA: the A operand is adaRMS-normalised on the fly (K == D, the block's waves hold complete rows): y = bf16((x * rstd) *
-//   (1 + scale) + shift), rstd over the row, scale / shift from `mod` — the norm that kai0_adarms_combine applied in a launch
+//   (1 + scale) + shift), rstd over the row, scale / shift from `mod` — kai0_adarms_fwd's arithmetic without a launch
 //   of its own (modeling_gemma.py:49-104).
 //   MTL = 16-row tiles per block: 4 (all 64 rows; the weight slice is read once) for the wide q|k|v and gate|up launches, 1 for the
 //   1024-column o_proj / down_proj, whose 64 column tiles alone would leave three quarters of the chip idle: their four row

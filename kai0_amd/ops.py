@@ -186,17 +186,6 @@ def gemm_plan(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, **kw) -> dict
     return plan
 
 
-def skinny_split_k(N: int, K: int) -> int:
-    """Split of the contraction for a mode-0 kai0_gemm_skinny_bf16 whose consumer is kai0_adarms_combine: enough blocks
-    to occupy the chip (N/32 tiles x split >= ~190), K / split in {1024, 512}."""
-    if K % 512:
-        raise _lib.Kai0HipError(f"skinny gemm: K={K} must be a multiple of 512")
-    tiles = N // 32
-    if K % 1024 == 0 and tiles * (K // 1024) >= 190:
-        return K // 1024
-    return K // 512
-
-
 def skinny_workspace(M: int, N: int, split_k: int, device) -> torch.Tensor:
     """f32 [split_k][M][N] partial-product buffer of a split-K skinny GEMM."""
     return torch.empty((max(split_k, 1), M, N), dtype=F32, device=device)
@@ -263,20 +252,6 @@ def pack_skinny_weight(w: torch.Tensor) -> torch.Tensor:
     if N % 16 or K % 32:
         raise ValueError(f"pack_skinny_weight: N % 16 == 0 and K % 32 == 0 required, got {tuple(w.shape)}")
     return w.view(N // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(N, K)
-
-
-def adarms_combine(partials, gate_prev, residual, mod, rows_per_batch: int, eps: float = 1e-6):
-    """kai0_adarms_combine: partials f32 [S][rows][D] -> (x, y, gate) with x = gated residual of the summed product,
-    (y, gate) = adaRMS(x, mod)."""
-    S, rows, D = partials.shape
-    Bn = rows // rows_per_batch
-    dev = partials.device
-    x = torch.empty((rows, D), dtype=BF16, device=dev)
-    y = torch.empty((rows, D), dtype=BF16, device=dev)
-    gate = torch.empty((Bn, D), dtype=BF16, device=dev)
-    _lib.call("kai0_adarms_combine", partials.data_ptr(), S, rows * D, _p(gate_prev), _p(residual), x.data_ptr(),
-              mod.data_ptr(), y.data_ptr(), gate.data_ptr(), rows, rows_per_batch, D, eps, _stream())  # fmt: skip
-    return x, y, gate
 
 
 def attn_decode(Q, K, Vt, O, qcode, kcode, *, batch, rows, H, HD, Sk, q0, q_bs, k_bs, k_ld, k_rows, vt_bs, vt_ld, scale):

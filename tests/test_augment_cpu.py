@@ -193,9 +193,9 @@ def test_header_binding_and_abi():
     p, i = C.c_void_p, C.c_int
     assert _lib._PROTOS["kai0_augment_f32"] == [p, p, p, p, i, i, i, i, i, p]
     assert {"kai0_augment_f32", "kai0_augment_scratch_floats"} <= set(_lib.EXPORTED_SYMBOLS)
-    assert "augment.hip" in SRC and _lib.ABI_VERSION == 3
+    assert "augment.hip" in SRC and _lib.ABI_VERSION == 4
     lib = _lib.load()
-    assert lib.kai0_abi_version() == 3
+    assert lib.kai0_abi_version() == 4
     # the scratch size needs no device: one float per block of 1024 pixels and sample; 0 outside the contract
     assert lib.kai0_augment_scratch_floats(32, 3, 224, 224) == 32 * 49
     assert lib.kai0_augment_scratch_floats(3, 3, 17, 23) == 3

@@ -242,7 +242,7 @@ def test_cabi_v2_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in kai0hip.h but not exported"
     assert declared == set(_lib.EXPORTED_SYMBOLS), declared ^ set(_lib.EXPORTED_SYMBOLS)
-    assert lib.kai0_abi_version() == 3
+    assert lib.kai0_abi_version() == 4
     assert ctypes.sizeof(_lib.GemmDesc) == lib.kai0_gemm_desc_size()
 
 

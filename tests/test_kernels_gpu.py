@@ -951,37 +951,6 @@ def test_skinny_plain_gate_residual(ops, M, K, N):
     assert rel_err(out, ref) < 2e-3
 
 
-@pytest.mark.parametrize("M,K,N,split", [(50, 2048, 1024, 4), (50, 4096, 1024, 8), (100, 4096, 1024, 4)])
-def test_skinny_splitk_partials_and_adarms_combine(ops, M, K, N, split):
-    """o_proj / down_proj form: split-K partial products + kai0_adarms_combine (sum, gated residual, adaRMS) ==
-    kai0_gemm_bf16 with the fused gate/residual epilogue followed by kai0_adarms_fwd; bit-stable across launches."""
-    rpb, S_ld, row0 = 50, 72, 11
-    nb = M // rpb
-    a_buf = rnd(nb * S_ld, K, seed=1)
-    w = rnd(N, K, seed=2, scale=0.05)
-    gate = rnd(nb, N, seed=3)
-    res = rnd(M, N, seed=4)
-    mod = rnd(nb, 3 * N, dtype=F32, seed=5, scale=0.3)
-    x_ref = torch.empty(M, N, dtype=BF16, device=dev())
-    ops.gemm(a_buf, w, x_ref, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, a_map=(rpb, S_ld, row0), gate=gate, gate_rpb=rpb,
-             gate_ld=N, residual=res, ldr=N)
-    y_ref, g_ref = ops.adarms(x_ref, mod, rpb, 1e-6)
-    ws = ops.skinny_workspace(M, N, split, dev())
-    outs = []
-    for _ in range(2):
-        ws.fill_(float("nan"))
-        ops.skinny_gemm(a_buf, w, M=M, N=N, K=K, lda=K, ldw=K, split_k=split, workspace=ws, a_map=(rpb, S_ld, row0))
-        outs.append(ops.adarms_combine(ws, gate, res, mod, rpb, 1e-6))
-    for a, b in zip(outs[0], outs[1]):
-        assert torch.equal(a, b)
-    x, y, g = outs[0]
-    assert torch.equal(g, g_ref)
-    assert rel_err(x, x_ref) < 2e-3 and rel_err(y, y_ref) < 3e-3
-    # adaRMS of the combined x itself is exact
-    y2, _ = ops.adarms(x, mod, rpb, 1e-6)
-    assert torch.equal(y, y2)
-
-
 def test_skinny_qkv_rope_segments(ops):
     """fused q|k|v projection + RoPE written through the row map into three buffers == separate GEMMs + kai0_rope_inplace."""
     B, Hs, P, S_ld, H, HD, K = 1, 50, 30, 88, 8, 256, 1024

@@ -314,7 +314,7 @@ def test_entry_points_are_declared_and_bound():
     p, i, i64 = C.c_void_p, C.c_int, C.c_int64
     assert _lib._PROTOS["kai0_mix"] == [C.POINTER(p), i, C.POINTER(C.c_float), i, p, i, i64, p]
     assert _lib._PROTOS["kai0_multi_dot"] == [p, i, C.POINTER(p), i, i, i64, p, p, p]
-    assert {"kai0_mix", "kai0_multi_dot"} <= set(_lib.EXPORTED_SYMBOLS) and _lib.ABI_VERSION == 3
+    assert {"kai0_mix", "kai0_multi_dot"} <= set(_lib.EXPORTED_SYMBOLS) and _lib.ABI_VERSION == 4
     assert callable(optim.mix_) and callable(optim.multi_dot_) and optim.MAX_MIX_SOURCES == ma.MAX_SOURCES == 8
 
 

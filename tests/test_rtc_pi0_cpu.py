@@ -285,5 +285,5 @@ def test_overwrite_seam_is_declared_and_bound():
     assert "pi0_rtc.py:322-327" in header
     p, i, i64 = C.c_void_p, C.c_int, C.c_int64
     assert _lib._PROTOS["kai0_rtc_overwrite"] == [p, p, p, i, p, i64, i, i, p]
-    assert "kai0_rtc_overwrite" in set(_lib.EXPORTED_SYMBOLS) and _lib.ABI_VERSION == 3
+    assert "kai0_rtc_overwrite" in set(_lib.EXPORTED_SYMBOLS) and _lib.ABI_VERSION == 4
     assert callable(ops.rtc_overwrite)

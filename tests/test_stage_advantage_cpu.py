@@ -295,4 +295,4 @@ def test_prototypes_and_bindings():
     p, i, i64 = C.c_void_p, C.c_int, C.c_int64
     assert _lib._PROTOS["kai0_frames_to_chw"] == [p, p, i, i, i, i, i, i, i, i, i, p]
     assert _lib._PROTOS["kai0_prefix_gather"] == [p, p, p, p, i, i, i, i, i, i64, p]
-    assert "frames.hip" in SRC and _lib.ABI_VERSION == 3
+    assert "frames.hip" in SRC and _lib.ABI_VERSION == 4

@@ -853,6 +853,35 @@ def test_colsum_direct(M, N, out_f32):
     within(out.t, R.colsum(dy, N, F64)["out"], f"B colsum M={M} N={N} f32={out_f32}")
 
 
+def test_reduce_partials_batch_equals_single_launches():
+    """kai0_reduce_partials_batch, the form the training step launches, on 33 items: a second launch of the 32-item split.  The
+    items cycle through (blocks, ncols, f32 out, first column, ld) = (1, 8, f32, 0, 8): the smallest; (17, 70, bf16, 8, 96): a
+    partial second 64-column block, one pass of the 16-row-group loop and a remainder, columns read from inside a wider row;
+    (512, 520, f32, 0, 520): nine column blocks.  Every output equals kai0_reduce_partials on the same item bit for bit."""
+    import ctypes as C
+
+    from kai0_amd import _lib
+
+    shapes = [(1, 8, 1, 0, 8), (17, 70, 0, 8, 96), (512, 520, 1, 0, 520)]
+    parts, outs, single, fields = [], [], [], []
+    for i in range(33):
+        blocks, ncols, f32, col0, ld = shapes[i % 3]
+        part = rnd(blocks, ld, dtype=F32, seed=i)
+        parts.append(part)
+        outs.append(Out((ncols,), F32 if f32 else BF16))
+        single.append(Out((ncols,), F32 if f32 else BF16))
+        fields.append((part.data_ptr() + 4 * col0, blocks, ncols, ld, f32))
+    items = (_lib.ReduceItem * 33)(*[_lib.ReduceItem(src, P(o.t), ld, blocks, ncols, f32, 0) for (src, blocks, ncols, ld, f32), o in zip(fields, outs)])
+    call("kai0_reduce_partials_batch", C.addressof(items), 33)
+    for (src, blocks, ncols, ld, f32), o in zip(fields, single):
+        call("kai0_reduce_partials", src, blocks, ncols, ld, P(o.t), f32)
+    torch.cuda.synchronize()
+    for i, (o, s) in enumerate(zip(outs, single)):
+        o.check(f"reduce_partials_batch item {i}")
+        s.check(f"reduce_partials item {i}")
+        exact(o.t, s.t, f"reduce_partials_batch item {i} vs kai0_reduce_partials")
+
+
 @pytest.mark.parametrize("n", [5, 8, 13, 1000 + 5])
 def test_add_bf16_add_f32_small(n):
     a, b = rnd(n, seed=1), rnd(n, seed=2)
