@@ -803,6 +803,31 @@ int kai0_chunk_stats_hist(const float* state, int64_t ld_state, int ds, const fl
                           int clip_action, int mask_state, uint32_t delta_mask, const double* edges, int bins, uint32_t col_mask,
                           unsigned long long* hist, kai0_stream_t stream);
 
+/* The same two passes over a dataset VIEW (kai0_amd.lerobot_dataset.view_plan): time scaling keeps every Nth row of an
+ * episode, space mirroring swaps the two arms.  The contract is that of the pair above, with per frame m
+ *     s = frame_stride ? max(frame_stride[m], 1) : 1         (int32 [M] or NULL)
+ *     mirrored = frame_mirror ? frame_mirror[m] != 0 : 0     (uint8 [M] or NULL)
+ * and, for i = frame_idx[m] (a kept row of its episode by construction), chunk row h and OUTPUT column c:
+ *     row = min(i + h * s, i + ((ep_end[i] - 1 - i) / s) * s)                  (the last kept row of i's episode; evaluated as
+ *                                                                                i + min(h, (ep_end[i] - 1 - i) / s) * s: no stride
+ *                                                                                value overflows or leaves the episode)
+ *     src = !mirrored ? c : c < right_dim ? left_dim + c : c < left_dim + right_dim ? c - right_dim : c
+ *     a = src < da ? action[row * ld_action + src] : 0;   s = (mask_state || src >= ds) ? 0 : state[i * ld_state + src]
+ * after which clip, delta_mask bit c (an OUTPUT column) and the subtract apply as above: what the pair above computes on a parquet
+ * whose vectors were rewritten as [right | left | rest].  left_dim, right_dim >= 0 and left_dim + right_dim <= width, or the call is
+ * refused before any launch.  With frame_stride == frame_mirror == NULL the launches are those of the pair above (the same bits).
+ * The workspace of kai0_chunk_stats_moments_view is kai0_chunk_stats_workspace_bytes(M, width). */
+int kai0_chunk_stats_moments_view(const float* state, int64_t ld_state, int ds, const float* action, int64_t ld_action, int da,
+                                  const int32_t* ep_end, int N, const int32_t* frame_idx, const int32_t* frame_stride,
+                                  const uint8_t* frame_mirror, int left_dim, int right_dim, int M, int horizon, int width, int clip_state,
+                                  int clip_action, int mask_state, uint32_t delta_mask, double* out, void* workspace,
+                                  int64_t workspace_bytes, kai0_stream_t stream);
+int kai0_chunk_stats_hist_view(const float* state, int64_t ld_state, int ds, const float* action, int64_t ld_action, int da,
+                               const int32_t* ep_end, int N, const int32_t* frame_idx, const int32_t* frame_stride,
+                               const uint8_t* frame_mirror, int left_dim, int right_dim, int M, int horizon, int width, int clip_state,
+                               int clip_action, int mask_state, uint32_t delta_mask, const double* edges, int bins, uint32_t col_mask,
+                               unsigned long long* hist, kai0_stream_t stream);
+
 /* Train-time image augmentation with its own parameters for every sample (models_pytorch/preprocessing_pytorch.py:52-142: the
  * arithmetic; models/model.py:196-214, augmax under jax.vmap with one key per sample: the granularity).  The definition is
  * kai0_amd.preprocessing.augment_apply_torch; kai0_amd.preprocessing.sample_augment_params draws the parameters on the host.

@@ -244,6 +244,10 @@ _PROTOS: dict[str, list] = {
     "kai0_chunk_stats_moments": [c_p, c_i64, c_i, c_p, c_i64, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, C.c_uint32, c_p, c_p, c_i64, c_p],
     "kai0_chunk_stats_hist": [c_p, c_i64, c_i, c_p, c_i64, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, C.c_uint32, c_p, c_i, C.c_uint32,
                               c_p, c_p],
+    "kai0_chunk_stats_moments_view": [c_p, c_i64, c_i, c_p, c_i64, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
+                                      C.c_uint32, c_p, c_p, c_i64, c_p],
+    "kai0_chunk_stats_hist_view": [c_p, c_i64, c_i, c_p, c_i64, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
+                                   C.c_uint32, c_p, c_i, C.c_uint32, c_p, c_p],
     "kai0_augment_f32": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
 }  # fmt: skip
 

@@ -1,5 +1,5 @@
 // norm_stats.hip — normalisation statistics over action chunks (kai0_amd/norm_stats.py; kai0hip.h kai0_chunk_stats_moments /
-// kai0_chunk_stats_hist).
+// kai0_chunk_stats_hist and their _view forms).
 // The statistic covers M x horizon x width virtual elements, every one a function of two small resident tables ([N, ds] state,
 // [N, da] action) and the episode ends: chunk row h of frame i is action row min(i + h, ep_end[i] - 1) (lerobot's window clamp), zero-padded
 // to `width`, glitch-filtered (|x| > f32(pi) -> 0, agilex_policy.py `_clip_glitches`) and shifted by the frame's state on the columns of
@@ -12,6 +12,11 @@
 //             walks the horizon of ONE (frame, column) and merges equal consecutive bins in a register before it touches LDS:
 //             the chunk rows of a frame are neighbouring samples of one trajectory (and identical past the episode's end), so most
 //             of the same-address LDS traffic — gripper columns on two values, slow joints — never happens.
+// The _view entry points read a dataset VIEW through the same two kernels, instantiated with VIEW = true: a frame may
+// step through its episode with a stride (time scaling: chunk row h is the h-th KEPT row after it, clamped to the last kept row) and
+// may be mirrored (space mirroring: output column c reads the table column the arm swap maps to it).  A chunk row is addressed as
+// i + min(h, steps) * stride with steps = (last row of the episode - i) / stride, so the product never passes the episode's end:
+// no stride value can overflow the index or reach a row outside the table.
 #include "common.h"
 #include "../../include/kai0hip.h"
 
@@ -28,6 +33,9 @@ struct ChunkArgs {
     const float* action;
     const int32_t* ep_end;
     const int32_t* frame_idx;
+    const int32_t* frame_stride;  // the _view forms only: NULL = 1
+    const uint8_t* frame_mirror;  //                       NULL = 0
+    int left_dim, right_dim;
     int64_t ld_state, ld_action;
     int ds, da, N, M, horizon, width;
     int clip_state, clip_action, mask_state;
@@ -39,24 +47,46 @@ __device__ __forceinline__ float clip_glitch(float x) {
     return fabsf(x) > kPi ? 0.0f : x;
 }
 
-// frame m of the launch -> table row i (or -1: outside the table, skipped) and the last row of its episode
-__device__ __forceinline__ int frame_of(const ChunkArgs& p, int m, int& last) {
-    const int i = p.frame_idx ? p.frame_idx[m] : m;
-    if ((unsigned)i >= (unsigned)p.N) return -1;
-    last = max(i, min(p.ep_end[i], p.N) - 1);
-    return i;
+// frame m of the launch: its table row i, the stride between its chunk rows, how many strides fit before its episode ends, and
+// whether its columns go through the arm swap
+struct Frame {
+    int i, stride, steps;
+    bool mirror;
+};
+
+// false: frame_idx[m] lies outside the table and the frame is skipped
+template <bool VIEW>
+__device__ __forceinline__ bool frame_of(const ChunkArgs& p, int m, Frame& f) {
+    f.i = p.frame_idx ? p.frame_idx[m] : m;
+    if ((unsigned)f.i >= (unsigned)p.N) return false;
+    const int last = max(f.i, min(p.ep_end[f.i], p.N) - 1);
+    f.stride = 1, f.steps = last - f.i, f.mirror = false;
+    if (VIEW) {
+        if (p.frame_stride) f.stride = max(p.frame_stride[m], 1);
+        f.steps = (last - f.i) / f.stride;
+        f.mirror = p.frame_mirror && p.frame_mirror[m];
+    }
+    return true;
 }
 
-// what the state contributes to column c of every chunk row of frame i
-__device__ __forceinline__ float delta_offset(const ChunkArgs& p, int i, int c, bool& has) {
+__device__ __forceinline__ int chunk_row(const Frame& f, int h) { return f.i + min(h, f.steps) * f.stride; }
+
+// the table column that output column c of a frame reads: [left | right | rest] -> [right | left | rest] for a mirrored one
+__device__ __forceinline__ int source_column(const ChunkArgs& p, const Frame& f, int c) {
+    if (!f.mirror || c >= p.left_dim + p.right_dim) return c;
+    return c < p.right_dim ? p.left_dim + c : c - p.right_dim;
+}
+
+// what the state contributes to output column c (read from table column src) of every chunk row of frame i
+__device__ __forceinline__ float delta_offset(const ChunkArgs& p, int i, int c, int src, bool& has) {
     has = (p.delta_mask >> c) & 1u;
-    if (!has || p.mask_state || c >= p.ds) return 0.0f;
-    const float s = p.state[(int64_t)i * p.ld_state + c];
+    if (!has || p.mask_state || src >= p.ds) return 0.0f;
+    const float s = p.state[(int64_t)i * p.ld_state + src];
     return p.clip_state ? clip_glitch(s) : s;
 }
 
-__device__ __forceinline__ float chunk_value(const ChunkArgs& p, int row, int c, bool has, float off) {
-    float a = c < p.da ? p.action[(int64_t)row * p.ld_action + c] : 0.0f;
+__device__ __forceinline__ float chunk_value(const ChunkArgs& p, int row, int src, bool has, float off) {
+    float a = src < p.da ? p.action[(int64_t)row * p.ld_action + src] : 0.0f;
     if (p.clip_action) a = clip_glitch(a);
     return has ? a - off : a;
 }
@@ -66,19 +96,20 @@ __device__ __forceinline__ double nan_min(double a, double b) { return (b < a ||
 __device__ __forceinline__ double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
 
 // partial[block][width][4] = {min, max, sum, sum of squares} of the block's frames
+template <bool VIEW>
 __global__ __launch_bounds__(MOM_THREADS) void chunk_moments_kernel(const ChunkArgs p, double* __restrict__ partial) {
     __shared__ double red[MOM_FRAMES][32][4];
     const int c = threadIdx.x & 31, sub = threadIdx.x >> 5;
     double lo = __builtin_inf(), hi = -__builtin_inf(), sum = 0.0, sq = 0.0;
     if (c < p.width) {
         for (int64_t m = (int64_t)blockIdx.x * MOM_FRAMES + sub; m < p.M; m += (int64_t)gridDim.x * MOM_FRAMES) {
-            int last;
-            const int i = frame_of(p, (int)m, last);
-            if (i < 0) continue;
+            Frame f;
+            if (!frame_of<VIEW>(p, (int)m, f)) continue;
+            const int src = VIEW ? source_column(p, f, c) : c;
             bool has;
-            const float off = delta_offset(p, i, c, has);
+            const float off = delta_offset(p, f.i, c, src, has);
             for (int h = 0; h < p.horizon; ++h) {
-                const double x = (double)chunk_value(p, min(i + h, last), c, has, off);
+                const double x = (double)chunk_value(p, chunk_row(f, h), src, has, off);
                 lo = nan_min(lo, x);
                 hi = nan_max(hi, x);
                 sum += x;
@@ -132,6 +163,7 @@ __device__ __forceinline__ int find_bin(const double* __restrict__ e, int bins, 
     return k;
 }
 
+template <bool VIEW>
 __global__ __launch_bounds__(HIST_THREADS) void chunk_hist_kernel(const ChunkArgs p, const HistCols hc, const double* __restrict__ edges,
                                                                    int bins, unsigned long long* __restrict__ hist) {
     extern __shared__ uint32_t counts[];  // [hc.n][bins]
@@ -145,19 +177,19 @@ __global__ __launch_bounds__(HIST_THREADS) void chunk_hist_kernel(const ChunkArg
         const double inv = (double)bins / (e[bins] - e[0]);
         uint32_t* mycounts = counts + slot * bins;
         for (int64_t m = (int64_t)blockIdx.x * HIST_FRAMES + sub; m < p.M; m += (int64_t)gridDim.x * HIST_FRAMES) {
-            int last;
-            const int i = frame_of(p, (int)m, last);
-            if (i < 0) continue;
+            Frame f;
+            if (!frame_of<VIEW>(p, (int)m, f)) continue;
+            const int src = VIEW ? source_column(p, f, c) : c;
             bool has;
-            const float off = delta_offset(p, i, c, has);
+            const float off = delta_offset(p, f.i, c, src, has);
             int run_bin = -1;
             uint32_t run = 0;
             for (int h = 0; h < p.horizon; ++h) {
-                if (i + h > last && run_bin >= 0) {  // past the episode's end every row repeats the last one
+                if (h > f.steps && run_bin >= 0) {  // past the episode's end every row repeats the last one
                     run += (uint32_t)(p.horizon - h);
                     break;
                 }
-                const int k = find_bin(e, bins, inv, (double)chunk_value(p, min(i + h, last), c, has, off));
+                const int k = find_bin(e, bins, inv, (double)chunk_value(p, chunk_row(f, h), src, has, off));
                 if (k != run_bin) {
                     if (run) atomicAdd(mycounts + run_bin, run);
                     run_bin = k, run = 0;
@@ -198,6 +230,57 @@ int blocks_for(int M, int frames_per_trip, int min_trips, int max_blocks) {
     return (int)(want < 1 ? 1 : (want > max_blocks ? max_blocks : want));
 }
 
+// The view arguments: the swap must fit the launch's columns, the arrays must be addressable as what they are.  (A stride needs no
+// bound: see chunk_row.)
+int check_view_args(const char* who, const int32_t* frame_stride, int left_dim, int right_dim, int width) {
+    KAI0_REQUIRE(left_dim >= 0 && right_dim >= 0 && (int64_t)left_dim + right_dim <= width,
+                 "%s: left_dim=%d + right_dim=%d must fit width=%d", who, left_dim, right_dim, width);
+    KAI0_REQUIRE(((uintptr_t)frame_stride & 3) == 0, "%s: frame_stride is not aligned to 4 bytes", who);
+    return 0;
+}
+
+int launch_moments(const char* who, const ChunkArgs& a, bool view, double* out, void* workspace, int64_t workspace_bytes,
+                   kai0_stream_t stream) {
+    KAI0_REQUIRE(out && ((uintptr_t)out & 7) == 0, "%s: out must be an 8-byte aligned buffer of 4 * width doubles", who);
+    const int blocks = a.M ? blocks_for(a.M, MOM_FRAMES, MOM_MIN_TRIPS, MOM_MAX_BLOCKS) : 0;
+    KAI0_REQUIRE(a.M == 0 || (workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= kai0_chunk_stats_workspace_bytes(a.M, a.width)),
+                 "%s: needs an 8-byte aligned workspace of %lld bytes (got %lld)", who,
+                 (long long)kai0_chunk_stats_workspace_bytes(a.M, a.width), (long long)workspace_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    if (blocks && view) hipLaunchKernelGGL(chunk_moments_kernel<true>, dim3(blocks), dim3(MOM_THREADS), 0, s, a, (double*)workspace);
+    if (blocks && !view) hipLaunchKernelGGL(chunk_moments_kernel<false>, dim3(blocks), dim3(MOM_THREADS), 0, s, a, (double*)workspace);
+    hipLaunchKernelGGL(chunk_moments_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)workspace, blocks, a.width, out);
+    return kai0_check_launch(who);
+}
+
+int launch_hist(const char* who, const ChunkArgs& a, bool view, const double* edges, int bins, uint32_t col_mask, unsigned long long* hist,
+                kai0_stream_t stream) {
+    const int M = a.M, width = a.width, horizon = a.horizon;
+    KAI0_REQUIRE(bins >= 1 && (int64_t)bins * 4 <= HIST_LDS_BYTES, "%s: bins=%d outside 1..%d", who, bins, HIST_LDS_BYTES / 4);
+    KAI0_REQUIRE(width == 32 || (col_mask >> width) == 0, "%s: col_mask 0x%x selects a column >= width=%d", who, col_mask, width);
+    if (M == 0 || col_mask == 0) return 0;
+    KAI0_REQUIRE(edges && hist && (((uintptr_t)edges | (uintptr_t)hist) & 7) == 0, "%s: edges / hist must be 8-byte aligned", who);
+    HistCols hc{};
+    for (int c = 0; c < width; ++c)
+        if ((col_mask >> c) & 1u) hc.col[hc.total++] = c;
+    const int fit = HIST_LDS_BYTES / (bins * 4);  // columns whose u32 counters fit the 160 KiB of a CU
+    const int per_block = fit < HIST_COLS ? fit : HIST_COLS;
+    const int groups = (hc.total + per_block - 1) / per_block;
+    hc.n = (hc.total + groups - 1) / groups;  // even groups: 14 columns -> 7 + 7, not 8 + 6
+    const int blocks = blocks_for(M, HIST_FRAMES, HIST_MIN_TRIPS, HIST_MAX_BLOCKS);
+    // a block's u32 counters hold its whole slab
+    KAI0_REQUIRE(((int64_t)M + blocks - 1) / blocks * horizon + (int64_t)HIST_FRAMES * horizon <= 0xffffffffLL,
+                 "%s: M=%d x horizon=%d overflows a block's 32-bit counters", who, M, horizon);
+    const int lds = hc.n * bins * 4;
+    const void* kernel = view ? (const void*)chunk_hist_kernel<true> : (const void*)chunk_hist_kernel<false>;
+    const hipError_t e = kai0_reserve_lds(kernel, HIST_LDS_BYTES);
+    KAI0_REQUIRE(e == hipSuccess, "%s: cannot reserve %d B of LDS: %s", who, HIST_LDS_BYTES, hipGetErrorString(e));
+    const dim3 grid(blocks, groups);
+    if (view) hipLaunchKernelGGL(chunk_hist_kernel<true>, grid, dim3(HIST_THREADS), lds, (hipStream_t)stream, a, hc, edges, bins, hist);
+    else hipLaunchKernelGGL(chunk_hist_kernel<false>, grid, dim3(HIST_THREADS), lds, (hipStream_t)stream, a, hc, edges, bins, hist);
+    return kai0_check_launch(who);
+}
+
 }  // namespace
 
 KAI0_API int64_t kai0_chunk_stats_workspace_bytes(int M, int width) {
@@ -209,50 +292,46 @@ KAI0_API int kai0_chunk_stats_moments(const float* state, int64_t ld_state, int 
                                       const int32_t* ep_end, int N, const int32_t* frame_idx, int M, int horizon, int width,
                                       int clip_state, int clip_action, int mask_state, uint32_t delta_mask, double* out, void* workspace,
                                       int64_t workspace_bytes, kai0_stream_t stream) {
-    if (check_chunk_args("kai0_chunk_stats_moments", state, ld_state, ds, action, ld_action, da, ep_end, N, frame_idx, M, horizon, width,
-                         delta_mask))
-        return -1;
-    KAI0_REQUIRE(out && ((uintptr_t)out & 7) == 0, "kai0_chunk_stats_moments: out must be an 8-byte aligned buffer of 4 * width doubles");
-    const int blocks = M ? blocks_for(M, MOM_FRAMES, MOM_MIN_TRIPS, MOM_MAX_BLOCKS) : 0;
-    KAI0_REQUIRE(M == 0 || (workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= kai0_chunk_stats_workspace_bytes(M, width)),
-                 "kai0_chunk_stats_moments: needs an 8-byte aligned workspace of %lld bytes (got %lld)",
-                 (long long)kai0_chunk_stats_workspace_bytes(M, width), (long long)workspace_bytes);
-    hipStream_t s = (hipStream_t)stream;
-    const ChunkArgs a{state, action, ep_end, frame_idx, ld_state, ld_action, ds, da, N, M, horizon, width, clip_state, clip_action, mask_state,
-                      delta_mask};
-    if (blocks) hipLaunchKernelGGL(chunk_moments_kernel, dim3(blocks), dim3(MOM_THREADS), 0, s, a, (double*)workspace);
-    hipLaunchKernelGGL(chunk_moments_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)workspace, blocks, width, out);
-    return kai0_check_launch("kai0_chunk_stats_moments");
+    const char* who = "kai0_chunk_stats_moments";
+    if (check_chunk_args(who, state, ld_state, ds, action, ld_action, da, ep_end, N, frame_idx, M, horizon, width, delta_mask)) return -1;
+    const ChunkArgs a{state, action, ep_end, frame_idx, nullptr, nullptr, 0, 0, ld_state, ld_action, ds, da, N, M, horizon, width,
+                      clip_state, clip_action, mask_state, delta_mask};
+    return launch_moments(who, a, false, out, workspace, workspace_bytes, stream);
 }
 
 KAI0_API int kai0_chunk_stats_hist(const float* state, int64_t ld_state, int ds, const float* action, int64_t ld_action, int da,
                                    const int32_t* ep_end, int N, const int32_t* frame_idx, int M, int horizon, int width, int clip_state,
                                    int clip_action, int mask_state, uint32_t delta_mask, const double* edges, int bins, uint32_t col_mask,
                                    unsigned long long* hist, kai0_stream_t stream) {
-    if (check_chunk_args("kai0_chunk_stats_hist", state, ld_state, ds, action, ld_action, da, ep_end, N, frame_idx, M, horizon, width,
-                         delta_mask))
-        return -1;
-    KAI0_REQUIRE(bins >= 1 && (int64_t)bins * 4 <= HIST_LDS_BYTES, "kai0_chunk_stats_hist: bins=%d outside 1..%d", bins, HIST_LDS_BYTES / 4);
-    KAI0_REQUIRE(width == 32 || (col_mask >> width) == 0, "kai0_chunk_stats_hist: col_mask 0x%x selects a column >= width=%d", col_mask,
-                 width);
-    if (M == 0 || col_mask == 0) return 0;
-    KAI0_REQUIRE(edges && hist && (((uintptr_t)edges | (uintptr_t)hist) & 7) == 0, "kai0_chunk_stats_hist: edges / hist must be 8-byte aligned");
-    HistCols hc{};
-    for (int c = 0; c < width; ++c)
-        if ((col_mask >> c) & 1u) hc.col[hc.total++] = c;
-    const int fit = HIST_LDS_BYTES / (bins * 4);  // columns whose u32 counters fit the 160 KiB of a CU
-    const int per_block = fit < HIST_COLS ? fit : HIST_COLS;
-    const int groups = (hc.total + per_block - 1) / per_block;
-    hc.n = (hc.total + groups - 1) / groups;  // even groups: 14 columns -> 7 + 7, not 8 + 6
-    const int blocks = blocks_for(M, HIST_FRAMES, HIST_MIN_TRIPS, HIST_MAX_BLOCKS);
-    // a block's u32 counters hold its whole slab
-    KAI0_REQUIRE(((int64_t)M + blocks - 1) / blocks * horizon + (int64_t)HIST_FRAMES * horizon <= 0xffffffffLL,
-                 "kai0_chunk_stats_hist: M=%d x horizon=%d overflows a block's 32-bit counters", M, horizon);
-    const int lds = hc.n * bins * 4;
-    const hipError_t e = kai0_reserve_lds((const void*)chunk_hist_kernel, HIST_LDS_BYTES);
-    KAI0_REQUIRE(e == hipSuccess, "kai0_chunk_stats_hist: cannot reserve %d B of LDS: %s", HIST_LDS_BYTES, hipGetErrorString(e));
-    const ChunkArgs a{state, action, ep_end, frame_idx, ld_state, ld_action, ds, da, N, M, horizon, width, clip_state, clip_action, mask_state,
-                      delta_mask};
-    hipLaunchKernelGGL(chunk_hist_kernel, dim3(blocks, groups), dim3(HIST_THREADS), lds, (hipStream_t)stream, a, hc, edges, bins, hist);
-    return kai0_check_launch("kai0_chunk_stats_hist");
+    const char* who = "kai0_chunk_stats_hist";
+    if (check_chunk_args(who, state, ld_state, ds, action, ld_action, da, ep_end, N, frame_idx, M, horizon, width, delta_mask)) return -1;
+    const ChunkArgs a{state, action, ep_end, frame_idx, nullptr, nullptr, 0, 0, ld_state, ld_action, ds, da, N, M, horizon, width,
+                      clip_state, clip_action, mask_state, delta_mask};
+    return launch_hist(who, a, false, edges, bins, col_mask, hist, stream);
+}
+
+KAI0_API int kai0_chunk_stats_moments_view(const float* state, int64_t ld_state, int ds, const float* action, int64_t ld_action, int da,
+                                           const int32_t* ep_end, int N, const int32_t* frame_idx, const int32_t* frame_stride,
+                                           const uint8_t* frame_mirror, int left_dim, int right_dim, int M, int horizon, int width,
+                                           int clip_state, int clip_action, int mask_state, uint32_t delta_mask, double* out,
+                                           void* workspace, int64_t workspace_bytes, kai0_stream_t stream) {
+    const char* who = "kai0_chunk_stats_moments_view";
+    if (check_chunk_args(who, state, ld_state, ds, action, ld_action, da, ep_end, N, frame_idx, M, horizon, width, delta_mask)) return -1;
+    if (check_view_args(who, frame_stride, left_dim, right_dim, width)) return -1;
+    const ChunkArgs a{state, action, ep_end, frame_idx, frame_stride, frame_mirror, left_dim, right_dim, ld_state, ld_action, ds, da, N, M,
+                      horizon, width, clip_state, clip_action, mask_state, delta_mask};
+    return launch_moments(who, a, frame_stride || frame_mirror, out, workspace, workspace_bytes, stream);
+}
+
+KAI0_API int kai0_chunk_stats_hist_view(const float* state, int64_t ld_state, int ds, const float* action, int64_t ld_action, int da,
+                                        const int32_t* ep_end, int N, const int32_t* frame_idx, const int32_t* frame_stride,
+                                        const uint8_t* frame_mirror, int left_dim, int right_dim, int M, int horizon, int width,
+                                        int clip_state, int clip_action, int mask_state, uint32_t delta_mask, const double* edges, int bins,
+                                        uint32_t col_mask, unsigned long long* hist, kai0_stream_t stream) {
+    const char* who = "kai0_chunk_stats_hist_view";
+    if (check_chunk_args(who, state, ld_state, ds, action, ld_action, da, ep_end, N, frame_idx, M, horizon, width, delta_mask)) return -1;
+    if (check_view_args(who, frame_stride, left_dim, right_dim, width)) return -1;
+    const ChunkArgs a{state, action, ep_end, frame_idx, frame_stride, frame_mirror, left_dim, right_dim, ld_state, ld_action, ds, da, N, M,
+                      horizon, width, clip_state, clip_action, mask_state, delta_mask};
+    return launch_hist(who, a, frame_stride || frame_mirror, edges, bins, col_mask, hist, stream);
 }

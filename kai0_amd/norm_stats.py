@@ -101,20 +101,35 @@ def _pad(x: np.ndarray, dim: int) -> np.ndarray:
 
 
 def chunk_rows(state, action, ep_end, *, horizon: int, action_dim: int, clip_state: bool, clip_action: bool, mask_state: bool,
-               delta_mask: int, frame_idx=None) -> tuple[np.ndarray, np.ndarray]:  # fmt: skip
+               delta_mask: int, frame_idx=None, frame_stride=None, frame_mirror=None, left_dim: int = 7,
+               right_dim: int = 7) -> tuple[np.ndarray, np.ndarray]:  # fmt: skip
     """What the transformed dataset yields under "state" and "actions" for the frames `frame_idx` (default: all), from the tables:
     f32 [M, action_dim] and f32 [M, horizon, action_dim].  state [N, ds] / action [N, da] f32, ep_end[i] = one past the last row of
-    frame i's episode: chunk row h of frame i is action row min(i + h, ep_end[i] - 1)."""
+    frame i's episode: chunk row h of frame i is action row min(i + h, ep_end[i] - 1).
+    A dataset view (`lerobot_dataset.ViewPlan`) adds, per frame, `frame_stride` s (time scaling: chunk row h is row
+    min(i + h s, last kept row of the episode), the kept rows being i, i + s, ...) and `frame_mirror` (space mirroring: the first
+    left_dim + right_dim columns of the padded state and action rows become [right, left] BEFORE the glitch filter, the state
+    mask and the delta subtraction — where a mirrored parquet would have them).  With both None this is the plain function."""
     state, action = np.asarray(state, np.float32), np.asarray(action, np.float32)
     ep_end = np.asarray(ep_end, np.int64)
     idx = np.arange(len(state)) if frame_idx is None else np.asarray(frame_idx, np.int64)
-    rows = np.minimum(idx[:, None] + np.arange(horizon)[None, :], ep_end[idx][:, None] - 1)
+    if frame_stride is None:
+        rows = np.minimum(idx[:, None] + np.arange(horizon)[None, :], ep_end[idx][:, None] - 1)
+    else:
+        step = np.maximum(np.asarray(frame_stride, np.int64), 1)
+        last = idx + (ep_end[idx] - 1 - idx) // step * step
+        rows = np.minimum(idx[:, None] + np.arange(horizon)[None, :] * step[:, None], last[:, None])
     s = _pad(state[idx], action_dim)
+    a = _pad(action[rows], action_dim)
+    if frame_mirror is not None:
+        perm = _normalize.arm_swap_perm(action_dim, left_dim, right_dim)
+        flip = np.asarray(frame_mirror).astype(bool)
+        s = np.where(flip[:, None], s[:, perm], s)
+        a = np.where(flip[:, None, None], a[:, :, perm], a)
     if clip_state:
         s = _clip(s)
     if mask_state:
         s = np.zeros_like(s)
-    a = _pad(action[rows], action_dim)
     if clip_action:
         a = _clip(a)
     if delta_mask:
@@ -174,31 +189,40 @@ def one_shot(rows: np.ndarray) -> NormStats:
 
 
 # ------------------------------------------------------------------------------------------------ host path (lowered)
-def _key_rows(key: str, state, action, ep_end, spec: ChunkSpec, horizon: int, frame_idx) -> np.ndarray:
+def _key_rows(key: str, state, action, ep_end, spec: ChunkSpec, horizon: int, frame_idx, view: dict | None = None) -> np.ndarray:
     s, a = chunk_rows(state, action, ep_end, horizon=horizon if key == "actions" else 1, action_dim=spec.action_dim,
                       clip_state=spec.clip_state, clip_action=spec.clip_action, mask_state=spec.mask_state,
-                      delta_mask=spec.delta_mask, frame_idx=frame_idx)  # fmt: skip
+                      delta_mask=spec.delta_mask, frame_idx=frame_idx, **(view or {}))  # fmt: skip
     return (s if key == "state" else a.reshape(-1, spec.action_dim)).astype(np.float64)
 
 
-def host_stats(state, action, ep_end, spec: ChunkSpec, horizon: int, frame_idx=None, *, slab_rows: int = HOST_SLAB_ROWS) -> dict[str, NormStats]:
+def _view_slice(view: dict, sl: slice) -> dict:
+    return {k: (v[sl] if k in ("frame_stride", "frame_mirror") and v is not None else v) for k, v in view.items()}
+
+
+def host_stats(state, action, ep_end, spec: ChunkSpec, horizon: int, frame_idx=None, *, slab_rows: int = HOST_SLAB_ROWS,
+               frame_stride=None, frame_mirror=None, left_dim: int = 7, right_dim: int = 7) -> dict[str, NormStats]:  # fmt: skip
     """`chunk_rows` + the one-shot estimator.  A selection that fits one slab goes through RunningStats itself; a larger one takes
     two passes over frame slabs (range and sums, then np.histogram over the fixed edges): the same counts as integers, sums added
-    slab by slab."""
+    slab by slab.  `frame_stride` / `frame_mirror` (one entry per selected frame) are chunk_rows' view arguments."""
     idx = np.arange(len(state)) if frame_idx is None else np.asarray(frame_idx, np.int64)
+    view = {}
+    if frame_stride is not None or frame_mirror is not None:
+        view = dict(frame_stride=None if frame_stride is None else np.asarray(frame_stride),
+                    frame_mirror=None if frame_mirror is None else np.asarray(frame_mirror), left_dim=left_dim, right_dim=right_dim)  # fmt: skip
     out = {}
     for key in KEYS:
         per = max(1, slab_rows // (horizon if key == "actions" else 1))
         if len(idx) <= per:
-            x = _key_rows(key, state, action, ep_end, spec, horizon, idx)
+            x = _key_rows(key, state, action, ep_end, spec, horizon, idx, view)
             check_finite(key, ColumnSums(len(x), x.min(0), x.max(0), None, None))  # np.min / np.max propagate a NaN
             out[key] = one_shot(x)
             continue
-        slabs = [idx[i : i + per] for i in range(0, len(idx), per)]
+        slabs = [slice(i, i + per) for i in range(0, len(idx), per)]
         d = spec.action_dim
         sums = ColumnSums(0, np.full(d, np.inf), np.full(d, -np.inf), np.zeros(d), np.zeros(d))
         for sl in slabs:
-            x = _key_rows(key, state, action, ep_end, spec, horizon, sl)
+            x = _key_rows(key, state, action, ep_end, spec, horizon, idx[sl], _view_slice(view, sl))
             sums.count += len(x)
             sums.lo, sums.hi = np.minimum(sums.lo, x.min(0)), np.maximum(sums.hi, x.max(0))  # (a NaN sticks in both)
             sums.sum += x.sum(0)
@@ -207,7 +231,7 @@ def host_stats(state, action, ep_end, spec: ChunkSpec, horizon: int, frame_idx=N
         edges = [column_edges(sums.lo[c], sums.hi[c]) for c in range(d)]
         hist = np.zeros((d, QUANTILE_BINS), np.int64)
         for sl in slabs:
-            x = _key_rows(key, state, action, ep_end, spec, horizon, sl)
+            x = _key_rows(key, state, action, ep_end, spec, horizon, idx[sl], _view_slice(view, sl))
             for c in range(d):
                 hist[c] += np.histogram(x[:, c], bins=edges[c])[0]
         out[key] = finish(sums, hist, edges)
@@ -215,10 +239,19 @@ def host_stats(state, action, ep_end, spec: ChunkSpec, horizon: int, frame_idx=N
 
 
 # ------------------------------------------------------------------------------------------------ device path (lowered)
+def _view_args(view) -> tuple | None:
+    """(frame_stride pointer, frame_mirror pointer, left_dim, right_dim) of a device view, None for a plain launch.
+    `view` = (int32 [M] tensor or None, uint8 [M] tensor or None, left_dim, right_dim)."""
+    if view is None:
+        return None
+    stride, mirror, left_dim, right_dim = view
+    return (None if stride is None else stride.data_ptr(), None if mirror is None else mirror.data_ptr(), int(left_dim), int(right_dim))
+
+
 def device_sums(state, action, ep_end, frame_idx, *, horizon: int, width: int, clip_state: bool, clip_action: bool, mask_state: bool,
-                delta_mask: int) -> ColumnSums:  # fmt: skip
+                delta_mask: int, view=None) -> ColumnSums:  # fmt: skip
     """kai0_chunk_stats_moments on resident tables (torch tensors on the GPU: f32 [N, ds], f32 [N, da], int32 [N], int32 [M] or None).
-    One device-to-host copy of 4 x width doubles."""
+    One device-to-host copy of 4 x width doubles.  `view` (see _view_args): kai0_chunk_stats_moments_view instead."""
     import torch
 
     from . import _lib
@@ -227,8 +260,10 @@ def device_sums(state, action, ep_end, frame_idx, *, horizon: int, width: int, c
     out = torch.empty(4, width, dtype=torch.float64, device=state.device)
     nbytes = _lib.load().kai0_chunk_stats_workspace_bytes(m, width)
     ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=state.device)
-    _lib.call("kai0_chunk_stats_moments", state.data_ptr(), state.stride(0), min(state.shape[1], width), action.data_ptr(), action.stride(0),
-              action.shape[1], ep_end.data_ptr(), n, None if frame_idx is None else frame_idx.data_ptr(), m, horizon, width,
+    va = _view_args(view)
+    _lib.call("kai0_chunk_stats_moments" if va is None else "kai0_chunk_stats_moments_view", state.data_ptr(), state.stride(0),
+              min(state.shape[1], width), action.data_ptr(), action.stride(0), action.shape[1], ep_end.data_ptr(), n,
+              None if frame_idx is None else frame_idx.data_ptr(), *(va or ()), m, horizon, width,
               int(clip_state), int(clip_action), int(mask_state), delta_mask, out.data_ptr(), ws.data_ptr(), ws.numel() * 8,
               torch.cuda.current_stream().cuda_stream)  # fmt: skip
     o = out.cpu().numpy()
@@ -236,8 +271,9 @@ def device_sums(state, action, ep_end, frame_idx, *, horizon: int, width: int, c
 
 
 def device_hist(state, action, ep_end, frame_idx, edges: np.ndarray, col_mask: int, *, horizon: int, width: int, clip_state: bool,
-                clip_action: bool, mask_state: bool, delta_mask: int) -> np.ndarray:  # fmt: skip
-    """kai0_chunk_stats_hist: int64 [width, bins] counts of the columns in col_mask over edges f64 [width, bins + 1] (host array)."""
+                clip_action: bool, mask_state: bool, delta_mask: int, view=None) -> np.ndarray:  # fmt: skip
+    """kai0_chunk_stats_hist: int64 [width, bins] counts of the columns in col_mask over edges f64 [width, bins + 1] (host array).
+    `view` (see _view_args): kai0_chunk_stats_hist_view instead."""
     import torch
 
     from . import _lib
@@ -246,8 +282,10 @@ def device_hist(state, action, ep_end, frame_idx, edges: np.ndarray, col_mask: i
     n, m = state.shape[0], (state.shape[0] if frame_idx is None else frame_idx.numel())
     dev_edges = torch.from_numpy(np.ascontiguousarray(edges, np.float64)).to(state.device)
     hist = torch.zeros(width, bins, dtype=torch.int64, device=state.device)
-    _lib.call("kai0_chunk_stats_hist", state.data_ptr(), state.stride(0), min(state.shape[1], width), action.data_ptr(), action.stride(0),
-              action.shape[1], ep_end.data_ptr(), n, None if frame_idx is None else frame_idx.data_ptr(), m, horizon, width,
+    va = _view_args(view)
+    _lib.call("kai0_chunk_stats_hist" if va is None else "kai0_chunk_stats_hist_view", state.data_ptr(), state.stride(0),
+              min(state.shape[1], width), action.data_ptr(), action.stride(0), action.shape[1], ep_end.data_ptr(), n,
+              None if frame_idx is None else frame_idx.data_ptr(), *(va or ()), m, horizon, width,
               int(clip_state), int(clip_action), int(mask_state), delta_mask, dev_edges.data_ptr(), bins, col_mask, hist.data_ptr(),
               torch.cuda.current_stream().cuda_stream)  # fmt: skip
     return hist.cpu().numpy()
@@ -260,6 +298,8 @@ def device_key_stats(key: str, state, action, ep_end, frame_idx, *, bins: int = 
     width = kw["width"]
     # columns past both tables are 0 - 0 whatever the data: the launches take the leading columns that can hold anything else
     live = max(1, min(width, max(action.shape[1], min(state.shape[1], kw["delta_mask"].bit_length()))))
+    if kw.get("view") is not None and kw["view"][1] is not None:  # a mirrored frame may move a table column up to left + right - 1
+        live = max(live, min(width, kw["view"][2] + kw["view"][3]))
     kw = {**kw, "width": live, "delta_mask": kw["delta_mask"] & ((1 << live) - 1)}
     sums = device_sums(state, action, ep_end, frame_idx, **kw)
     check_finite(key, sums)
@@ -284,16 +324,20 @@ class KeyResult:
     stats: NormStats | None  # None for a single row (the estimator refuses it)
 
 
-def device_stats(state, action, ep_end, spec: ChunkSpec, horizon: int, frame_idx=None, *, device="cuda") -> dict[str, NormStats]:
-    res = device_results(state, action, ep_end, spec, horizon, frame_idx, device=device)
+def device_stats(state, action, ep_end, spec: ChunkSpec, horizon: int, frame_idx=None, *, device="cuda", **view) -> dict[str, NormStats]:
+    res = device_results(state, action, ep_end, spec, horizon, frame_idx, device=device, **view)
     if any(r.stats is None for r in res.values()):
         raise ValueError("Cannot compute statistics for less than 2 vectors.")
     return {key: r.stats for key, r in res.items()}
 
 
-def device_results(state, action, ep_end, spec: ChunkSpec, horizon: int, frame_idx=None, *, device="cuda") -> dict[str, KeyResult]:
+def device_results(state, action, ep_end, spec: ChunkSpec, horizon: int, frame_idx=None, *, device="cuda", frame_stride=None,
+                   frame_mirror=None, left_dim: int = 7, right_dim: int = 7) -> dict[str, KeyResult]:  # fmt: skip
     """The two tables go to the GPU once; two passes per key.  "state" is the horizon = 1, no-delta case of the same kernels with
-    the state table in the action slot (a masked state is all zeros: its statistics need no launch)."""
+    the state table in the action slot (a masked state is all zeros: its statistics need no launch).  With `frame_stride` and / or
+    `frame_mirror` (host arrays, one entry per frame: a `lerobot_dataset.ViewPlan`) the `_view` entry points run instead; a
+    stride whose product with the horizon does not fit int32, or arms that do not fit action_dim, are refused here, before any
+    upload or launch."""
     import torch
 
     state, action = np.ascontiguousarray(state, np.float32), np.ascontiguousarray(action, np.float32)
@@ -307,11 +351,27 @@ def device_results(state, action, ep_end, spec: ChunkSpec, horizon: int, frame_i
         frame_idx = np.asarray(frame_idx, np.int64)
         if frame_idx.size and (frame_idx.min() < 0 or frame_idx.max() >= n):
             raise ValueError("norm stats: frame_idx outside the table")
+    m = n if frame_idx is None else len(frame_idx)
+    has_view = frame_stride is not None or frame_mirror is not None
+    if has_view:
+        if left_dim < 0 or right_dim < 0 or left_dim + right_dim > spec.action_dim:
+            raise ValueError(f"norm stats: left_dim = {left_dim} + right_dim = {right_dim} do not fit action_dim = {spec.action_dim}")
+        for name, v in (("frame_stride", frame_stride), ("frame_mirror", frame_mirror)):
+            if v is not None and np.shape(v) != (m,):
+                raise ValueError(f"norm stats: {name} must hold one entry per frame ({m}), got shape {np.shape(v)}")
+        if frame_stride is not None:
+            frame_stride = np.asarray(frame_stride, np.int64)
+            if frame_stride.size and (frame_stride.min() < 1 or int(frame_stride.max()) * horizon >= 2**31):
+                raise ValueError(f"norm stats: frame_stride must lie in [1, 2^31 / horizon), got {frame_stride.min()}..{frame_stride.max()}")
     dev = torch.device(device)
     t_state, t_action = torch.from_numpy(state).to(dev), torch.from_numpy(action).to(dev)
     t_end = torch.from_numpy(ep_end.astype(np.int32)).to(dev)
     t_idx = None if frame_idx is None else torch.from_numpy(frame_idx.astype(np.int32)).to(dev)
-    m = n if frame_idx is None else len(frame_idx)
+    view = None
+    if has_view:
+        view = (None if frame_stride is None else torch.from_numpy(frame_stride.astype(np.int32)).to(dev),
+                None if frame_mirror is None else torch.from_numpy(np.ascontiguousarray(np.asarray(frame_mirror) != 0, np.uint8)).to(dev),
+                left_dim, right_dim)  # fmt: skip
     d = spec.action_dim
     out = {}
     with torch.cuda.device(dev):
@@ -322,10 +382,10 @@ def device_results(state, action, ep_end, spec: ChunkSpec, horizon: int, frame_i
             out["state"] = KeyResult(zeros, hist, edges, finish(zeros, hist, list(edges)) if m >= 2 else None)
         else:
             out["state"] = device_key_stats("state", t_state, t_state, t_end, t_idx, horizon=1, width=d, clip_state=False,
-                                            clip_action=spec.clip_state, mask_state=False, delta_mask=0)  # fmt: skip
+                                            clip_action=spec.clip_state, mask_state=False, delta_mask=0, view=view)  # fmt: skip
         out["actions"] = device_key_stats("actions", t_state, t_action, t_end, t_idx, horizon=horizon, width=d,
                                           clip_state=spec.clip_state, clip_action=spec.clip_action, mask_state=spec.mask_state,
-                                          delta_mask=spec.delta_mask)  # fmt: skip
+                                          delta_mask=spec.delta_mask, view=view)  # fmt: skip
     return out
 
 
@@ -352,6 +412,22 @@ def _sample(n: int, max_frames: int | None, seed: int):
     if max_frames is None or max_frames >= n:
         return None
     return np.sort(np.random.default_rng(seed).choice(n, size=max_frames, replace=False))
+
+
+def _config_plan(data_config, meta, episodes, state, action, ep_end):
+    """The ViewPlan `create_torch_dataset` gives this data config, from the episode boundaries of the tables alone."""
+    from . import lerobot_dataset as lrd
+
+    eps = list(episodes) if episodes is not None else sorted(meta.episodes)
+    ends, lengths = np.unique(ep_end, return_counts=True)
+    if len(lengths) != len(eps):
+        raise ValueError(f"{meta.root}: {len(eps) - len(lengths)} of the selected episodes hold no frame")
+    if data_config.space_mirror:
+        total = data_config.left_dim + data_config.right_dim
+        if state.shape[1] != total or action.shape[1] != total:  # swap_arms_in_array's error, before anything is computed
+            raise ValueError(f"Array dimension mismatch: expected {total} dims (left{data_config.left_dim} + right{data_config.right_dim}), "
+                             f"got {state.shape[1]} / {action.shape[1]} dims")  # fmt: skip
+    return lrd.plan_view(lengths, eps, data_config.time_scaling, data_config.space_mirror)
 
 
 def compute_norm_stats(config, *, max_frames: int | None = None, seed: int = 0, device=None) -> dict[str, NormStats]:
@@ -384,17 +460,28 @@ def compute_norm_stats(config, *, max_frames: int | None = None, seed: int = 0, 
         data_config = dataclasses.replace(data_config, episodes=episodes)
     if spec is None:
         logger.info("norm stats of %s on the host, through the transformed dataset: %s", data_config.repo_id, why)
-        n = sum(meta.episodes[e]["length"] for e in (episodes if episodes is not None else sorted(meta.episodes)))
+        eps = list(episodes) if episodes is not None else sorted(meta.episodes)
+        n = len(lrd.plan_view([meta.episodes[e]["length"] for e in eps], eps, data_config.time_scaling, data_config.space_mirror))
         return loader_stats(config, data_config, _sample(n, max_frames, seed))
     state, action, ep_end = lrd.read_state_action_columns(data_config.repo_id, spec.state_col, spec.action_col, episodes=episodes)
-    frame_idx = _sample(len(state), max_frames, seed)
+    view = {}
+    if data_config.space_mirror or data_config.time_scaling is not None:
+        # the statistics of the AUGMENTED dataset: every sample the loader will yield, as (row, stride, mirrored)
+        plan = _config_plan(data_config, meta, episodes, state, action, ep_end)
+        pick = _sample(len(plan), max_frames, seed)
+        pick = slice(None) if pick is None else pick
+        frame_idx = plan.frame_idx[pick]
+        view = dict(frame_stride=plan.frame_stride[pick], frame_mirror=plan.frame_mirror[pick], left_dim=data_config.left_dim,
+                    right_dim=data_config.right_dim)  # fmt: skip
+    else:
+        frame_idx = _sample(len(state), max_frames, seed)
     horizon = config.model.action_horizon
     use_gpu = torch.cuda.is_available() if device is None else torch.device(device).type == "cuda"
     if not use_gpu:
         logger.info("norm stats of %s on the host (%s): chunk_rows + the one-shot estimator", data_config.repo_id,
                     "device='cpu' was asked for" if device is not None else "no GPU is present")  # fmt: skip
-        return host_stats(state, action, ep_end, spec, horizon, frame_idx)
-    return device_stats(state, action, ep_end, spec, horizon, frame_idx, device=device or "cuda")
+        return host_stats(state, action, ep_end, spec, horizon, frame_idx, **view)
+    return device_stats(state, action, ep_end, spec, horizon, frame_idx, device=device or "cuda", **view)
 
 
 def output_dir(config) -> pathlib.Path:

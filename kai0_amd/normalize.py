@@ -112,6 +112,42 @@ def load(directory) -> dict[str, NormStats]:
     return deserialize_json(path.read_text())
 
 
+# ------------------------------------------------------------------------------------------------ space mirroring
+def arm_swap_perm(width: int, left_dim: int = 7, right_dim: int = 7) -> np.ndarray:
+    """Source column of every output column when a dual-arm vector `[left | right | rest]` becomes `[right | left | rest]`
+    (train_deploy_alignment/data_augment/space_mirroring.py:39-87: a pure swap, no sign change; the rest is padding and stays)."""
+    total = left_dim + right_dim
+    if left_dim < 0 or right_dim < 0 or total > width:
+        raise ValueError(f"Insufficient array dimensions: expected at least {total} dims (left{left_dim} + right{right_dim}), got {width} dims")
+    return np.concatenate([np.arange(left_dim, total), np.arange(left_dim), np.arange(total, width)]).astype(np.int64)
+
+
+def swap_arms(x, left_dim: int = 7, right_dim: int = 7):
+    """A state / action row (or a window of rows: the last axis) of exactly left_dim + right_dim values with its arms swapped
+    (space_mirroring.py:39-63, applied per parquet cell); any other length is a ValueError, as there.  numpy array or torch tensor."""
+    if x.shape[-1] != left_dim + right_dim:
+        raise ValueError(f"Array dimension mismatch: expected {left_dim + right_dim} dims (left{left_dim} + right{right_dim}), "
+                         f"got {x.shape[-1]} dims")  # fmt: skip
+    return x[..., arm_swap_perm(x.shape[-1], left_dim, right_dim)]
+
+
+def mirror_norm_stats(stats: dict[str, NormStats], left_dim: int = 7, right_dim: int = 7) -> dict[str, NormStats]:
+    """The statistics of the mirrored dataset from those of the original (space_mirroring.py:214-255): the first left_dim +
+    right_dim entries of mean / std / q01 / q99 of "state" and "actions" swapped, the padding after them kept, other keys untouched.
+    Its own inverse for left_dim == right_dim."""
+    out = {}
+    for key, s in stats.items():
+        if key not in ("state", "actions"):
+            out[key] = s
+            continue
+        fields = {}
+        for f in ("mean", "std", "q01", "q99"):
+            v = getattr(s, f)
+            fields[f] = None if v is None else np.asarray(v)[..., arm_swap_perm(np.shape(v)[-1], left_dim, right_dim)]
+        out[key] = NormStats(**fields)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ the two maps
 def _pad_last(v: np.ndarray, n: int, value: float) -> np.ndarray:
     if v.shape[-1] >= n:

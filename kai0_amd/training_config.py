@@ -24,6 +24,7 @@ from . import agilex_policy
 from . import normalize as _normalize
 from . import transforms as _transforms
 from .config import AdvantageEstimatorConfig, Pi0Config
+from .lerobot_dataset import TimeScaling
 from .optim import lr_schedule as _lr_schedule
 
 
@@ -91,6 +92,12 @@ class DataConfig:
     action_sequence_keys: Sequence[str] = ("actions",)
     prompt_from_task: bool = False
     episodes: list[int] | None = None
+    # train-deploy alignment as dataset views (lerobot_dataset.py): time scaling first, mirroring over the result
+    space_mirror: bool = False
+    time_scaling: TimeScaling | None = None
+    left_dim: int = 7
+    right_dim: int = 7
+    mirror_flip_only: Sequence[str] = ()  # cameras that are none of top_head / hand_left / hand_right: flipped in place
 
 
 @dataclasses.dataclass(frozen=True)
@@ -177,6 +184,12 @@ class LerobotAgilexDataConfig(DataConfigFactory):
     mask_state: bool = False
     insert_advantage_into_prompt: bool = False
     tokenizer_model: Any = None  # see ModelTransformFactory
+    # kai0's data_augment tools as views over the dataset: original ∪ mirrored, every Nth frame of (some) episodes
+    space_mirror: bool = False
+    time_scaling: TimeScaling | None = None
+    left_dim: int = 7
+    right_dim: int = 7
+    mirror_flip_only: Sequence[str] = ()
 
     _inputs_cls = agilex_policy.AgilexInputs
     _outputs_cls = agilex_policy.AgilexOutputs
@@ -199,7 +212,9 @@ class LerobotAgilexDataConfig(DataConfigFactory):
         model = ModelTransformFactory(default_prompt=self.default_prompt, tokenizer_model=self.tokenizer_model)(model_config)
         return dataclasses.replace(self.create_base_config(assets_dirs, model_config), repack_transforms=repack,
                                    data_transforms=data, model_transforms=model,
-                                   action_sequence_keys=self.action_sequence_keys, episodes=self.episodes)  # fmt: skip
+                                   action_sequence_keys=self.action_sequence_keys, episodes=self.episodes,
+                                   space_mirror=self.space_mirror, time_scaling=self.time_scaling, left_dim=self.left_dim,
+                                   right_dim=self.right_dim, mirror_flip_only=self.mirror_flip_only)  # fmt: skip
 
 
 @dataclasses.dataclass(frozen=True)
@@ -356,7 +371,9 @@ def get_config(config_name: str) -> TrainConfig:
 
 def cli(argv: Sequence[str] | None = None) -> TrainConfig:
     """`<config-name> [--field value ...]` -> TrainConfig (config.py:1398-1399; tyro's overridable_config_cli reduced to the
-    scalar top-level fields, which is what the training scripts pass: --exp_name, --batch_size, --overwrite, --resume, ...)."""
+    scalar top-level fields, which is what the training scripts pass: --exp_name, --batch_size, --overwrite, --resume, ...).
+    The dataset views of a LeRobot data config are set the same way, under tyro's dotted names: --data.space_mirror,
+    --data.time_scaling.factor N [--data.time_scaling.split_ratio R], --data.left_dim, --data.right_dim."""
     ap = argparse.ArgumentParser(description="kai0_amd training configuration")
     sub = ap.add_subparsers(dest="_name", required=True)
     scalar = {}
@@ -371,6 +388,19 @@ def cli(argv: Sequence[str] | None = None) -> TrainConfig:
             else:
                 conv = {"int": int, "float": float}.get(ftype.split(" ")[0], str)
                 sp.add_argument(f"--{fname}", f"--{fname.replace('_', '-')}", dest=fname, type=conv, default=None)
+        if isinstance(_CONFIGS_DICT[name].data, LerobotAgilexDataConfig):
+            sp.add_argument("--data.space_mirror", "--data.space-mirror", dest="data.space_mirror", action=argparse.BooleanOptionalAction, default=None)
+            sp.add_argument("--data.time_scaling.factor", "--data.time-scaling.factor", dest="data.time_scaling.factor", type=int, default=None)
+            sp.add_argument("--data.time_scaling.split_ratio", "--data.time-scaling.split-ratio", dest="data.time_scaling.split_ratio", type=float, default=None)
+            sp.add_argument("--data.left_dim", "--data.left-dim", dest="data.left_dim", type=int, default=None)
+            sp.add_argument("--data.right_dim", "--data.right-dim", dest="data.right_dim", type=int, default=None)
     ns = vars(ap.parse_args(argv))
     base = _CONFIGS_DICT[ns.pop("_name")]
+    data = {k[len("data.") :]: ns.pop(k) for k in [k for k in ns if k.startswith("data.")]}
+    scaling = {k[len("time_scaling.") :]: data.pop(k) for k in [k for k in data if k.startswith("time_scaling.")]}
+    data = {k: v for k, v in data.items() if v is not None}
+    if any(v is not None for v in scaling.values()):
+        data["time_scaling"] = dataclasses.replace(base.data.time_scaling or TimeScaling(), **{k: v for k, v in scaling.items() if v is not None})
+    if data:
+        ns["data"] = dataclasses.replace(base.data, **data)
     return dataclasses.replace(base, **{k: v for k, v in ns.items() if v is not None})

@@ -8,7 +8,11 @@ action_horizon 50, action_dim 32, delta mask (6, -1, 6, -1)), in one process:
 on three tables: a joint-like random walk, the same with two gripper-like two-valued columns, and white noise (no two consecutive
 chunk rows share a bin: the histogram kernel's run merging finds nothing to merge — the spread between the tables is the price of the
 LDS counter traffic).
-usage: python tools/probes/norm_stats_rate.py [--frames N] [--rounds R] [--out profiles/norm_stats.txt]"""
+With --view, per table, also the two "actions" kernels through the _view entry points, on the resident tables:
+  v0  no view               frame_stride = frame_mirror = NULL: the launches of form a, reached through the new entry points
+  v1  stride 2 + mirror     the augmented dataset of space_mirror + TimeScaling(2): every second row of every episode, once as it is
+                            and once mirrored (`lerobot_dataset.plan_view`) — as many frames as the plain table has rows
+usage: python tools/probes/norm_stats_rate.py [--frames N] [--rounds R] [--view] [--out profiles/norm_stats.txt]"""
 import argparse
 import os
 import statistics
@@ -21,6 +25,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+from kai0_amd import lerobot_dataset as lrd  # noqa: E402
 from kai0_amd import norm_stats as ns  # noqa: E402
 from kai0_amd.normalize import RunningStats  # noqa: E402
 
@@ -31,6 +36,7 @@ ap.add_argument("--horizon", type=int, default=50)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--host-frames", type=int, default=20_000)
 ap.add_argument("--streamed-frames", type=int, default=6_400)
+ap.add_argument("--view", action="store_true", help="also time the _view entry points: no view, and stride 2 + mirror on half the frames")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "norm_stats.txt"))
 ap.add_argument("--commit", default=None, help="commit to record (default: git rev-parse HEAD, 'unknown' outside a git checkout)")
 args = ap.parse_args()
@@ -101,6 +107,25 @@ for kind in ("walk", "walk + grippers", "white noise"):
         m = statistics.median(ts)
         label = kind + ": " + name
         lines.append(f"{label:<58}{m:>11.4f}{min(ts):>10.4f}{N / m:>14.3e}")
+    if args.view:
+        plan = lrd.plan_view([args.episode] * n_ep, None, lrd.TimeScaling(2), True)
+        t_plan = tuple(torch.from_numpy(x).to(dev) for x in (plan.frame_idx, plan.frame_stride, plan.frame_mirror))
+        forms = (("v0 no view (NULL, NULL)", None, (None, None, 7, 7)),
+                 (f"v1 stride 2 + mirror on half, {len(plan)} frames", t_plan[0], (t_plan[1], t_plan[2], 7, 7)))  # fmt: skip
+        for label, t_idx, view in forms:
+            m = N if t_idx is None else len(plan)
+            mom, hist = [], []
+            for r in range(args.rounds + 1):
+                t1, sums = timed(lambda: ns.device_sums(t_state, t_action, t_end, t_idx, **kw, view=view))
+                edges = np.stack([ns.column_edges(sums.lo[c], sums.hi[c]) for c in range(32)])
+                mask = sum(1 << c for c in range(32) if sums.lo[c] != sums.hi[c])
+                t2, _ = timed(lambda: ns.device_hist(t_state, t_action, t_end, t_idx, edges, mask, **kw, view=view))
+                if r:
+                    mom.append(t1), hist.append(t2)
+            for name, ts in (("kai0_chunk_stats_moments_view", mom), ("kai0_chunk_stats_hist_view", hist)):
+                med = statistics.median(ts)
+                line = f"{kind}: {label}: {name}"
+                lines.append(f"{line:<96}{med:>11.4f}{min(ts):>10.4f}{m / med:>14.3e}")
     if kind == "walk + grippers":
         idx = np.sort(np.random.default_rng(0).choice(N, size=min(N, args.host_frames), replace=False))
         t0 = time.perf_counter()
