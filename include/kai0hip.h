@@ -719,8 +719,17 @@ int kai0_mix(const void* const* srcs, int src_f32, const float* weights, int n_s
 int kai0_multi_dot(const void* g, int g_f32, const void* const* srcs, int src_f32, int n_src, int64_t n, double* out,
                    float* scratch, kai0_stream_t stream);
 /* coef[0] = min(1, max_norm / (sqrt(sumsq[0]) + 1e-6)) ; norm_out[0] = sqrt(sumsq[0])
- * (torch.nn.utils.clip_grad_norm_) */
+ * (torch.nn.utils.clip_grad_norm_ with error_if_nonfinite=False).  Unguarded: sumsq = +inf gives coef = 0 (and inf * 0 = NaN in the
+ * update), sumsq = NaN gives coef = 1 (the comparison with 1 is false): either way the update is applied.  Always 0 <= coef <= 1. */
 int kai0_clip_coef(const float* sumsq, float max_norm, float* coef, float* norm_out, kai0_stream_t stream);
+/* A negative clip coefficient means: leave everything as it is.  kai0_adamw, _rows, _ema and _rows_ema return before any other load
+ * or store when coef[0] < 0: master, m, v, ema, the model copy and row_active keep their bytes, the gradient is not read. */
+#define KAI0_COEF_SKIP (-1.0f)
+/* kai0_clip_coef that skips the step whose gradient norm is not finite: norm_out[0] = nrm = sqrt(sumsq[0]);
+ *   nrm finite:      coef[0] = the bits kai0_clip_coef writes, or 1.0f when max_norm <= 0 ("no clipping"); skipped untouched
+ *   nrm inf or NaN:  coef[0] = KAI0_COEF_SKIP and skipped[0] += 1   (int32, one thread: stream-ordered, no atomics)
+ * All four pointers non-null. */
+int kai0_clip_coef_guard(const float* sumsq, float max_norm, float* coef, float* norm_out, int32_t* skipped, kai0_stream_t stream);
 
 /* LoRA adapters (src/openpi/models/lora.py:54-65 `Einsum`: result + einsum(einsum(x, lora_a), lora_b) * scaling_value, every einsum in
  * the activation dtype; :144-148 `FeedForward._dot`: the same without the scale).  The two products with an activation-sized operand

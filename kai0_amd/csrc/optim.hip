@@ -49,12 +49,32 @@ __global__ __launch_bounds__(256) void sumsq_finish_kernel(const float* __restri
     if (threadIdx.x == 0) out[0] += acc;
 }
 
+// min(1, max_norm / (nrm + 1e-6)) as both clip kernels form it; a NaN quotient (NaN norm) gives 1, an infinite norm 0
+__device__ __forceinline__ float clip_coef_value(float nrm, float max_norm) {
+    const float c = max_norm / (nrm + 1e-6f);
+    return c < 1.0f ? c : 1.0f;
+}
+
 __global__ void clip_coef_kernel(const float* __restrict__ sumsq, float max_norm, float* __restrict__ coef,
                                  float* __restrict__ norm_out) {
     const float nrm = sqrtf(sumsq[0]);
     if (norm_out) norm_out[0] = nrm;
-    const float c = max_norm / (nrm + 1e-6f);
-    coef[0] = c < 1.0f ? c : 1.0f;
+    coef[0] = clip_coef_value(nrm, max_norm);
+}
+
+// clip_coef_kernel with the non-finite guard: a norm that is inf or NaN (a bf16 gradient overflow, a NaN in the batch, a negative
+// or overflowed sum) writes KAI0_COEF_SKIP, which every AdamW form below reads as "leave everything as it is", and counts the step
+// in skipped[0] (one thread: a plain read-modify-write).  A finite norm gives clip_coef_kernel's bits; max_norm <= 0 = no clipping.
+__global__ void clip_coef_guard_kernel(const float* __restrict__ sumsq, float max_norm, float* __restrict__ coef,
+                                       float* __restrict__ norm_out, int* __restrict__ skipped) {
+    const float nrm = sqrtf(sumsq[0]);
+    norm_out[0] = nrm;
+    if (!__builtin_isfinite(nrm)) {
+        coef[0] = KAI0_COEF_SKIP;
+        skipped[0] += 1;
+        return;
+    }
+    coef[0] = max_norm > 0.0f ? clip_coef_value(nrm, max_norm) : 1.0f;
 }
 
 // dst[i] = round(sum_j src[j * stride + i]), j = 0 .. chunks-1 in that order, summed in f32: the local half of the all-pairs
@@ -140,11 +160,15 @@ __device__ __forceinline__ float ema_element(float e, float p, float omd) { retu
 // The argument block of every form; omd = 1 - ema_decay is unused without the EMA.
 struct AdamwEmaK {
     float cc, lr, b1, b2, eps, wd, inv_bc1, inv_sqrt_bc2, omd;
-    // the host passes bc1 / bc2 in the inv_* slots; this is the one place where the device turns them into the factors
-    __device__ __forceinline__ void finish(const float* coef) {
+    // the host passes bc1 / bc2 in the inv_* slots; this is the one place where the device turns them into the factors.
+    // false: coef[0] is negative (KAI0_COEF_SKIP from kai0_clip_coef_guard) — the step is skipped, the kernel returns before any
+    // other load or store.  Block-uniform, on the one value every block reads anyway; kai0_clip_coef only writes 0 <= coef <= 1.
+    __device__ __forceinline__ bool finish(const float* coef) {
         cc = coef ? coef[0] : 1.0f;
+        if (cc < 0.0f) return false;
         inv_bc1 = 1.0f / inv_bc1;
         inv_sqrt_bc2 = rsqrtf(inv_sqrt_bc2);
+        return true;
     }
 };
 
@@ -206,7 +230,7 @@ template <bool GF32, bool PF32, bool EMA>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
                                                     float* __restrict__ ema, const void* __restrict__ grad, void* __restrict__ param,
                                                     int64_t n, int64_t head, AdamwEmaK k, const float* __restrict__ coef) {
-    k.finish(coef);
+    if (!k.finish(coef)) return;
     const int64_t n4 = (n - head) >> 2;
     const int64_t per = (n4 + gridDim.x - 1) / gridDim.x, lo = per * blockIdx.x, hi = lo + per < n4 ? lo + per : n4;
     for (int64_t j = lo + threadIdx.x; j < hi; j += 256) adamw_vec4<GF32, PF32, EMA>(master, m, v, ema, grad, param, head + 4 * j, k);
@@ -229,7 +253,7 @@ __global__ __launch_bounds__(256) void adamw_rows_kernel(float* __restrict__ mas
                                                          void* __restrict__ param, int64_t n_rows, int row_len,
                                                          unsigned char* __restrict__ active, int vec, AdamwEmaK k,
                                                          const float* __restrict__ coef) {
-    k.finish(coef);
+    if (!k.finish(coef)) return;  // a skipped step reads no gradient and sets no activity flag
     for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
         const int64_t base = row * row_len;
         int nz = 0;
@@ -484,6 +508,15 @@ KAI0_API int kai0_sum_chunks(const void* src, int is_f32, int chunks, int64_t ch
 KAI0_API int kai0_clip_coef(const float* sumsq, float max_norm, float* coef, float* norm_out, kai0_stream_t stream) {
     hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, sumsq, max_norm, coef, norm_out);
     return kai0_check_launch("kai0_clip_coef");
+}
+
+KAI0_API int kai0_clip_coef_guard(const float* sumsq, float max_norm, float* coef, float* norm_out, int32_t* skipped,
+                                  kai0_stream_t stream) {
+    KAI0_REQUIRE(sumsq && coef && norm_out && skipped, "kai0_clip_coef_guard: null buffer");
+    KAI0_REQUIRE(((uintptr_t)sumsq % 4) == 0 && ((uintptr_t)coef % 4) == 0 && ((uintptr_t)norm_out % 4) == 0 && ((uintptr_t)skipped % 4) == 0,
+                 "kai0_clip_coef_guard: a buffer is not aligned to its element size");
+    hipLaunchKernelGGL(clip_coef_guard_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, sumsq, max_norm, coef, norm_out, skipped);
+    return kai0_check_launch("kai0_clip_coef_guard");
 }
 
 namespace {

@@ -162,15 +162,32 @@ def clip_coef_(sumsq, max_norm: float, coef, norm_out):
     _lib.call("kai0_clip_coef", sumsq.data_ptr(), float(max_norm), coef.data_ptr(), norm_out.data_ptr(), _stream())
 
 
+COEF_SKIP = -1.0  # KAI0_COEF_SKIP (include/kai0hip.h): a negative clip coefficient makes every AdamW form leave everything as it is
+
+
+def clip_coef_guard_(sumsq, max_norm, coef, norm_out, skipped):
+    """kai0_clip_coef_guard: clip_coef_ for a finite norm (max_norm None / <= 0: coef = 1, no clipping); a norm that is inf or NaN writes
+    coef = COEF_SKIP — the AdamW launches that follow then change nothing — and adds 1 to `skipped` (int32 [1], on the device)."""
+    assert skipped.dtype == torch.int32 and coef.dtype == F32 and norm_out.dtype == F32 and sumsq.dtype == F32
+    _lib.call("kai0_clip_coef_guard", sumsq.data_ptr(), float(max_norm or 0.0), coef.data_ptr(), norm_out.data_ptr(), skipped.data_ptr(),
+              _stream())  # fmt: skip
+
+
 class FusedAdamW:
     """torch.optim.AdamW-shaped optimizer (param_groups with "lr", step(), zero_grad(), state_dict()).
 
     step() = [sum of squared grads over all params -> clip coefficient on device] -> fused AdamW per tensor.
     No host synchronisation: the clip coefficient stays in device memory and is read by the update kernel.
-    `ema_decay` (None = off): an f32 EMA of the master copies, state[p]["ema"], updated inside the same kernel (kai0_adamw_ema)."""
+    `ema_decay` (None = off): an f32 EMA of the master copies, state[p]["ema"], updated inside the same kernel (kai0_adamw_ema).
+    `skip_nonfinite` (False = off, the launches of before): a step whose global gradient norm is inf or NaN changes nothing — masters,
+    moments, EMA and parameters keep their bytes — and is counted in `skipped_steps` (int32 [1], on the device; kai0_clip_coef_guard).
+    The norm is then computed even without `max_grad_norm`.  `step_count` advances all the same, so after a skip Adam's bias
+    corrections run one step ahead of the number of applied updates (negligible after warm-up; the step stays free of host reads)."""
 
-    def __init__(self, params, lr=2.5e-5, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-10, max_grad_norm=1.0, ema_decay=None):
+    def __init__(self, params, lr=2.5e-5, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-10, max_grad_norm=1.0, ema_decay=None,
+                 skip_nonfinite=False):
         self.ema_decay = check_ema_decay(ema_decay)
+        self.skip_nonfinite = bool(skip_nonfinite)
         self.params = [p for p in params if p.requires_grad]
         # tied parameters appear once
         seen, uniq = set(), []
@@ -195,6 +212,8 @@ class FusedAdamW:
         self._sumsq = torch.zeros(1, dtype=F32, device=dev)
         self._coef = torch.ones(1, dtype=F32, device=dev)
         self._norm = torch.zeros(1, dtype=F32, device=dev)
+        if self.skip_nonfinite:
+            self.skipped_steps = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def master_params(self):
         return [self.state[p]["master"] for p in self.params]
@@ -220,11 +239,14 @@ class FusedAdamW:
         self.step_count += 1
         live = [p for p in self.params if p.grad is not None]
         coef = None
-        if self.max_grad_norm is not None:
+        if self.max_grad_norm is not None or self.skip_nonfinite:
             self._sumsq.zero_()
             for p in live:
                 sumsq_accumulate_(p.grad.contiguous(), self._sumsq)
-            clip_coef_(self._sumsq, self.max_grad_norm, self._coef, self._norm)
+            if self.skip_nonfinite:
+                clip_coef_guard_(self._sumsq, self.max_grad_norm, self._coef, self._norm, self.skipped_steps)
+            else:
+                clip_coef_(self._sumsq, self.max_grad_norm, self._coef, self._norm)
             coef = self._coef
         for p in live:
             st = self.state[p]
@@ -237,10 +259,13 @@ class FusedAdamW:
             "step": self.step_count,
             "param_groups": [{k: v for k, v in self.param_groups[0].items() if k != "params"}],
             "state": [{k: v for k, v in self.state[p].items()} for p in self.params],
+            **({"skipped_steps": int(self.skipped_steps)} if self.skip_nonfinite else {}),
         }
 
     def load_state_dict(self, sd):
         self.step_count = sd["step"]
+        if self.skip_nonfinite:  # absent in a state written without the guard: 0
+            self.skipped_steps.fill_(int(sd.get("skipped_steps", 0)))
         for k, v in sd["param_groups"][0].items():
             self.param_groups[0][k] = v
         for p, st in zip(self.params, sd["state"], strict=True):

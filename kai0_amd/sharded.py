@@ -45,6 +45,11 @@ last the gradient reduction is finished as in step() and every bucket's gradient
 squares of the result from the same launch — and clips / updates from the accumulator.  Every pass is reduce-scattered, only the
 1/N shard is accumulated: the full-size gradient buffers stay staging buffers (fsdp).
 
+Non-finite gradients (`skip_nonfinite`, off by default): the step never talks to the host, so a gradient norm that is inf or NaN is
+caught where it is formed — kai0_clip_coef_guard writes a negative clip coefficient, which every AdamW form reads as "leave everything
+as it is", and counts the step (`skipped_steps`).  Without the switch such a step is applied (inf * 0 = NaN, or NaN unclipped) and
+the run is lost, EMA included.
+
 The whole optimizer is 3 kernels per bucket on flat shards (sum of squares, clip coefficient kept on device, fused
 AdamW) — no per-tensor launches, no host sync.  The arithmetic is pluggable (`ShardOps`) only so the collective /
 partition logic can be exercised on CPU with gloo; the product default is the HIP kernels and raises without them.
@@ -74,6 +79,11 @@ class HipShardOps:
         from .optim import clip_coef_
 
         clip_coef_(sumsq, max_norm, coef, norm)
+
+    def clip_coef_guard(self, sumsq, max_norm, coef, norm, skipped):
+        from .optim import clip_coef_guard_
+
+        clip_coef_guard_(sumsq, max_norm, coef, norm, skipped)
 
     def sum_chunks(self, src, chunks, out):
         from .optim import sum_chunks_
@@ -244,11 +254,23 @@ def plan_partition(units, *, world_size: int, bucket_bytes: int, exclude=()):
 class ShardedDataParallel:
     def __init__(self, params, *, world_size: int, rank: int, group=None, ops=None, betas=(0.9, 0.95), eps=1e-8,
                  weight_decay=1e-10, max_grad_norm=1.0, bucket_bytes: int = 512 << 20, units=None, mode: str = "zero2",
-                 prefetch: int = 1, sync_params: bool = True, rs_algo: str | None = None, ema_decay: float | None = None):  # fmt: skip
+                 prefetch: int = 1, sync_params: bool = True, rs_algo: str | None = None, ema_decay: float | None = None,
+                 skip_nonfinite: bool = False):  # fmt: skip
         """`params`: parameters, or (name, parameter) pairs (names make the checkpoint world-size independent).
         `units`: [(unit name, [parameters])] in forward-use order; parameters not listed form a last unit "rest".
         `ema_decay`: None (default) = no EMA, nothing allocated, the kernels of before; d in [0, 1) = an f32 EMA shard per bucket,
-        initialised from the master, ema += (1 - d) (master - ema) after every update."""
+        initialised from the master, ema += (1 - d) (master - ema) after every update.
+        `skip_nonfinite`: False (default) = the launches of before.  True = a step whose global gradient norm is inf or NaN is dropped
+        on the device: `ops.clip_coef_guard` writes a negative clip coefficient and every AdamW launch of the step returns at once —
+        masters, moments, EMA, the model copy and the row-activity flags keep their bytes — and `skipped_steps` (int32 [1], device)
+        counts it.  The norm is all-reduced, so every rank takes the same decision; it is computed even with max_grad_norm=None.
+        `step_count` and with it the bias corrections advance on a skipped step (the batch is consumed, the host never learns the
+        norm inside the step): after a skip Adam's t runs one ahead of the number of applied updates, which is negligible after
+        warm-up.  Needs an `ops` object with `clip_coef_guard` whose AdamW forms honour the negative coefficient."""
+        self.skip_nonfinite = bool(skip_nonfinite)
+        if self.skip_nonfinite and ops is not None and not hasattr(ops, "clip_coef_guard"):
+            raise TypeError(f"skip_nonfinite=True needs an ops object with clip_coef_guard (and AdamW forms that honour a negative clip "
+                            f"coefficient); {type(ops).__name__} has none")  # fmt: skip
         if ema_decay is not None:
             ema_decay = float(ema_decay)
             if not 0.0 <= ema_decay < 1.0:
@@ -340,6 +362,8 @@ class ShardedDataParallel:
         self._sumsq = torch.zeros(1, dtype=F32, device=self.device)
         self._coef = torch.ones(1, dtype=F32, device=self.device)
         self._norm = torch.zeros(1, dtype=F32, device=self.device)
+        if self.skip_nonfinite:  # (an engine without the guard has no such attribute)
+            self.skipped_steps = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._in_backward = False
         self._micro = 0  # micro-batches of the current step already added into the buckets' `acc` (end_micro_batch)
         # KAI0_SPARSE_EMBED=0: the embedding table's rows all go through the dense update (A/B; the result is bit-identical)
@@ -771,13 +795,15 @@ class ShardedDataParallel:
     def step(self, lr: float):
         """Finish the gradient reduction, clip by the global norm, update the local shards, start the parameter all-gathers
         (zero2; waited for by the next forward, unit by unit).  Returns the global (pre-clip) gradient norm as a 1-element
-        device tensor.  After `end_micro_batch()` calls the gradient is the accumulated one (this backward's added last)."""
+        device tensor.  After `end_micro_batch()` calls the gradient is the accumulated one (this backward's added last).
+        With `skip_nonfinite` a norm that is inf or NaN leaves every shard as it is (the constructor's docstring); the returned norm
+        is that non-finite value, `step_count` advances."""
         self._not_in_ema("step()")
         self.step_count += 1
         self._finish_reduction()
         accumulated = self._micro > 0
         coef = None
-        if self.max_grad_norm is not None:
+        if self.max_grad_norm is not None or self.skip_nonfinite:  # the guard needs the norm even without clipping
             self._sumsq.zero_()
             if accumulated:
                 self._accumulate(sumsq_out=self._sumsq)
@@ -786,7 +812,11 @@ class ShardedDataParallel:
                     self.ops.sumsq(b.grad_shard, self._sumsq)
             if self.world > 1:
                 self._wait(dist.all_reduce(self._sumsq, op=dist.ReduceOp.SUM, group=self.group, async_op=True), "norm_all_reduce")
-            self.ops.clip_coef(self._sumsq, self.max_grad_norm, self._coef, self._norm)
+            if self.skip_nonfinite:
+                # the all-reduced sum is the same on every rank: all of them skip or none does.  max_norm = 0: coef = 1 (no clipping)
+                self.ops.clip_coef_guard(self._sumsq, self.max_grad_norm or 0.0, self._coef, self._norm, self.skipped_steps)
+            else:
+                self.ops.clip_coef(self._sumsq, self.max_grad_norm, self._coef, self._norm)
             coef = self._coef
         elif accumulated:
             self._accumulate()
@@ -846,7 +876,11 @@ class ShardedDataParallel:
             ema_kw = {"ema_decay": self.ema_decay} if fused else {}
             getattr(self.ops, name + "_ema" if fused else name)(*state, grad[lo:hi], b.param_shard[lo:hi], *(rows or ()), **ema_kw, **kw)
             if ema_on and not fused:  # an ops object without the fused form (the torch oracle of the CPU tests): the same update as a second pass
-                b.ema[lo:hi].lerp_(b.master[lo:hi], ema_lerp_weight(self.ema_decay))
+                if self.skip_nonfinite:  # ... which a skipped step must not make: the decision is read on the device, like the kernels do
+                    e = b.ema[lo:hi]
+                    e.copy_(torch.where(coef < 0, e, e.lerp(b.master[lo:hi], ema_lerp_weight(self.ema_decay))))
+                else:
+                    b.ema[lo:hi].lerp_(b.master[lo:hi], ema_lerp_weight(self.ema_decay))
 
         # with EMA the row-sparse form must know about it (an ops object that does not falls back to the dense update)
         if self._sparse_rows and hasattr(self.ops, "adamw_rows_ema" if ema_on else "adamw_rows"):
@@ -900,7 +934,8 @@ class ShardedDataParallel:
             raise KeyError(f"param_order lacks trained parameters: {sorted(missing)[:3]} ...")
         return {"state": {i: by_name[n] for i, n in enumerate(order) if n in by_name},
                 "param_groups": [{"betas": self.betas, "eps": self.eps, "weight_decay": self.wd, "params": list(range(len(order)))}],
-                "param_names": order, "step": self.step_count}  # fmt: skip
+                "param_names": order, "step": self.step_count,
+                **({"skipped_steps": int(self.skipped_steps)} if self.skip_nonfinite else {})}  # fmt: skip
 
     @torch.no_grad()
     def load_state_dict(self, sd, param_order=None):
@@ -919,6 +954,8 @@ class ShardedDataParallel:
         by_name = {pnames[i]: ent for i, ent in state.items()}
         steps = [float(s["step"]) for s in state.values() if "step" in s]
         self.step_count = int(sd.get("step", max(steps) if steps else 0))
+        if self.skip_nonfinite:  # absent in a state written without the guard: no step was ever skipped
+            self.skipped_steps.fill_(int(sd.get("skipped_steps", 0)))
         # torch.optim.AdamW only holds state for parameters that have received a gradient: in the reference's optimizer.pt the
         # last layer's prefix o_proj / MLP / post-attention norm and language_model.norm (dead values) have no entry.
         # A missing entry = "never updated": zero moments, master copy = the current parameter.  Master copies are adopted per

@@ -9,6 +9,8 @@ layout (train_pytorch.py:149-194): `model.safetensors` + ONE world-size independ
 `tmp_<step>` then renamed atomically; a checkpoint resumes on any number of GPUs.  With a parameter EMA (`Trainer(ema_decay=...)`,
 `KAI0_EMA=1` for `train_loop`; the JAX trainer's scripts/train.py:172-177) the f32 average rides in `optimizer.pt` and its rounded
 copy is written beside the raw weights as `model_ema.safetensors` — the file `create_trained_policy(..., ema=True)` serves.
+With `Trainer(skip_nonfinite=True)` (`KAI0_SKIP_NONFINITE=1` for `train_loop`) an optimizer step whose gradient norm is inf or NaN is
+dropped on the device instead of destroying the run; the count rides in `optimizer.pt` and `metadata.pt`.
 
 Weights must be in the model BEFORE the Trainer is built (it moves every parameter into flat buffers and cuts its f32 master
 copies from them); weights written in place afterwards (`load_state_dict`, `p.data.copy_`, model_arithmetic) are adopted
@@ -20,6 +22,7 @@ from __future__ import annotations
 import contextlib
 import dataclasses
 import logging
+import math
 import os
 import shutil
 import time
@@ -38,7 +41,7 @@ class Trainer:
     def __init__(self, model, *, world_size: int = 1, rank: int = 0, group=None, peak_lr=2.5e-5, warmup_steps=1000,
                  decay_steps=30000, end_lr=2.5e-6, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-10, clip_norm=1.0,
                  shard_ops=None, bucket_bytes: int | None = None, mode: str | None = None, prefetch: int | None = None,
-                 ema_decay: float | None = None, micro_batch: int | None = None):  # fmt: skip
+                 ema_decay: float | None = None, micro_batch: int | None = None, skip_nonfinite: bool = False):  # fmt: skip
         """`bucket_bytes` / `prefetch` default per mode: zero2 512 MB buckets (few, large collectives; nothing waits on them
         inside forward / backward); fsdp 256 MB (~ one joint Gemma-2B + expert layer, SURVEY.md §8e's unit) gathered two
         buckets ahead, so that a bucket's gather has two layers of compute to hide behind and ~0.75 GB of full parameters
@@ -46,7 +49,9 @@ class Trainer:
         updated inside the AdamW pass (sharded.ShardedDataParallel).  `micro_batch`: None = env KAI0_MICRO_BATCH (unset / 0 = off);
         m = `train_step` runs the rank's batch of B samples as B // m forward / backward passes of m samples whose gradients the
         engine accumulates in f32 (`end_micro_batch`), then ONE optimizer step: the trajectory of the batch size the recipe was
-        written for, at the activation memory of m samples."""
+        written for, at the activation memory of m samples.  `skip_nonfinite`: False = as before (default); True = an optimizer step whose
+        global gradient norm is inf or NaN is dropped on the device (sharded.ShardedDataParallel): weights, moments and EMA keep their
+        bytes, `skipped_steps` counts it, `global_step` and the LR schedule advance (the batch is consumed)."""
         if micro_batch is None:
             micro_batch = int(os.environ.get("KAI0_MICRO_BATCH", "0") or 0)
         if micro_batch < 0:
@@ -70,7 +75,8 @@ class Trainer:
             prefetch = int(os.environ.get("KAI0_FSDP_PREFETCH", "2" if mode == "fsdp" else "1"))
         self.engine = ShardedDataParallel(named, world_size=world_size, rank=rank, group=group, ops=shard_ops, betas=betas,
                                           eps=eps, weight_decay=weight_decay, max_grad_norm=clip_norm,
-                                          bucket_bytes=bucket_bytes, units=units, mode=mode, prefetch=prefetch, ema_decay=ema_decay)  # fmt: skip
+                                          bucket_bytes=bucket_bytes, units=units, mode=mode, prefetch=prefetch, ema_decay=ema_decay,
+                                          skip_nonfinite=skip_nonfinite)  # fmt: skip
         # the model announces its units (pre_forward / post_forward): parameter gathers are awaited layer by layer
         self._hooked = hasattr(model, "set_unit_hooks")
         if self._hooked:
@@ -141,6 +147,14 @@ class Trainer:
     def ema_decay(self):
         return self.engine.ema_decay
 
+    @property
+    def skip_nonfinite(self) -> bool:
+        return self.engine.skip_nonfinite
+
+    def skipped_total(self) -> int:
+        """Optimizer steps dropped so far for a non-finite gradient norm (reads the device counter: synchronises); 0 without the guard."""
+        return int(self.engine.skipped_steps) if self.engine.skip_nonfinite else 0
+
     @contextlib.contextmanager
     def ema_weights(self):
         """The model computes with the averaged (EMA) weights inside the context and with the raw ones again after it (every rank
@@ -179,6 +193,7 @@ class Trainer:
         self.engine.wait_params()
         opt_sd = self.engine.state_dict(self._param_order)
         rng = _gather_rng_states(self.world, self.engine.device)
+        skipped = self.skipped_total()
         if self.rank == 0:
             if os.path.exists(tmp):
                 shutil.rmtree(tmp)
@@ -195,6 +210,8 @@ class Trainer:
             # (not in the reference's metadata) the ranks' RNG states: with them and `skip_batches` a resumed run draws the same
             # noise / time / augmentation and sees the same batches as the run that was interrupted
             meta = {"global_step": step, "world_size": self.world, "timestamp": time.time(), "rng_state": rng}
+            if self.skip_nonfinite:
+                meta["skipped_total"] = skipped  # steps dropped for a non-finite gradient norm (also in optimizer.pt: skipped_steps)
             if config is not None:
                 meta["config"] = _plain(dataclasses.asdict(config) if dataclasses.is_dataclass(config) else config)
             torch.save(meta, os.path.join(tmp, "metadata.pt"))
@@ -235,6 +252,8 @@ class Trainer:
                                                 "no RNG state", d, type(e).__name__)  # fmt: skip
             meta = {}
         self.global_step = int(meta.get("global_step", step))
+        if self.skip_nonfinite and "skipped_total" in meta:  # (optimizer.pt carries the same count; a checkpoint without either: 0)
+            self.engine.skipped_steps.fill_(int(meta["skipped_total"]))
         self.resumed_rng_state = meta.get("rng_state")  # train_loop restores it when the world size is the one that wrote it
         if getattr(self.model, "_engine", None) is not None:
             self.model.invalidate_inference_engine()
@@ -302,6 +321,15 @@ def augment_mode_from_env() -> str:
     return mode
 
 
+def skip_nonfinite_from_env() -> bool:
+    """KAI0_SKIP_NONFINITE: unset or `0` = off (the default: the launches of before), `1` = optimizer steps whose gradient norm is not
+    finite are dropped on the device (`Trainer(skip_nonfinite=True)`)."""
+    v = os.environ.get("KAI0_SKIP_NONFINITE", "0")
+    if v not in ("0", "1"):
+        raise ValueError(f"KAI0_SKIP_NONFINITE={v!r}: expected '0' or '1'")
+    return v == "1"
+
+
 def build_model(config, device):
     """train_pytorch.py:399-458: `config.model` in `pytorch_training_precision`, on `device`, with `pytorch_weight_path`'s
     `model.safetensors` loaded (strict unless an AdvantageEstimator is initialised from a policy checkpoint)."""
@@ -348,10 +376,14 @@ def train_loop(config, *, device=None, shard_ops=None, model=None, log=None):
     (`pytorch_weight_path`) -> `Trainer` from `config.lr_schedule` / `config.optimizer` -> for every batch: one train step; mean
     loss / lr / grad-norm logged every `log_interval` steps (the step itself never synchronises: the scalars of an interval are
     read when it is logged); checkpoint every `save_interval` steps and at the last step, with the norm stats; `resume`
-    continues from the newest checkpoint on any number of GPUs.  Returns the list of logged records (rank 0)."""
+    continues from the newest checkpoint on any number of GPUs.  Returns the list of logged records (rank 0).
+    KAI0_SKIP_NONFINITE=1: steps with a non-finite gradient norm are skipped on the device; the record's loss / grad_norm / learning_rate
+    are then means over the interval's applied steps and it gains `skipped` (this interval) and `skipped_total` (also in the
+    checkpoint's metadata, restored on resume).  No abort rule: a diverged run shows as skipped == steps in every interval."""
     from .data_loader import DeviceFeeder
     from .lerobot_dataset import create_data_loader
 
+    guard = skip_nonfinite_from_env()  # (first: a misspelt switch is refused before anything is built)
     world, rank, dev = _setup_distributed()
     device = torch.device(device) if device is not None else dev
     is_main = rank == 0
@@ -390,7 +422,7 @@ def train_loop(config, *, device=None, shard_ops=None, model=None, log=None):
     trainer = Trainer(model, world_size=world, rank=rank, peak_lr=sch.peak_lr, warmup_steps=sch.warmup_steps,
                       decay_steps=sch.decay_steps, end_lr=sch.decay_lr, betas=(opt.b1, opt.b2), eps=opt.eps,
                       weight_decay=opt.weight_decay, clip_norm=opt.clip_gradient_norm, shard_ops=shard_ops, ema_decay=ema_decay,
-                      micro_batch=int(os.environ.get("KAI0_MICRO_BATCH", "0") or 0) or None)  # fmt: skip
+                      micro_batch=int(os.environ.get("KAI0_MICRO_BATCH", "0") or 0) or None, skip_nonfinite=guard)  # fmt: skip
     if resuming:
         step = trainer.load_checkpoint(str(ckpt_dir))
         exact = _restore_rng_state(getattr(trainer, "resumed_rng_state", None), world, rank, device)
@@ -410,6 +442,12 @@ def train_loop(config, *, device=None, shard_ops=None, model=None, log=None):
     else:
         say("parameter EMA off" + (" (KAI0_EMA=1, but config.ema_decay is None)" if os.environ.get("KAI0_EMA", "0") == "1"
                                    else f" (config.ema_decay={config.ema_decay} is ignored unless KAI0_EMA=1)"))  # fmt: skip
+    if guard:
+        say(f"non-finite guard on (KAI0_SKIP_NONFINITE=1): a step whose gradient norm is inf or NaN is skipped on the device; "
+            f"{trainer.skipped_total()} skipped so far")  # fmt: skip
+    else:
+        say("non-finite guard off (KAI0_SKIP_NONFINITE=1 skips optimizer steps whose gradient norm is inf or NaN)")
+    warn = log or (logging.warning if is_main else (lambda *_: None))
 
     records, pending, t0 = [], [], time.time()
     while trainer.global_step < config.num_train_steps:
@@ -424,12 +462,24 @@ def train_loop(config, *, device=None, shard_ops=None, model=None, log=None):
             pending.append((loss, lr, trainer.last_grad_norm.clone()))
             if step % config.log_interval == 0:
                 vals = [(float(l), r, float(g)) for l, r, g in pending]  # the interval's only host synchronisation
-                rec = {"step": step, "loss": sum(v[0] for v in vals) / len(vals), "learning_rate": sum(v[1] for v in vals) / len(vals),
-                       "grad_norm": sum(v[2] for v in vals) / len(vals), "time_per_step": (time.time() - t0) / len(vals)}  # fmt: skip
+                n_steps, skipped = len(vals), 0
+                if guard:  # the means are over the applied steps: a step was skipped iff its norm (what the device tested) is not finite
+                    vals = [v for v in vals if math.isfinite(v[2])]
+                    skipped = n_steps - len(vals)
+                mean = lambda i: sum(v[i] for v in vals) / len(vals) if vals else float("nan")  # noqa: E731
+                rec = {"step": step, "loss": mean(0), "learning_rate": mean(1), "grad_norm": mean(2),
+                       "time_per_step": (time.time() - t0) / n_steps}  # fmt: skip
+                if guard:
+                    rec["skipped"], rec["skipped_total"] = skipped, trainer.skipped_total()
                 if is_main:
                     records.append(rec)
-                    say(f"step={step} loss={rec['loss']:.4f} lr={rec['learning_rate']:.2e} grad_norm={rec['grad_norm']:.2f} "
-                        f"time/step={rec['time_per_step']:.3f}s")  # fmt: skip
+                    line = (f"step={step} loss={rec['loss']:.4f} lr={rec['learning_rate']:.2e} grad_norm={rec['grad_norm']:.2f} "
+                            f"time/step={rec['time_per_step']:.3f}s")  # fmt: skip
+                    if skipped:
+                        warn(line + f" skipped={skipped} of {n_steps} steps (non-finite gradient norm), skipped_total={rec['skipped_total']}"
+                             + (": EVERY step of the interval was skipped, the means are NaN" if not vals else ""))  # fmt: skip
+                    else:
+                        say(line)
                 pending, t0 = [], time.time()
             gs = trainer.global_step
             if (gs % config.save_interval == 0 and gs > 0) or gs == config.num_train_steps:
