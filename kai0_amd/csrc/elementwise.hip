@@ -30,12 +30,45 @@ inline int ew_grid(int64_t n_items, int per_block) {
 }
 
 // ---------------------------------------------------------------------------------------------- RoPE
+// The rotation as helpers (pack_rows_kernel calls them; rope_kernel below is the same arithmetic written out).  A thread owns 4
+// consecutive frequency indices i4..i4+3 of one row and walks the heads, so the sin / cos of a position is computed once for all heads.
+// The roundings are the parity contract with the reference's bf16-typed torch ops: cos and sin rounded to bf16, then
+// q*cos + rotate_half(q)*sin with every product and the sum rounded to bf16 — f2bf(rbf(x1*c) + rbf(-x2*sn)).
+__device__ __forceinline__ void rope_sincos4(const float* inv_freq, int i4, float p, int inverse, float (&c)[4], float (&sn)[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float ang = inv_freq[i4 + e] * p;
+        c[e] = rbf(cosf(ang));
+        sn[e] = rbf(sinf(ang));
+        if (inverse) sn[e] = -sn[e];
+    }
+}
+// dst_row[h][:] = rotate(src_row[h][:]) for the H heads of one row, this thread's 4 + 4 elements of each (in place when dst_row == src_row)
+__device__ __forceinline__ void rope_rotate_heads(bf16_t* dst_row, const bf16_t* src_row, int H, int HD, int i4, const float (&c)[4],
+                                                  const float (&sn)[4]) {
+    for (int h = 0; h < H; ++h) {
+        const bf16x4 a = *reinterpret_cast<const bf16x4*>(src_row + h * HD + i4);
+        const bf16x4 bq = *reinterpret_cast<const bf16x4*>(src_row + h * HD + i4 + (HD >> 1));
+        bf16x4 o1, o2;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float x1 = bf2f(a[e]), x2 = bf2f(bq[e]);
+            o1[e] = f2bf(rbf(x1 * c[e]) + rbf(-x2 * sn[e]));
+            o2[e] = f2bf(rbf(x2 * c[e]) + rbf(x1 * sn[e]));
+        }
+        *reinterpret_cast<bf16x4*>(dst_row + h * HD + i4) = o1;
+        *reinterpret_cast<bf16x4*>(dst_row + h * HD + i4 + (HD >> 1)) = o2;
+    }
+}
+
 // dst[b][s][h][:] = rope(src[b][s][h][:], pos[b][s]) for B x S rows of H heads (in place when dst == src and the strides
 // agree).  A thread owns 4 consecutive frequency indices i4..i4+3 of one (b, s) row and walks the heads, so the sin / cos of
 // a position is computed once for all heads.  Strides (elements): *_bs between batch entries, *_ld between rows; pos_bs
 // between the position rows of consecutive batch entries.  The strided form lets the joint-attention assembly (scatter a
 // segment's q / k into the joint buffer, or gather its gradient back out) apply the rotation on the way instead of in a
 // separate in-place pass over the joint buffer.
+// (Written out, not on rope_sincos4 / rope_rotate_heads: the helpers give hipcc another instruction order, and the training step, where
+// such a change is timed, no longer launches this kernel — see profiles/HISTORY.md.)
 __global__ __launch_bounds__(256) void rope_kernel(bf16_t* __restrict__ dst, const bf16_t* __restrict__ src,
                                                    const int32_t* __restrict__ pos, const float* __restrict__ inv_freq, int B,
                                                    int S, int64_t dst_bs, int64_t dst_ld, int64_t src_bs, int64_t src_ld,
@@ -497,27 +530,9 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(PackArgs a) {
     const int i4 = tl * 4;
     const float p = (float)a.pos[(int64_t)b * a.pos_bs + pt.pos_off + s];
     float c[4], sn[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float ang = a.inv_freq[i4 + e] * p;
-        c[e] = rbf(cosf(ang));
-        sn[e] = rbf(sinf(ang));
-        if (pt.mode == 2) sn[e] = -sn[e];
-    }
+    rope_sincos4(a.inv_freq, i4, p, pt.mode == 2, c, sn);
     const int H = pt.cols / HD;
-    for (int h = 0; h < H; ++h) {
-        const bf16x4 x1v = *reinterpret_cast<const bf16x4*>(xr + h * HD + i4);
-        const bf16x4 x2v = *reinterpret_cast<const bf16x4*>(xr + h * HD + i4 + (HD >> 1));
-        bf16x4 o1, o2;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float x1 = bf2f(x1v[e]), x2 = bf2f(x2v[e]);
-            o1[e] = f2bf(rbf(x1 * c[e]) + rbf(-x2 * sn[e]));  // the roundings of rope_kernel
-            o2[e] = f2bf(rbf(x2 * c[e]) + rbf(x1 * sn[e]));
-        }
-        *reinterpret_cast<bf16x4*>(yr + h * HD + i4) = o1;
-        *reinterpret_cast<bf16x4*>(yr + h * HD + i4 + (HD >> 1)) = o2;
-    }
+    rope_rotate_heads(yr, xr, H, HD, i4, c, sn);
 }
 
 // Sampled content checksum of a list of buffers (device array of {pointer, bytes}): every `stride`-th 64-byte unit of each buffer,
@@ -662,7 +677,7 @@ static bool rope_hd_ok(int HD) { return HD % 8 == 0 && HD >= 8 && HD <= 2048 && 
 static int rope_launch(const char* who, bf16_t* dst, const bf16_t* src, const int32_t* pos, const float* inv_freq, int B, int S, int64_t dst_bs,
                        int64_t dst_ld, int64_t src_bs, int64_t src_ld, int64_t pos_bs, int H, int HD, int inverse, kai0_stream_t stream,
                        bf16_t* x2 = nullptr, int64_t x2_bs = 0, int64_t x2_ld = 0, int H2 = 0) {
-    if (B * S <= 0) return 0;
+    if ((int64_t)B * S <= 0) return 0;
     const int rpb = 256 / (HD / 8);
     hipLaunchKernelGGL(rope_kernel, dim3(ew_grid((int64_t)B * S, rpb)), dim3(256), 0, S_(stream), dst, src, pos, inv_freq, B, S, dst_bs, dst_ld,
                        src_bs, src_ld, pos_bs, H, HD, inverse, x2, x2_bs, x2_ld, H2);
@@ -843,7 +858,7 @@ KAI0_API int kai0_copy_rows_bf16(const void* src, void* dst, int B, int rows, in
 KAI0_API int kai0_pack_rows(const kai0_pack_part* parts, int n, const int32_t* pos, int64_t pos_bs, const float* inv_freq, int HD,
                             kai0_stream_t stream) {
     KAI0_REQUIRE(parts != nullptr && n > 0 && n <= 12, "kai0_pack_rows: 1..12 parts (n=%d)", n);
-    KAI0_REQUIRE(HD % 8 == 0 && HD >= 8 && HD <= 2048 && 256 % (HD / 8) == 0, "kai0_pack_rows: HD=%d unsupported", HD);
+    KAI0_REQUIRE(rope_hd_ok(HD), "kai0_pack_rows: HD=%d unsupported", HD);
     PackArgs a;
     const int rpb = 256 / (HD / 8);
     int blocks = 0;
@@ -983,20 +998,26 @@ __global__ __launch_bounds__(256) void prefix_codes_kernel(const CodesArgs a, in
 }
 }  // namespace
 
-KAI0_API int kai0_prefix_state_codes(const void* const* img_masks, int ncam, const void* lang_mask, int B, int n_img, int T,
-                                     int n_state, int Hs, int32_t* qcode, int32_t* kcode, int32_t* pos, kai0_stream_t stream) {
-    KAI0_REQUIRE(img_masks && lang_mask && qcode && kcode && pos, "kai0_prefix_state_codes: null operand");
-    KAI0_REQUIRE(ncam >= 1 && ncam <= 8 && n_img >= 1 && T >= 0 && Hs >= 0 && B >= 1 && n_state >= 0 && n_state <= 16,
-                 "kai0_prefix_state_codes: ncam=%d n_img=%d T=%d n_state=%d Hs=%d B=%d", ncam, n_img, T, n_state, Hs, B);
+// The one prefix_codes_kernel launch behind both entry points (operands and ranges already checked by the entry point, under its own messages)
+static int prefix_codes_launch(const char* who, const void* const* img_masks, int ncam, const void* lang_mask, int B, int n_img, int T,
+                               int n_state, int Hs, int32_t* qcode, int32_t* kcode, int32_t* pos, kai0_stream_t stream) {
     CodesArgs a{};
     for (int c = 0; c < ncam; ++c) {
-        KAI0_REQUIRE(img_masks[c] != nullptr, "kai0_prefix_state_codes: null camera mask %d", c);
+        KAI0_REQUIRE(img_masks[c] != nullptr, "%s: null camera mask %d", who, c);
         a.img[c] = (const uint8_t*)img_masks[c];
     }
     a.lang = (const uint8_t*)lang_mask;
     a.ncam = ncam; a.n_img = n_img; a.T = T; a.Hs = Hs; a.n_state = n_state;
     hipLaunchKernelGGL(prefix_codes_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, qcode, kcode, pos);
-    return kai0_check_launch("kai0_prefix_state_codes");
+    return kai0_check_launch(who);
+}
+
+KAI0_API int kai0_prefix_state_codes(const void* const* img_masks, int ncam, const void* lang_mask, int B, int n_img, int T,
+                                     int n_state, int Hs, int32_t* qcode, int32_t* kcode, int32_t* pos, kai0_stream_t stream) {
+    KAI0_REQUIRE(img_masks && lang_mask && qcode && kcode && pos, "kai0_prefix_state_codes: null operand");
+    KAI0_REQUIRE(ncam >= 1 && ncam <= 8 && n_img >= 1 && T >= 0 && Hs >= 0 && B >= 1 && n_state >= 0 && n_state <= 16,
+                 "kai0_prefix_state_codes: ncam=%d n_img=%d T=%d n_state=%d Hs=%d B=%d", ncam, n_img, T, n_state, Hs, B);
+    return prefix_codes_launch("kai0_prefix_state_codes", img_masks, ncam, lang_mask, B, n_img, T, n_state, Hs, qcode, kcode, pos, stream);
 }
 
 KAI0_API int kai0_prefix_codes(const void* const* img_masks, int ncam, const void* lang_mask, int B, int n_img, int T, int Hs,
@@ -1004,13 +1025,5 @@ KAI0_API int kai0_prefix_codes(const void* const* img_masks, int ncam, const voi
     KAI0_REQUIRE(img_masks && lang_mask && qcode && kcode && pos, "kai0_prefix_codes: null operand");
     KAI0_REQUIRE(ncam >= 1 && ncam <= 8 && n_img >= 1 && T >= 0 && Hs >= 0 && B >= 1, "kai0_prefix_codes: ncam=%d n_img=%d T=%d Hs=%d B=%d",
                  ncam, n_img, T, Hs, B);
-    CodesArgs a{};
-    for (int c = 0; c < ncam; ++c) {
-        KAI0_REQUIRE(img_masks[c] != nullptr, "kai0_prefix_codes: null camera mask %d", c);
-        a.img[c] = (const uint8_t*)img_masks[c];
-    }
-    a.lang = (const uint8_t*)lang_mask;
-    a.ncam = ncam; a.n_img = n_img; a.T = T; a.Hs = Hs;
-    hipLaunchKernelGGL(prefix_codes_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a, qcode, kcode, pos);
-    return kai0_check_launch("kai0_prefix_codes");
+    return prefix_codes_launch("kai0_prefix_codes", img_masks, ncam, lang_mask, B, n_img, T, 0, Hs, qcode, kcode, pos, stream);
 }

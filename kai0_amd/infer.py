@@ -338,8 +338,8 @@ class InferenceEngine:
         table = pe.paligemma.model.language_model.embed_tokens.weight
         ops.embed_gather(table, tok, embs, ops.sqrt_scale(D), P * D, ncam * n_img, D)
         if not direct:
-            for c in range(ncam):
-                ops._copy_rows(feats.reshape(ncam * B * n_img, D)[c * B * n_img :], embs, B, n_img, D, n_img * D, 0, D, P * D, c * n_img, D)
+            for c, cam in enumerate(feats.reshape(ncam, B, n_img, D)):
+                ops.copy_rows(cam, embs.view(B, P, D)[:, c * n_img : (c + 1) * n_img])
         return embs.view(B, P, D)
 
     def _build_fast(self):
@@ -455,7 +455,7 @@ class InferenceEngine:
                 gemm(hp, self.lm_wqkv[l][NQ:], self.k_cache[l], M=M, N=2 * HD, K=self.Dp, lda=self.Dp, ldb=self.Dp, ldc=HD,
                      c_map=(P, S_ld, 0), segs=[(self.k_cache[l], HD, 0), (self.v_cache[l], HD, HD)],
                      split_k=pick_split_k(M, 2 * HD, self.Dp))  # fmt: skip
-                ops.rope_(self.k_cache[l], self.pos_prefix, inv_freq, B, P, S_ld, 0, 1, HD)
+                ops.rope_(self.k_cache[l][:, :P], self.pos_prefix, inv_freq, HD)
                 break
             # stacked q|k|v projection written straight into the padded q buffer and the K / V caches
             segs = [(self.q_buf, NQ, 0), (self.k_cache[l], HD, NQ), (self.v_cache[l], HD, NQ + HD)]
@@ -465,7 +465,7 @@ class InferenceEngine:
             else:
                 gemm(hp, self.lm_wqkv[l], self.q_buf, M=M, N=NQ + 2 * HD, K=self.Dp, lda=self.Dp, ldb=self.Dp, ldc=NQ,
                      c_map=(P, S_ld, 0), segs=segs, split_k=_PREFIX_SPLITS[0] or 1)
-                ops.rope2_(self.q_buf, H, self.k_cache[l], 1, self.pos_prefix, inv_freq, B, P, S_ld, 0, HD)  # q and k: one launch
+                ops.rope2_(self.q_buf[:, :P], self.k_cache[l][:, :P], self.pos_prefix, inv_freq, HD)  # q and k: one launch
             self._attend(l, 0, P, P, qcode, kcode)
             pan = layer.post_attention_layernorm
             xp, hp = self._oproj(at.o_proj, P, 0, residual=xp, norm=(1, pan.weight, None, pan.eps))
@@ -640,7 +640,7 @@ class InferenceEngine:
         a = ops.linear_f32(x_t.view(B * Hs, self.A), model.action_in_proj.weight, model.action_in_proj.bias)
         pre = ops.linear_f32(a, sch.w_act, sch.tvec[step].contiguous())
         y = ops.linear_f32(ops.silu_f32(pre), model.action_time_mlp_out.weight, model.action_time_mlp_out.bias)
-        ops._copy_rows(ops.cast(y, BF16), xs, B, Hs, De, Hs * De, 0, De, self.Ss * De, 1, De)
+        ops.copy_rows(ops.cast(y, BF16).view(B, Hs, De), xs.view(B, self.Ss, De)[:, 1:])
         return pre
 
     def _pi0_state_rows(self, state):
@@ -649,7 +649,7 @@ class InferenceEngine:
         model, B, De = self.model, self.B, self.De
         xs = torch.empty((B * self.Ss, De), dtype=BF16, device=self.dev)
         s = ops.linear_f32(state.to(F32).contiguous(), model.state_proj.weight, model.state_proj.bias)
-        ops._copy_rows(ops.cast(s, BF16), xs, B, 1, De, De, 0, De, self.Ss * De, 0, De)
+        ops.copy_rows(ops.cast(s, BF16).view(B, 1, De), xs.view(B, self.Ss, De)[:, :1])
         return xs
 
     def _denoise_step(self, x_t, step: int, sch, xs=None, tape: list | None = None):
@@ -696,14 +696,14 @@ class InferenceEngine:
             self._proj_into(hs, at.q_proj, self.q_buf, Ss, P, NQ)
             self._proj_into(hs, at.k_proj, self.k_cache[l], Ss, P, HD)
             self._proj_into(hs, at.v_proj, self.v_cache[l], Ss, P, HD)
-            ops.rope_(self.q_buf, self.pos_suffix, inv_freq, B, Ss, S_ld, P, H, HD)
-            ops.rope_(self.k_cache[l], self.pos_suffix, inv_freq, B, Ss, S_ld, P, 1, HD)
+            ops.rope_(self.q_buf[:, P : P + Ss], self.pos_suffix, inv_freq, HD)
+            ops.rope_(self.k_cache[l][:, P : P + Ss], self.pos_suffix, inv_freq, HD)
             probs = self._attend(l, P, Ss, P + Ss, self.qcode, self.kcode, want_probs=tape is not None)
             if tape is not None:  # q_buf / att_buf are shared by the layers: this layer's suffix rows, compact [B Ss, H HD]
                 q_rows = torch.empty((B * Ss, NQ), dtype=BF16, device=self.dev)
                 att_rows = torch.empty((B * Ss, NQ), dtype=BF16, device=self.dev)
-                ops._copy_rows(self.q_buf, q_rows, B, Ss, NQ, S_ld * NQ, P, NQ, Ss * NQ, 0, NQ)
-                ops._copy_rows(self.att_buf, att_rows, B, Ss, NQ, S_ld * NQ, P, NQ, Ss * NQ, 0, NQ)
+                ops.copy_rows(self.q_buf[:, P : P + Ss], q_rows.view(B, Ss, NQ))
+                ops.copy_rows(self.att_buf[:, P : P + Ss], att_rows.view(B, Ss, NQ))
             xs = self._oproj(at.o_proj, Ss, P, residual=xs, gate=gate1)
             x_mid = xs
             hs, gate2, rstd2 = norm(xs, layer.post_attention_layernorm, m2)
@@ -718,7 +718,7 @@ class InferenceEngine:
             tape.append((xs, rstd_f, pre))
         if Ss != Hs:  # pi0: the action rows of every sample, compact
             act = torch.empty((B * Hs, De), dtype=BF16, device=self.dev)
-            ops._copy_rows(out, act, B, Hs, De, Ss * De, Ss - Hs, De, Hs * De, 0, De)
+            ops.copy_rows(out.view(B, Ss, De)[:, Ss - Hs :], act.view(B, Hs, De))
             out = act
         v = ops.linear_f32(ops.cast(out, F32), model.action_out_proj.weight, model.action_out_proj.bias)
         return v.view(B, Hs, self.A)
@@ -777,7 +777,7 @@ class InferenceEngine:
         if Ss != Hs:  # pi0: action_out_proj read the last Hs rows of every sample; the state row's output has no reader
             act = dout
             dout = torch.zeros((M, De), dtype=BF16, device=dev)
-            ops._copy_rows(act, dout, B, Hs, De, Hs * De, 0, De, Ss * De, Ss - Hs, De)
+            ops.copy_rows(act.view(B, Hs, De), dout.view(B, Ss, De)[:, Ss - Hs :])
         x_last, rstd_f, pre = tape[-1]
         dxs = self._adarms_bwd(dout, x_last, mf, rstd_f, None)
         c0 = P // 8 * 8  # the suffix key columns, from a 16-byte boundary of the probability rows
@@ -799,8 +799,8 @@ class InferenceEngine:
             for dst, a_t, b_t in ((dkv[0], dS, q_rows), (dkv[1], probs, datt)):  # dK = dS^T Q, dV = P^T dO over the suffix key columns
                 gemm(a_t, b_t, dst, M=kw, N=HD, K=R, a_kc=False, b_kc=False, lda=S_ld, ldb=HD, ldc=HD, batch=B, sA=(R * S_ld, 0),
                      sB=(R * HD, 0), sC=(kw * HD, 0), a_off_elems=c0)
-            ops.rope_(dq, self.pos_suffix, self._inv_freq, B, Ss, Ss, 0, H, HD, inverse=True)
-            ops.rope_(dkv[0], self.pos_suffix, self._inv_freq, B, Ss, kw, koff, 1, HD, inverse=True)
+            ops.rope_(dq.view(B, Ss, NQ), self.pos_suffix, self._inv_freq, HD, inverse=True)
+            ops.rope_(dkv[0][:, koff : koff + Ss], self.pos_suffix, self._inv_freq, HD, inverse=True)
             dhs = self._dgrad(dq, at.q_proj.weight)
             self._dgrad(dkv[0], at.k_proj.weight, a_map=(Ss, kw, koff), into=dhs)
             self._dgrad(dkv[1], at.v_proj.weight, a_map=(Ss, kw, koff), into=dhs)
@@ -812,7 +812,7 @@ class InferenceEngine:
         # pi0: rows 1 .. Hs of xs = bf16(y),  y = W_out silu(pre) + b_out,  pre = w_act a + tvec[step],  a = action_in_proj(x_t)
         Ma = B * Hs
         dy = torch.empty((Ma, De), dtype=BF16, device=dev)
-        ops._copy_rows(dxs, dy, B, Hs, De, Ss * De, Ss - Hs, De, Hs * De, 0, De)
+        ops.copy_rows(dxs.view(B, Ss, De)[:, Ss - Hs :], dy.view(B, Hs, De))
         dh = torch.empty((Ma, De), dtype=F32, device=dev)
         ops.gemm_f32(ops.cast(dy, F32), De, 1, model.action_time_mlp_out.weight, De, 1, dh, Ma, De, De)
         dpre = ops.silu_bwd_f32(dh, pre)

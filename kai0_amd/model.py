@@ -926,10 +926,10 @@ class PrefixAssembleFn(torch.autograd.Function):
                              f"one [B={B}, {ncam} x {n_img} + {T}, D] sequence (projector width must equal the PaliGemma width)")
         P = ncam * n_img + T
         out = torch.empty((B * P, D), dtype=BF16, device=feats.device)
-        for c in range(ncam):
-            src = feats[c * B * n_img :]
-            ops._copy_rows(src, out, B, n_img, D, n_img * D, 0, D, P * D, c * n_img, D)
-        ops._copy_rows(lang, out, B, T, D, T * D, 0, D, P * D, ncam * n_img, D)
+        rows = out.view(B, P, D)
+        for c, cam in enumerate(feats.view(ncam, B, n_img, D)):
+            ops.copy_rows(cam, rows[:, c * n_img : (c + 1) * n_img])
+        ops.copy_rows(lang.view(B, T, D), rows[:, ncam * n_img :])
         ctx.dims = (B, ncam, n_img, T, D, P)
         return out
 
@@ -939,8 +939,8 @@ class PrefixAssembleFn(torch.autograd.Function):
         dout = dout.contiguous()
         dfeats = torch.empty((ncam * B * n_img, D), dtype=BF16, device=dout.device)
         dlang = torch.empty((B * T, D), dtype=BF16, device=dout.device)
-        for c in range(ncam):
-            dst = dfeats[c * B * n_img :]
-            ops._copy_rows(dout, dst, B, n_img, D, P * D, c * n_img, D, n_img * D, 0, D)
-        ops._copy_rows(dout, dlang, B, T, D, P * D, ncam * n_img, D, T * D, 0, D)
+        rows = dout.view(B, P, D)
+        for c, cam in enumerate(dfeats.view(ncam, B, n_img, D)):
+            ops.copy_rows(rows[:, c * n_img : (c + 1) * n_img], cam)
+        ops.copy_rows(rows[:, ncam * n_img :], dlang.view(B, T, D))
         return dfeats, dlang, None, None, None, None

@@ -17,6 +17,7 @@ import contextlib
 import ctypes as C
 import os
 import math
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -1380,43 +1381,123 @@ def patch_embed(img, w, b, pos, patch):
 
 
 # --------------------------------------------------------------------------------------------- attention
-def _copy_rows(src, dst, Bn, rows, D, sbs, sr0, sld, dbs, dr0, dld):
-    _lib.call("kai0_copy_rows_bf16", src.data_ptr(), dst.data_ptr(), Bn, rows, D, sbs, sr0, sld, dbs, dr0, dld, _stream())
+# The strided row movers (kai0_copy_rows_bf16, kai0_pack_rows, kai0_rope_*) take their rows as torch VIEWS: `q_all[:, r0 : r0 + L]`,
+# `dq.unflatten(0, (B, L))`, `dkv[0][:, koff : koff + Ss]`.  The view carries the base address, both strides and the shape; `_rows` is the
+# one place that turns it into the numbers of the C interface.
+def _rows(t, name: str = "view", dtype=BF16):
+    """(data_ptr, batch stride, row stride, B, rows, cols) of a [B, rows, cols] or [rows, cols] view whose last stride is 1 (strides in
+    elements; 2-D: B = 1 and the batch stride that of dense rows).  ValueError, naming the argument, for anything else."""
+    if not isinstance(t, torch.Tensor) or t.dim() not in (2, 3):
+        raise ValueError(f"{name}: expected a [B, rows, cols] or [rows, cols] view, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name}: expected {dtype}, got {t.dtype}")
+    if min(t.shape) <= 0:
+        raise ValueError(f"{name}: empty shape {tuple(t.shape)}")
+    if t.stride(-1) != 1:
+        raise ValueError(f"{name}: last stride {t.stride(-1)}, the movers need contiguous columns")
+    rows, cols = t.shape[-2:]
+    ld = t.stride(-2)
+    Bn, bs = (t.shape[0], t.stride(0)) if t.dim() == 3 else (1, rows * ld)
+    return t.data_ptr(), bs, ld, Bn, rows, cols
 
 
-def rope_(x, pos, inv_freq, Bn, S, s_ld, row0, H, HD, inverse=False):
-    _lib.call("kai0_rope_inplace", x.data_ptr(), pos.data_ptr(), inv_freq.data_ptr(), Bn, S, s_ld, row0, H, HD,
-              int(inverse), _stream())  # fmt: skip
+def _row0(t, bs: int, ld: int) -> int:
+    """The first row of a view within its batch entry, for the entry points that take (base, first row) instead of an address: any
+    split with row0 * ld inside the storage offset names the same memory, this one gives `x[:, r0 : r0 + n]` its r0."""
+    return t.storage_offset() % bs // ld if t.dim() == 3 and bs > 0 and ld > 0 else 0
 
 
-def rope2_(x, H, x2, H2, pos, inv_freq, Bn, S, s_ld, row0, HD):
-    """kai0_rope_inplace2: rotate q (H heads) and k (H2 heads) of one layer in place with one launch."""
-    _lib.call("kai0_rope_inplace2", x.data_ptr(), H, x2.data_ptr(), H2, pos.data_ptr(), inv_freq.data_ptr(), Bn, S, s_ld, row0, HD,
-              _stream())
+def copy_rows(src, dst):
+    """dst[b, r, :] = src[b, r, :] between two bf16 row views of one shape (kai0_copy_rows_bf16)."""
+    sp, sbs, sld, Bn, rows, cols = _rows(src, "copy_rows: src")
+    dp, dbs, dld, *dshape = _rows(dst, "copy_rows: dst")
+    if dshape != [Bn, rows, cols]:
+        raise ValueError(f"copy_rows: src {tuple(src.shape)} and dst {tuple(dst.shape)} differ in shape")
+    sr0, dr0 = _row0(src, sbs, sld), _row0(dst, dbs, dld)
+    _lib.call("kai0_copy_rows_bf16", sp - 2 * sr0 * sld, dp - 2 * dr0 * dld, Bn, rows, cols, sbs, sr0, sld, dbs, dr0, dld, _stream())
 
 
-def rope_copy(src_t, dst_t, pos, inv_freq, Bn, S, H, HD, *, src, dst, pos_bs, pos_off=0, inverse=False):
-    """dst[b][dst_row0 + s] = rope(src[b][src_row0 + s], pos[b][pos_off + s]) (kai0_rope_copy).  `src` / `dst` =
-    (batch stride, row stride, first row) in elements / rows of the tensors' data pointers (which may be column slices)."""
-    sbs, sld, sr0 = src
-    dbs, dld, dr0 = dst
-    _lib.call("kai0_rope_copy", src_t.data_ptr() + 2 * sr0 * sld, dst_t.data_ptr() + 2 * dr0 * dld, pos.data_ptr() + 4 * pos_off,
-              inv_freq.data_ptr(), Bn, S, H, HD, sbs, sld, dbs, dld, pos_bs, int(inverse), _stream())  # fmt: skip
+def _rope_dense(x, name: str, HD: int, pos):
+    """kai0_rope_inplace's layout of a view: dense rows of H = cols / HD heads, rows `row0 ..` of every `s_ld` -> (base, B, S, s_ld, row0, H)."""
+    ptr, bs, ld, Bn, S, cols = _rows(x, name)
+    if ld != cols or cols % HD != 0 or (Bn > 1 and bs % cols != 0):
+        raise ValueError(f"{name}: rows of {cols} elements with strides ({bs}, {ld}) do not fit the in-place entry point "
+                         f"(dense rows of whole heads of {HD}); use rope_copy")
+    if tuple(pos.shape) != (Bn, S) or not pos.is_contiguous() or pos.dtype != torch.int32:
+        raise ValueError(f"{name}: positions must be contiguous int32 [{Bn}, {S}], got {pos.dtype} {tuple(pos.shape)} strides {pos.stride()}")
+    row0 = _row0(x, bs, ld)
+    return ptr - 2 * row0 * cols, Bn, S, bs // cols, row0, cols // HD
 
 
-def pack_rows(parts, HD: int, pos=None, pos_bs: int = 0, inv_freq=None):
-    """kai0_pack_rows: up to 12 strided row moves in one launch.  parts = [(src | None, src element offset, dst, dst element offset,
-    (src batch stride, src row stride), (dst batch stride, dst row stride), B, rows, cols, mode, pos_off)] with mode 0 copy,
-    1 RoPE, 2 inverse RoPE, 3 zero fill."""
-    for c0 in range(0, len(parts), 12):
-        chunk = parts[c0 : c0 + 12]
+def rope_(x, pos, inv_freq, HD: int, inverse: bool = False):
+    """Rotate the rows of the view x [B, S, H * HD] in place with pos [B, S] (kai0_rope_inplace)."""
+    base, Bn, S, s_ld, row0, H = _rope_dense(x, "rope_: x", HD, pos)
+    _lib.call("kai0_rope_inplace", base, pos.data_ptr(), inv_freq.data_ptr(), Bn, S, s_ld, row0, H, HD, int(inverse), _stream())
+
+
+def rope2_(q, k, pos, inv_freq, HD: int):
+    """kai0_rope_inplace2: rotate q [B, S, H * HD] and k [B, S, H2 * HD], the same rows of equally padded buffers, in place with one launch."""
+    base, Bn, S, s_ld, row0, H = _rope_dense(q, "rope2_: q", HD, pos)
+    base2, *geom2, H2 = _rope_dense(k, "rope2_: k", HD, pos)
+    if geom2 != [Bn, S, s_ld, row0]:
+        raise ValueError(f"rope2_: q {tuple(q.shape)} and k {tuple(k.shape)} are not the same rows of equally padded buffers")
+    _lib.call("kai0_rope_inplace2", base, H, base2, H2, pos.data_ptr(), inv_freq.data_ptr(), Bn, S, s_ld, row0, HD, _stream())
+
+
+def rope_copy(src, dst, pos, inv_freq, HD: int, inverse: bool = False):
+    """dst[b, s] = rope(src[b, s], pos[b, s]) between row views [B, S, H * HD] (column and row slices allowed) with a view pos [B, S]
+    of the positions (kai0_rope_copy)."""
+    sp, sbs, sld, Bn, S, cols = _rows(src, "rope_copy: src")
+    dp, dbs, dld, *dshape = _rows(dst, "rope_copy: dst")
+    if dshape != [Bn, S, cols] or cols % HD != 0:
+        raise ValueError(f"rope_copy: src {tuple(src.shape)} / dst {tuple(dst.shape)}: one shape of whole heads of {HD} expected")
+    if tuple(pos.shape) != (Bn, S) or pos.stride(1) != 1 or pos.dtype != torch.int32:
+        raise ValueError(f"rope_copy: positions must be an int32 [{Bn}, {S}] view with unit last stride, got {pos.dtype} {tuple(pos.shape)}")
+    _lib.call("kai0_rope_copy", sp, dp, pos.data_ptr(), inv_freq.data_ptr(), Bn, S, cols // HD, HD, sbs, sld, dbs, dld, pos.stride(0),
+              int(inverse), _stream())
+
+
+COPY, ROPE, ROPE_INV, ZERO = 0, 1, 2, 3  # kai0_pack_part.mode (kai0hip.h)
+
+
+class Move(NamedTuple):
+    """One part of a kai0_pack_rows launch: dst[b, r, :] = kind(src[b, r, :]) between row views of one shape.  ROPE / ROPE_INV rotate
+    per head with position pos[b, pos_off + r]; ZERO takes src = None."""
+
+    src: Optional[torch.Tensor]
+    dst: torch.Tensor
+    kind: int
+    pos_off: int = 0
+
+
+def pack_parts(moves):
+    """The kai0_pack_part arrays of a list of moves, at most 12 per launch (no device work: addresses and strides only)."""
+    chunks = []
+    for c0 in range(0, len(moves), 12):
+        chunk = moves[c0 : c0 + 12]
         arr = (_lib.PackPart * len(chunk))()
-        for a, (src, soff, dst, doff, (sbs, sld), (dbs, dld), Bn, rows, cols, mode, pos_off) in zip(arr, chunk):
-            a.src = None if src is None else src.data_ptr() + 2 * soff
-            a.dst = dst.data_ptr() + 2 * doff
-            a.src_bs, a.src_ld, a.dst_bs, a.dst_ld = sbs, sld, dbs, dld
-            a.B, a.rows, a.cols, a.mode, a.pos_off = Bn, rows, cols, mode, pos_off
-        _lib.call("kai0_pack_rows", C.addressof(arr), len(chunk), _p(pos), pos_bs, _p(inv_freq), HD, _stream())
+        for a, (i, m) in zip(arr, enumerate(chunk, c0)):
+            if m.kind not in (COPY, ROPE, ROPE_INV, ZERO):
+                raise ValueError(f"pack_rows: move {i}: unknown kind {m.kind!r}")
+            a.dst, a.dst_bs, a.dst_ld, a.B, a.rows, a.cols = _rows(m.dst, f"pack_rows: move {i}: dst")
+            if m.kind == ZERO:
+                if m.src is not None:
+                    raise ValueError(f"pack_rows: move {i}: ZERO takes src=None")
+            else:
+                a.src, a.src_bs, a.src_ld, *sshape = _rows(m.src, f"pack_rows: move {i}: src")
+                if sshape != [a.B, a.rows, a.cols]:
+                    raise ValueError(f"pack_rows: move {i}: src {tuple(m.src.shape)} and dst {tuple(m.dst.shape)} differ in shape")
+            a.mode, a.pos_off = m.kind, m.pos_off
+        chunks.append(arr)
+    return chunks
+
+
+def pack_rows(moves, HD: int, pos=None, inv_freq=None):
+    """kai0_pack_rows: the moves (`Move`) in launches of up to 12; pos [B, S] int32 (its batch stride is taken from the tensor) and
+    inv_freq for the rotating kinds."""
+    pos_bs = 0 if pos is None else pos.stride(0)
+    for arr in pack_parts(moves):
+        _lib.call("kai0_pack_rows", C.addressof(arr), len(arr), _p(pos), pos_bs, _p(inv_freq), HD, _stream())
 
 
 def round_up(x: int, m: int) -> int:
@@ -1514,18 +1595,18 @@ def _joint_attention_grads(cfg, pos, inv_freq, dq_all, dk_all, dv_all):
     (Takes what it needs of the saved tensors from the caller: under activation checkpointing they can be unpacked once only.)"""
     Bn, S, S_ld, H, HD, seg_lens, scale, recompute = cfg
     dev = dq_all.device
-    grads, parts = [], []
+    grads, moves = [], []
     r0 = 0
     for Li in seg_lens:
-        W3 = (H + 2) * HD  # dq | dk | dv as column slices of one [Bn*Li, W3] buffer (see fused_columns)
-        dq, dk, dv = fused_columns(Bn * Li, (H * HD, HD, HD), dev)
+        dq, dk, dv = fused_columns(Bn * Li, (H * HD, HD, HD), dev)  # dq | dk | dv as column slices of one [Bn*Li, (H + 2) HD] buffer
+        seg = slice(r0, r0 + Li)
         # the inverse rotation is applied while the segment's rows are gathered out of the joint gradient buffers
-        parts.append((dq_all, r0 * H * HD, dq, 0, (S_ld * H * HD, H * HD), (Li * W3, W3), Bn, Li, H * HD, 2, r0))
-        parts.append((dk_all, r0 * HD, dk, 0, (dk_all.stride(0), HD), (Li * W3, W3), Bn, Li, HD, 2, r0))
-        parts.append((dv_all, r0 * HD, dv, 0, (dv_all.stride(0), HD), (Li * W3, W3), Bn, Li, HD, 0, 0))
+        moves.append(Move(dq_all[:, seg], dq.unflatten(0, (Bn, Li)), ROPE_INV, r0))
+        moves.append(Move(dk_all[:, seg], dk.unflatten(0, (Bn, Li)), ROPE_INV, r0))
+        moves.append(Move(dv_all[:, seg], dv.unflatten(0, (Bn, Li)), COPY))
         grads += [dq, dk, dv]
         r0 += Li
-    pack_rows(parts, HD, pos, S, inv_freq)
+    pack_rows(moves, HD, pos, inv_freq)
     return (None, None, None, None, None, None, None, *grads)
 
 
@@ -1549,34 +1630,33 @@ class JointAttentionFn(torch.autograd.Function):
         v_all = torch.empty((Bn, S_ld, HD), dtype=BF16, device=dev)
         # one launch: q / k of every segment rotated on their way into the joint buffers, v copied, and the padding rows cleared
         # (only they need defined contents: they enter the dK / dV GEMMs multiplied by P = 0)
-        parts = []
+        moves = []
         r0 = 0
         for i in range(nseg):
             Li = seg_lens[i]
-            parts.append((qs[i], 0, q_all, r0 * H * HD, (Li * qs[i].stride(0), qs[i].stride(0)), (S_ld * H * HD, H * HD), Bn, Li, H * HD, 1, r0))
-            parts.append((ks[i], 0, k_all, r0 * HD, (Li * ks[i].stride(0), ks[i].stride(0)), (S_ld * HD, HD), Bn, Li, HD, 1, r0))
-            parts.append((vs[i], 0, v_all, r0 * HD, (Li * vs[i].stride(0), vs[i].stride(0)), (S_ld * HD, HD), Bn, Li, HD, 0, 0))
+            seg = slice(r0, r0 + Li)
+            moves.append(Move(qs[i].unflatten(0, (Bn, Li)), q_all[:, seg], ROPE, r0))
+            moves.append(Move(ks[i].unflatten(0, (Bn, Li)), k_all[:, seg], ROPE, r0))
+            moves.append(Move(vs[i].unflatten(0, (Bn, Li)), v_all[:, seg], COPY))
             r0 += Li
         if S_ld > S:
-            parts.append((None, 0, q_all, S * H * HD, (0, 0), (S_ld * H * HD, H * HD), Bn, S_ld - S, H * HD, 3, 0))
-            parts.append((None, 0, k_all, S * HD, (0, 0), (S_ld * HD, HD), Bn, S_ld - S, HD, 3, 0))
-            parts.append((None, 0, v_all, S * HD, (0, 0), (S_ld * HD, HD), Bn, S_ld - S, HD, 3, 0))
-        pack_rows(parts, HD, pos, S, inv_freq)
+            moves += [Move(None, t[:, S:], ZERO) for t in (q_all, k_all, v_all)]
+        pack_rows(moves, HD, pos, inv_freq)
         scale = HD**-0.5
         # one pass, no stored probabilities: the backward recomputes them from lse (kai0_attn_bwd_dq2), which stages the key codes of
         # up to 2048 keys in LDS (AB_KC_MAX in attn_bwd.hip).  Longer sequences take the two-pass forward that stores P and the
         # backward that reads it (kai0_attn_bwd_dq): a selection from the input size alone
         recompute = S <= 2048
         att, probs = mqa_attention_fwd(q_all, k_all, v_all, qcode, kcode, Bn, S, 0, S, S_ld, H, HD, scale, want_lse=recompute)
-        outs, parts = [], []
+        outs, moves = [], []
         r0 = 0
         for i in range(nseg):
             Li = seg_lens[i]
             o = torch.empty((Bn * Li, H * HD), dtype=BF16, device=dev)
-            parts.append((att, r0 * H * HD, o, 0, (S_ld * H * HD, H * HD), (Li * H * HD, H * HD), Bn, Li, H * HD, 0, 0))
+            moves.append(Move(att[:, r0 : r0 + Li], o.view(Bn, Li, H * HD), COPY))
             outs.append(o)
             r0 += Li
-        pack_rows(parts, HD)
+        pack_rows(moves, HD)
         ctx.save_for_backward(q_all, k_all, v_all, probs, pos, inv_freq, att, qcode, kcode)
         ctx.cfg = (Bn, S, S_ld, H, HD, seg_lens, scale, recompute)
         return tuple(outs)
@@ -1593,14 +1673,14 @@ class JointAttentionFn(torch.autograd.Function):
             pd = torch.empty((2, Bn, M, S_ld), dtype=BF16, device=dev)
             lse, probs, dscores = probs, pd[0], pd[1]
         datt = torch.empty((Bn, S_ld, H * HD), dtype=BF16, device=dev)
-        parts = []
+        moves = []
         r0 = 0
         for i, Li in enumerate(seg_lens):
-            parts.append((douts[i].contiguous(), 0, datt, r0 * H * HD, (Li * H * HD, H * HD), (S_ld * H * HD, H * HD), Bn, Li, H * HD, 0, 0))
+            moves.append(Move(douts[i].contiguous().view(Bn, Li, H * HD), datt[:, r0 : r0 + Li], COPY))
             r0 += Li
         if S_ld > S:
-            parts.append((None, 0, datt, S * H * HD, (0, 0), (S_ld * H * HD, H * HD), Bn, S_ld - S, H * HD, 3, 0))
-        pack_rows(parts, HD)
+            moves.append(Move(None, datt[:, S:], ZERO))
+        pack_rows(moves, HD)
         if recompute:
             # query side first: it (re)produces P for the dV GEMM below — S, P = exp(S - lse), dP, dS, dQ in one launch
             d = AttnBwdDesc()

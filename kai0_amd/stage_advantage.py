@@ -213,8 +213,8 @@ class ValueAnnotator:
                 run = 1
                 while g + run < g1 and ring_slot(g + run, ep["interval"], self.batch_size) == s0 + run:
                     run += 1
-                rows = run * NCAM * n_img
-                ops._copy_rows(feats[(g - g0) * NCAM :], bank[s0 * NCAM :], 1, rows, D, rows * D, 0, D, rows * D, 0, D)
+                i0, n = (g - g0) * NCAM, run * NCAM  # images of the run, n_img rows of D each
+                ops.copy_rows(feats[i0 : i0 + n].view(n * n_img, D), bank[s0 * NCAM : s0 * NCAM + n].view(n * n_img, D))
                 g += run
         ep["filled"] = hi
 

@@ -253,7 +253,7 @@ def test_gemm_rope_epilogue_is_bit_identical_to_gemm_then_rope(ops, B, P, S_ld, 
     q0, k0, v0 = bufs()
     segs = lambda q, k, v: [(q, NQ, 0), (k, HD, NQ), (v, HD, NQ + HD)]  # noqa: E731
     ops.gemm(x, w, q0, M=M, N=NQ + 2 * HD, K=D, lda=D, ldb=D, ldc=NQ, c_map=(P, S_ld, 0), segs=segs(q0, k0, v0))
-    ops.rope2_(q0, H, k0, 1, pos, inv_freq, B, P, S_ld, 0, HD)
+    ops.rope2_(q0[:, :P], k0[:, :P], pos, inv_freq, HD)
     q1, k1, v1 = bufs()
     perm = ops.rope_permutation(NQ + 2 * HD, NQ + HD).to(dev())
     cos, sin = ops.rope_table(pos.reshape(-1), inv_freq)
@@ -577,7 +577,7 @@ def test_rope(ops, H, HD):
     ref = x.clone()
     ref[:, row0 : row0 + S] = _rope_ref(x[:, row0 : row0 + S].reshape(B, S, H, HD), pos, inv).reshape(B, S, H * HD)
     y = x.clone()
-    ops.rope_(y, pos, inv, B, S, S_ld, row0, H, HD)
+    ops.rope_(y[:, row0 : row0 + S], pos, inv, HD)
     # cos/sin of a large angle may differ by one bf16 ulp between libms: allow a handful of 1-ulp flips
     mism = (y != ref).float().mean().item()
     assert mism < 2e-2, f"rope mismatch fraction {mism}"
@@ -966,8 +966,8 @@ def test_skinny_qkv_rope_segments(ops):
     v_ref = torch.zeros(B, S_ld, HD, dtype=BF16, device=dev())
     for w_, dst, width in ((wq, q_ref, H * HD), (wk, k_ref, HD), (wv, v_ref, HD)):
         ops.gemm(x, w_, dst, M=M, N=width, K=K, lda=K, ldb=K, ldc=width, c_map=(Hs, S_ld, P))
-    ops.rope_(q_ref, pos, inv_freq, B, Hs, S_ld, P, H, HD)
-    ops.rope_(k_ref, pos, inv_freq, B, Hs, S_ld, P, 1, HD)
+    ops.rope_(q_ref[:, P : P + Hs], pos, inv_freq, HD)
+    ops.rope_(k_ref[:, P : P + Hs], pos, inv_freq, HD)
     # fused path
     q = torch.zeros_like(q_ref)
     k = torch.zeros_like(k_ref)
@@ -1585,16 +1585,18 @@ def test_pack_rows_equals_the_separate_rope_copy_and_fill_launches(ops, HD, H):
         t[:, S:].zero_()
     parts, r0 = [], 0
     for i, L in enumerate(lens):
-        ops.rope_copy(qs[i], ref[0], pos, inv, B, L, H, HD, src=(L * H * HD, H * HD, 0), dst=(S_ld * H * HD, H * HD, r0), pos_bs=S, pos_off=r0)
-        ops.rope_copy(ks[i], ref[1], pos, inv, B, L, 1, HD, src=(L * HD, HD, 0), dst=(S_ld * HD, HD, r0), pos_bs=S, pos_off=r0)
-        ops._copy_rows(vs[i], ref[2], B, L, HD, L * HD, 0, HD, S_ld * HD, r0, HD)
-        parts.append((qs[i], 0, got[0], r0 * H * HD, (L * H * HD, H * HD), (S_ld * H * HD, H * HD), B, L, H * HD, 1, r0))
-        parts.append((ks[i], 0, got[1], r0 * HD, (L * HD, HD), (S_ld * HD, HD), B, L, HD, 1, r0))
-        parts.append((vs[i], 0, got[2], r0 * HD, (L * HD, HD), (S_ld * HD, HD), B, L, HD, 0, 0))
+        seg = slice(r0, r0 + L)
+        q, k, v = (t[i].view(B, L, -1) for t in (qs, ks, vs))
+        ops.rope_copy(q, ref[0][:, seg], pos[:, seg], inv, HD)
+        ops.rope_copy(k, ref[1][:, seg], pos[:, seg], inv, HD)
+        ops.copy_rows(v, ref[2][:, seg])
+        parts.append(ops.Move(q, got[0][:, seg], ops.ROPE, r0))
+        parts.append(ops.Move(k, got[1][:, seg], ops.ROPE, r0))
+        parts.append(ops.Move(v, got[2][:, seg], ops.COPY))
         r0 += L
-    for t, w in zip(got, (H * HD, HD, HD)):
-        parts.append((None, 0, t, S * w, (0, 0), (S_ld * w, w), B, S_ld - S, w, 3, 0))
-    ops.pack_rows(parts, HD, pos, S, inv)
+    for t in got:
+        parts.append(ops.Move(None, t[:, S:], ops.ZERO))
+    ops.pack_rows(parts, HD, pos, inv)
     for a, b in zip(ref, got):
         assert torch.equal(a, b)
     # the way back: inverse rotation while a segment's rows are gathered into column slices of one buffer
@@ -1603,13 +1605,15 @@ def test_pack_rows_equals_the_separate_rope_copy_and_fill_launches(ops, HD, H):
     L = lens[1]
     ref_b = torch.full((B * L, W3), nan, dtype=BF16, device=dev())
     got_b = ref_b.clone()
-    ops.rope_copy(ref[0], ref_b, pos, inv, B, L, H, HD, src=(S_ld * H * HD, H * HD, r0), dst=(L * W3, W3, 0), pos_bs=S, pos_off=r0, inverse=True)
-    ops.rope_copy(ref[1], ref_b[:, H * HD :], pos, inv, B, L, 1, HD, src=(S_ld * HD, HD, r0), dst=(L * W3, W3, 0), pos_bs=S, pos_off=r0,
-                  inverse=True)
-    ops._copy_rows(ref[2], ref_b[:, (H + 1) * HD :], B, L, HD, S_ld * HD, r0, HD, L * W3, 0, W3)
-    ops.pack_rows([(got[0], r0 * H * HD, got_b, 0, (S_ld * H * HD, H * HD), (L * W3, W3), B, L, H * HD, 2, r0),
-                   (got[1], r0 * HD, got_b[:, H * HD :], 0, (S_ld * HD, HD), (L * W3, W3), B, L, HD, 2, r0),
-                   (got[2], r0 * HD, got_b[:, (H + 1) * HD :], 0, (S_ld * HD, HD), (L * W3, W3), B, L, HD, 0, 0)], HD, pos, S, inv)
+    seg = slice(r0, r0 + L)
+    cols = (slice(0, H * HD), slice(H * HD, (H + 1) * HD), slice((H + 1) * HD, W3))  # dq | dk | dv
+    rq, rk, rv = (ref_b.view(B, L, W3)[:, :, c] for c in cols)
+    gq, gk, gv = (got_b.view(B, L, W3)[:, :, c] for c in cols)
+    ops.rope_copy(ref[0][:, seg], rq, pos[:, seg], inv, HD, inverse=True)
+    ops.rope_copy(ref[1][:, seg], rk, pos[:, seg], inv, HD, inverse=True)
+    ops.copy_rows(ref[2][:, seg], rv)
+    ops.pack_rows([ops.Move(got[0][:, seg], gq, ops.ROPE_INV, r0), ops.Move(got[1][:, seg], gk, ops.ROPE_INV, r0),
+                   ops.Move(got[2][:, seg], gv, ops.COPY)], HD, pos, inv)
     assert torch.equal(ref_b, got_b)
 
 
@@ -1620,10 +1624,10 @@ def test_rope_two_tensors_in_one_launch(ops):
     pos = torch.randint(0, 900, (B, S), dtype=torch.int32, device=dev())
     inv = (1.0 / (10000.0 ** (torch.arange(0, HD, 2, dtype=torch.float32) / HD))).to(dev())
     q1, k1 = q.clone(), k.clone()
-    ops.rope_(q1, pos, inv, B, S, S_ld, 0, H, HD)
-    ops.rope_(k1, pos, inv, B, S, S_ld, 0, 1, HD)
+    ops.rope_(q1[:, :S], pos, inv, HD)
+    ops.rope_(k1[:, :S], pos, inv, HD)
     q2, k2 = q.clone(), k.clone()
-    ops.rope2_(q2, H, k2, 1, pos, inv, B, S, S_ld, 0, HD)
+    ops.rope2_(q2[:, :S], k2[:, :S], pos, inv, HD)
     assert torch.equal(q1, q2) and torch.equal(k1, k2) and not torch.equal(q1, q)
 
 
@@ -1640,3 +1644,27 @@ def test_device_resize_on_the_gpu_is_pillow_bit_for_bit():
         got = device_resize.resize_with_pad_u8(torch.from_numpy(frames).to(dev()), H, W)
         assert got.is_cuda and got.dtype == torch.uint8
         assert np.array_equal(got.cpu().numpy(), image_tools.resize_with_pad(frames, H, W))
+
+
+def test_row_movers_between_views_sliced_in_rows_and_columns(ops):
+    """copy_rows, and pack_rows with a COPY and a ZERO move, between views that take 3 of 5 rows and 8 of 24 columns: the destination
+    view equals torch's dst_view.copy_(src_view) (zeros for ZERO), and every element outside it keeps the sentinel."""
+    B, HD = 2, 8
+    src = rnd(B, 5, 24, seed=5)
+    sview = src[:, 1:4, 16:24]
+    view = lambda t: t[:, 2:5, 8:16]  # noqa: E731
+    zview = lambda t: t[:, 0:3, 0:8]  # noqa: E731
+    sentinel = torch.full((B, 5, 24), -7.0, dtype=BF16, device=dev())
+
+    ref = sentinel.clone()
+    view(ref).copy_(sview)
+    got = sentinel.clone()
+    ops.copy_rows(sview, view(got))
+    assert torch.equal(got, ref) and torch.equal(view(got), sview)
+
+    ref_z = ref.clone()
+    zview(ref_z).zero_()
+    got = sentinel.clone()
+    ops.pack_rows([ops.Move(sview, view(got), ops.COPY), ops.Move(None, zview(got), ops.ZERO)], HD)
+    assert torch.equal(got, ref_z) and torch.equal(view(got), sview) and not zview(got).any()
+    assert torch.equal(src, rnd(B, 5, 24, seed=5))  # the source is only read

@@ -336,8 +336,8 @@ def _sweep_pi05_as_merged(eng, cot, tape, step, mods, mf):
         for dst, a_t, b_t in ((dkv[0], dS, q_rows), (dkv[1], probs, datt)):
             gemm(a_t, b_t, dst, M=kw, N=HD, K=R, a_kc=False, b_kc=False, lda=S_ld, ldb=HD, ldc=HD, batch=B, sA=(R * S_ld, 0),
                  sB=(R * HD, 0), sC=(kw * HD, 0), a_off_elems=c0)
-        ops.rope_(dq, eng.pos_suffix, eng._inv_freq, B, Hs, Hs, 0, H, HD, inverse=True)
-        ops.rope_(dkv[0], eng.pos_suffix, eng._inv_freq, B, Hs, kw, koff, 1, HD, inverse=True)
+        ops.rope_(dq.view(B, Hs, NQ), eng.pos_suffix, eng._inv_freq, HD, inverse=True)
+        ops.rope_(dkv[0][:, koff : koff + Hs], eng.pos_suffix, eng._inv_freq, HD, inverse=True)
         dhs = eng._dgrad(dq, at.q_proj.weight)
         eng._dgrad(dkv[0], at.k_proj.weight, a_map=(Hs, kw, koff), into=dhs)
         eng._dgrad(dkv[1], at.v_proj.weight, a_map=(Hs, kw, koff), into=dhs)
